@@ -13,10 +13,15 @@ One "step" = one full generate pass over the local batch: before_generate (queue
 prompt) + 16 000 auto-regressive steps + mu-law expansion of the result, inputs resident in HBM.
 Clips shard over ranks with one weight broadcast and no other collective (weak scaling).
 
-The JSON line also carries
-  roofline     : HBM roofline of the dominant kernel, from HIP start/stop events on its launches
-  cpu_baseline : the reference ALGORITHM (oracle/torch_ref.py: naive full-window forward per step,
-                 Python loop) timed on this box's host cores on a bounded sample of the same workload.
+A plain run sets up, warms up, times the --steps passes and prints the line; everything that needs runs
+of its own is behind --full, which adds to the JSON line
+  roofline        : HBM roofline of the dominant kernel, from HIP start/stop events on its launches
+  strong_scaling  : wavenet_cfg4 only: BASELINE config 4's whole 256-clip job divided over the ranks
+  cpu_baseline    : the reference ALGORITHM (oracle/torch_ref.py: naive full-window forward per step,
+                    Python loop) timed on the host's cores on a bounded sample of the same workload
+  other_workloads : wavenet_cfg4 at N = 1 only: one short fenced run of every other workload
+--dump-outputs DIR writes what the last timed pass computed as DIR/<name>.npy (float32 / float64, at most
+64 MB in all: a fixed, seeded sample of the elements of larger outputs), rank 0's clips only.
 """
 import argparse
 import json
@@ -58,10 +63,13 @@ def parse():
     ap.add_argument("--seconds", type=float, default=1.0, help="generated audio per clip")
     ap.add_argument("--temperature", type=float, default=0.0,
                     help="> 0: sampled decode at this temperature (throughput only: the CPU check needs greedy decode)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-strong-leg", action="store_true", help="wavenet_cfg4: skip the strong-scaling leg (256 clips / N ranks) after the timed region")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also the roofline, the strong-scaling leg, the CPU baseline and "
+                    "the other workloads (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed pass computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-strong-leg", action="store_true", help="with --full, wavenet_cfg4: skip the strong-scaling leg (256 clips / N ranks) after the timed region")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline sample")
-    ap.add_argument("--no-others", action="store_true", help="wavenet_cfg4 at N = 1: skip the short passes of the other BASELINE workloads (`other_workloads` key)")
+    ap.add_argument("--no-others", action="store_true", help="with --full, wavenet_cfg4 at N = 1: skip the short passes of the other BASELINE workloads (`other_workloads` key)")
     ap.add_argument("--force-dist", action="store_true", help="with --gpus 1: initialise the RCCL process group of ONE rank all the same and run the path's "
                     "collectives (weight broadcast, fenced max-over-ranks clock) on it - what an N-GPU run does, on a 1-GPU box")
     ap.add_argument("--tuning", default="", help="execution switches of the plans of this run, NAME=VALUE[;NAME=VALUE...] (include/mmk.h `tuning`): "
@@ -150,6 +158,9 @@ class WaveNetJob:
         net.generate_block((self.idx, *self.cond), p, self.n_steps, **self.params)
         net.after_generate((self.idx,), None)
         self.audio_out = self.expand(self.idx)
+
+    def outputs(self):
+        return {"indices": self.idx, "audio": self.audio_out}
 
     def units_per_pass(self):
         return self.clips * self.n_steps
@@ -317,6 +328,9 @@ class SrnnJob:
         self.net.after_generate((self.idx,), None)
         self.audio_out = self.expand(self.idx)
 
+    def outputs(self):
+        return {"indices": self.idx, "audio": self.audio_out}
+
     def units_per_pass(self):
         return self.clips * self.n_steps
 
@@ -417,6 +431,9 @@ class S2SJob:
         self.net.before_generate((self.frames[:, :self.prompt_frames],), None)
         self.net.generate_block((self.frames,), self.prompt_frames, self.n_steps)
         self.net.after_generate((self.frames,), None)
+
+    def outputs(self):
+        return {"frames": self.frames}
 
     def units_per_pass(self):
         return self.clips * self.n_steps * self.samples_per_frame
@@ -522,6 +539,9 @@ class FeatureJob:
     def one_pass(self):
         self.out = self.f(self.x)
 
+    def outputs(self):
+        return {self.name: self.out}
+
     def units_per_pass(self):
         if self.name == "mulaw":
             return self.x.numel()
@@ -599,6 +619,9 @@ class StubJob:
 
     def one_pass(self):
         time.sleep(self.pass_s)
+
+    def outputs(self):
+        return {}
 
     def units_per_pass(self):
         return self.clips
@@ -757,6 +780,34 @@ def other_workloads(args, device, sync):
     return out
 
 
+DUMP_BYTES = 60 * 2 ** 20      # --dump-outputs: the data of all files together
+DUMP_SEED = 0
+
+
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: one DIR/<name>.npy per output of the last timed pass, float32 (float64 for float64 data and for integers float32 would
+    round).  When the outputs hold more than DUMP_BYTES, each keeps the same share of its elements, at flattened positions drawn with a fixed
+    seed and sorted: runs with the same arguments write the same positions, so two builds can be compared output for output."""
+    import numpy as np
+    prepared = {}
+    for name, t in outputs.items():
+        t = torch.view_as_real(t.detach()) if t.is_complex() else t.detach()
+        if t.is_floating_point():
+            dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+        else:
+            dtype = torch.float64 if t.numel() and int(t.abs().max()) > 2 ** 24 else torch.float32
+        prepared[name] = (t, dtype)
+    total = sum(t.numel() * (8 if dtype == torch.float64 else 4) for t, dtype in prepared.values())
+    share = min(1.0, DUMP_BYTES / total) if total else 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (t, dtype) in prepared.items():
+        if share < 1.0:
+            gen = torch.Generator().manual_seed(DUMP_SEED)
+            pos = torch.unique(torch.randint(0, t.numel(), (int(t.numel() * share),), generator=gen))    # sorted, each position once
+            t = t.reshape(-1)[pos.to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.to(dtype).cpu().numpy())
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -804,10 +855,13 @@ def main():
 
     from mimikit_amd.shard import timed_passes
     elapsed = timed_passes(job.one_pass, args.steps, args.warmup, sync)   # barrier + sync, MAX over ranks
+    if args.dump_outputs and rank == 0:
+        dump_outputs(job.outputs(), args.dump_outputs)
 
     units = job.units_per_pass() * args.steps * world
     value = units / elapsed
-    strong = strong_scaling_leg(args, device, rank, world, sync) if (args.workload == "wavenet_cfg4" and not args.no_strong_leg) else None
+    strong = (strong_scaling_leg(args, device, rank, world, sync) if (args.full and args.workload == "wavenet_cfg4" and not args.no_strong_leg)
+              else None)
     line = {
         "metric": "audio samples/sec generated (WaveNet 256-ch mu-law, 16kHz)" if args.workload == "wavenet_cfg4"
         else f"{job.unit} ({args.workload})",
@@ -827,14 +881,15 @@ def main():
             line["whole_step_hbm_roofline"] = {"samples_per_s_per_gpu_at_peak": round(roof, 1),
                                                "algorithmic_bytes_per_step": job.step_bytes(),
                                                "frac": round(value / world / roof, 5)}
-        roof = job.roofline()
+        roof = job.roofline() if args.full else None
         if roof is not None:
             line["roofline"] = roof
         if strong is not None:
             line["strong_scaling"] = strong
-        if world == 1 and not args.no_cpu_baseline and not args.temperature > 0:    # N = 1 only; the CPU leg re-checks the GREEDY samples
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.temperature > 0:    # N = 1 only; the CPU leg re-checks the GREEDY samples
             line["cpu_baseline"] = job.cpu_baseline(args.cpu_seconds)
-        if world == 1 and args.workload == "wavenet_cfg4" and not args.no_others and not args.clips and not args.temperature > 0 and not args.tuning:
+        if (args.full and world == 1 and args.workload == "wavenet_cfg4" and not args.no_others and not args.clips and not args.temperature > 0
+                and not args.tuning):
             line["other_workloads"] = other_workloads(args, device, sync)
         print(json.dumps(line), flush=True)
     if world > 1 or (args.force_dist and dist.is_initialized()):

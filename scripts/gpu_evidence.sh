@@ -38,24 +38,24 @@ tests)
 line)
   wl=$1; shift
   name=bench_$wl$(echo "$*" | grep -o -- "--clips [0-9]*" | sed 's/--clips /_clips/')
-  timeout 900 python bench.py --workload $wl "$@" > $O/$name.json 2> $O/$name.err
+  timeout 900 python bench.py --full --workload $wl "$@" > $O/$name.json 2> $O/$name.err
   echo "$name exit $?: $(fields $O/$name.json)"
   ;;
 lines)
   for wl in wavenet_cfg2 srnn_cfg3 s2s_cfg5 mulaw stft istft gla; do
     case $wl in mulaw|stft|istft) k="--steps 20 --warmup 5";; *) k="";; esac      # (sub-millisecond passes: two of them would time the launch overhead)
-    timeout 600 python bench.py --workload $wl --no-others $k > $O/bench_$wl.json 2> $O/bench_$wl.err
+    timeout 600 python bench.py --full --workload $wl --no-others $k > $O/bench_$wl.json 2> $O/bench_$wl.err
     echo "$wl exit $?: $(fields $O/bench_$wl.json)"
   done
   for n in 64 128 256; do
-    timeout 900 python bench.py --clips $n --no-cpu-baseline --no-strong-leg --no-others > $O/bench_wavenet_cfg4_clips$n.json 2> $O/bench_clips$n.err
+    timeout 900 python bench.py --full --clips $n --no-cpu-baseline --no-strong-leg --no-others > $O/bench_wavenet_cfg4_clips$n.json 2> $O/bench_clips$n.err
     echo "cfg4 clips $n exit $?: $(fields $O/bench_wavenet_cfg4_clips$n.json)"
   done
   ;;
 stats)
   wl=$1; shift
   cd /tmp; rm -rf $O/stats_$wl
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$wl -- python3 $R/bench.py --workload $wl --no-cpu-baseline --no-strong-leg --no-others "$@" > $O/stats_$wl.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$wl -- python3 $R/bench.py --full --workload $wl --no-cpu-baseline --no-strong-leg --no-others "$@" > $O/stats_$wl.log 2>&1
   echo "stats exit $?"
   f=$(find $O/stats_$wl -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $O/${wl}_kernel_stats.csv && head -6 $f | cut -c1-220
@@ -89,7 +89,7 @@ mfma)
 sq)
   wl=$1
   cd /tmp; rm -rf $O/sq_$wl
-  timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/sq_$wl -- python3 $R/bench.py --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-others > $O/sq_$wl.log 2>&1
+  timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/sq_$wl -- python3 $R/bench.py --full --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-others > $O/sq_$wl.log 2>&1
   echo "sq exit $?"
   cd $R
   python3 scripts/pmc_summary.py --raw $O/sq_$wl $O/pmc_sq_${wl}_summary.csv | head -8
@@ -111,7 +111,7 @@ sqring)
   ;;
 soak)
   n=$1; passes=${2:-20}
-  timeout 2400 python bench.py --clips $n --steps $passes --warmup 1 --no-cpu-baseline --no-strong-leg --no-others > $O/soak_$n.json 2> $O/soak_$n.err
+  timeout 2400 python bench.py --full --clips $n --steps $passes --warmup 1 --no-cpu-baseline --no-strong-leg --no-others > $O/soak_$n.json 2> $O/soak_$n.err
   echo "clips $n exit $?: $(fields $O/soak_$n.json 2) redone batches: $(grep -c "regenerating\|timed out" $O/soak_$n.err)"
   ;;
 stamps)
@@ -136,7 +136,7 @@ abw)
       lib=$([ $v = mimikit_amd/libmmk_hip.so ] && echo "" || echo $R/$v)
       line="$(basename $v)"
       for wl in $1; do
-        r=$(MMK_DIAG_LIB=$lib timeout 300 python bench.py --workload $wl --steps 5 --warmup 2 --no-cpu-baseline --no-others 2>/dev/null | grep -o '"avg_launch_us": [0-9.]*\|"us_per_step[a-z_]*": [0-9.]*\|"us_per_generate_step": [0-9.]*' | head -2 | tr '\n' ' ')
+        r=$(MMK_DIAG_LIB=$lib timeout 300 python bench.py --full --workload $wl --steps 5 --warmup 2 --no-cpu-baseline --no-others 2>/dev/null | grep -o '"avg_launch_us": [0-9.]*\|"us_per_step[a-z_]*": [0-9.]*\|"us_per_generate_step": [0-9.]*' | head -2 | tr '\n' ' ')
         line="$line | $wl: $r"
       done
       echo "$line" | tee -a $O/abw.log
