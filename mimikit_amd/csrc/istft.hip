@@ -769,36 +769,22 @@ void gla1024q_iter_kernel(const SpectralTables T, const float* __restrict__ wave
   }
 }
 
-#ifndef MMK_STFT_WAVES
-#define MMK_STFT_WAVES 4
-#endif
-#ifndef MMK_STFT_WPE
-#define MMK_STFT_WPE 3
-#endif
-constexpr int kStftWaves = MMK_STFT_WAVES;      // waves (= frame pairs in flight) per workgroup of the n_fft = 1024 STFT kernel
+constexpr int kStftWaves = 4;      // waves (= frame pairs in flight) per workgroup of the n_fft = 1024 STFT kernel
+constexpr int kStftWpe = 3;        // its waves per SIMD (launch bound and the host's count of resident workgroups)
 
 template <int OUT>
-__global__ __launch_bounds__(64 * kStftWaves) __attribute__((amdgpu_waves_per_eu(MMK_STFT_WPE, MMK_STFT_WPE)))
+__global__ __launch_bounds__(64 * kStftWaves) __attribute__((amdgpu_waves_per_eu(kStftWpe, kStftWpe)))
 void stft1024_kernel(const SpectralTables T, const float* __restrict__ x, int64_t x_row_stride, int64_t n_samples, int hop, int center, int reflect,
                      int64_t n_frames, int64_t total_pairs, int runs_per_row, float* __restrict__ out, float* __restrict__ tprev, float momentum) {
   constexpr int N = 1024, bins = 513;
-#ifndef MMK_STFT_REGTW
-#define MMK_STFT_REGTW 1      // the lane's 30 twiddles in registers for the whole kernel (no table in LDS at all)
-#endif
-  __shared__ cf32 tw[MMK_STFT_REGTW ? 1 : N];
   __shared__ cf32 bufs[kStftWaves * kFftWaveLds];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   float win[16];                                            // periodic Hann at n = lane + 64 r (functionals.py:513)
 #pragma unroll
   for (int r = 0; r < 16; ++r) win[r] = T.hann1024[lane + 64 * r];
-  FftLaneTw ltw;
-  if (MMK_STFT_REGTW) {
-    ltw.load(T.tw1024, lane);
-  } else {
-    load_twiddles(tw, T.tw1024, tid, 64 * kStftWaves);
-    __syncthreads();
-  }
+  FftLaneTw ltw;                                            // the lane's 30 twiddles in registers for the whole kernel (no table in LDS at all)
+  ltw.load(T.tw1024, lane);
   cf32* buf = bufs + wave * kFftWaveLds;
   const int64_t pairs_per_row = (n_frames + 1) >> 1;
   const int64_t pad = center ? N / 2 : 0;
@@ -855,8 +841,7 @@ void stft1024_kernel(const SpectralTables T, const float* __restrict__ x, int64_
 #pragma unroll
       for (int r = 0; r < 16; ++r) buf[lane + 64 * r] = v[r];
       __builtin_amdgcn_wave_barrier();
-    } else if (MMK_STFT_REGTW) fft1024_wave_regtw<true>(v, buf, ltw, lane);
-    else fft1024_wave<true>(v, buf, tw, lane);
+    } else fft1024_wave_regtw<true>(v, buf, ltw, lane);
     // the two real spectra:  A[k] = (Z[k] + conj(Z[N-k])) / 2 ,  B[k] = (Z[k] - conj(Z[N-k])) / (2i)
 #pragma unroll
     for (int jj = 0; jj < 9; ++jj) {
@@ -1204,7 +1189,7 @@ int launch_stft1024(const float* x, int64_t x_row_stride, int batch, int64_t n_s
   const int64_t n_frames = mmk_stft_n_frames(n_samples, 1024, hop, center);
   const int64_t pairs_per_row = (n_frames + 1) / 2;
   const int64_t total_pairs = (int64_t)batch * pairs_per_row;
-  const int64_t resident = 256 * (4 * MMK_STFT_WPE / kStftWaves);          // workgroups that are resident together on the chip
+  const int64_t resident = 256 * (4 * kStftWpe / kStftWaves);          // workgroups that are resident together on the chip
   // runs of consecutive pairs per clip: about one run per resident wave (at least 2 pairs per run where a clip has them, at most the clip)
   int64_t runs_per_row = (resident * kStftWaves + batch - 1) / batch;
   runs_per_row = runs_per_row > (pairs_per_row + 1) / 2 ? (pairs_per_row + 1) / 2 : runs_per_row;

@@ -20,30 +20,17 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
 
-#ifndef MMK_IP_NOLOAD
-#define MMK_IP_NOLOAD 0      // timing experiments only (wrong results)
+#ifndef MMK_IP_ABL
+#define MMK_IP_ABL 0      // timing experiments (results wrong): 1 no fragment loads, 2 no epilogue, 4 no barrier after a block's products
 #endif
-#ifndef MMK_IP_NOEPI
-#define MMK_IP_NOEPI 0
-#endif
-#ifndef MMK_IP_NOBAR
-#define MMK_IP_NOBAR 0
-#endif
-#ifndef MMK_IP_SPREAD
-#define MMK_IP_SPREAD 1      // the next block's fragments are requested one per chunk of products (0: all in front of the first)
-#endif
-#ifndef MMK_IP_EPI_EARLY
-#define MMK_IP_EPI_EARLY 1   // chunk of the next block in front of which waves 0 - 3 add up a block's partial sums ...
-#endif
-#ifndef MMK_IP_EPI_LATE
-#define MMK_IP_EPI_LATE 5    // ... and waves 4 - 7 (the other wave of each SIMD)
-#endif
+constexpr int kIpEpiEarly = 1;   // chunk of the next block in front of which waves 0 - 3 add up a block's partial sums ...
+constexpr int kIpEpiLate = 5;    // ... and waves 4 - 7 (the other wave of each SIMD)
 constexpr int kIpThreads = 512;
 constexpr int kIpWaves = kIpThreads / 64;
 
 template <int CPW>
 __device__ __forceinline__ void ip_request(u32x4s (&set)[CPW], const __amdgpu_buffer_rsrc_t& x, int byte_off, int n_valid) {
-  if (MMK_IP_NOLOAD) return;
+  if (MMK_IP_ABL & 1) return;
 #pragma unroll
   for (int u = 0; u < CPW; ++u) {
     // (chunks beyond K carry zero weights: any finite fragment will do - the last valid one, so that nothing is read out of bounds)
@@ -130,24 +117,20 @@ __global__ __launch_bounds__(kIpThreads) void lstm_inproj_kernel(const LstmInPro
     if (r0 + 1 < a.rows) dst[a.out_ld] = sum.y + bias;
   };
   const bool late_half = wave >= 4;
-  constexpr int kEpiEarly = MMK_IP_EPI_EARLY < CPW ? MMK_IP_EPI_EARLY : CPW - 1, kEpiLate = MMK_IP_EPI_LATE < CPW ? MMK_IP_EPI_LATE : CPW - 1;
+  constexpr int kEpiEarly = kIpEpiEarly < CPW ? kIpEpiEarly : CPW - 1, kEpiLate = kIpEpiLate < CPW ? kIpEpiLate : CPW - 1;
   auto pass = [&](auto setc, int blk, bool has_prev) {
     constexpr int set = decltype(setc)::value;
     const int next_off = frag_off(blk + 1 < b_end ? blk + 1 : blk);   // (the last pass asks for its own once more: every pass defines the other set anew)
-    if (!MMK_IP_SPREAD) {
-      ip_request<CPW>(xa[set ^ 1], xsrc, next_off, n_valid);
-      __builtin_amdgcn_sched_barrier(0);
-    }
     f32x4 acc[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u = 0; u < CPW; ++u) {
-      if (MMK_IP_SPREAD && !MMK_IP_NOLOAD) {
+      if (!(MMK_IP_ABL & 1)) {
         const int uu = u < n_valid ? u : (n_valid > 0 ? n_valid - 1 : 0);
         xa[set ^ 1][u] = __builtin_amdgcn_raw_buffer_load_b128(xsrc, next_off, uu * 64, 0);
       }
-      if (!MMK_IP_NOEPI && has_prev && ((u == kEpiEarly && !late_half) || (u == kEpiLate && late_half))) epilogue(blk - 1, set ^ 1);
+      if (!(MMK_IP_ABL & 2) && has_prev && ((u == kEpiEarly && !late_half) || (u == kEpiLate && late_half))) epilogue(blk - 1, set ^ 1);
       __builtin_amdgcn_sched_barrier(0);
       if (u < n_valid) {      // (same for the whole wave)
 #pragma unroll
@@ -163,14 +146,14 @@ __global__ __launch_bounds__(kIpThreads) void lstm_inproj_kernel(const LstmInPro
     const int slot = set;
 #pragma unroll
     for (int g = 0; g < 4; ++g) red[((slot * 4 + g) * kIpWaves + wave) * 64 + lane] = acc[g];
-    if (!MMK_IP_NOBAR) __syncthreads();
+    if (!(MMK_IP_ABL & 4)) __syncthreads();
   };
   int blk = b_first;
   for (; blk < b_end; blk += 2) {
     pass(std::integral_constant<int, 0>{}, blk, blk > b_first);
     if (blk + 1 < b_end) pass(std::integral_constant<int, 1>{}, blk + 1, true);
   }
-  if (!MMK_IP_NOEPI) epilogue(b_end - 1, (b_end - 1 - b_first) & 1);
+  if (!(MMK_IP_ABL & 2)) epilogue(b_end - 1, (b_end - 1 - b_first) & 1);
 }
 
 bool lstm_inproj_supported(int rows, int K, int k_chunks, int H) {

@@ -33,53 +33,18 @@ constexpr int kSqWaves = kSqThreads / 64;
 constexpr uint32_t kSqPoison = 0xFFFFFFFFu;
 constexpr unsigned kSqSpinLimit = 1u << 14;     // re-requests of one fragment (1 - 2 us each) before giving up
 
-#ifndef MMK_SQ_AHEAD
-#define MMK_SQ_AHEAD 1         // request a phase's state fragments during the phase before (two row blocks)
-#endif
-#ifndef MMK_SQ_AHEAD_AT
-#define MMK_SQ_AHEAD_AT 5      // ... in front of the products of chunk CPW * this / 8
-#endif
-#ifndef MMK_SQ_FAST_RCP
-#define MMK_SQ_FAST_RCP 1      // v_rcp_f32 in the cell's activations
-#endif
-#ifndef MMK_SQ_CHECK_GROUP
-#define MMK_SQ_CHECK_GROUP 1   // fragments whose poison check is one compare and one branch
-#endif
-#ifndef MMK_SQ_MAX3
-#define MMK_SQ_MAX3 1
-#endif
-#ifndef MMK_SQ_SPREAD
-#define MMK_SQ_SPREAD 1        // ... and dealt out over the chunks from there to the phase's last (0: all at once)
-#endif
-#ifndef MMK_SQ_FIRST_SC1
-#define MMK_SQ_FIRST_SC1 1     // 1: a fragment's FIRST request goes past the L2 as well (re-requests always do)
-#endif
-#ifndef MMK_SQ_ACC2
-#define MMK_SQ_ACC2 0          // experiment: two accumulator sets per gate (even / odd K quarter of a chunk)
-#endif
-#ifndef MMK_SQ_NOLOAD
-#define MMK_SQ_NOLOAD 0        // timing experiment only (wrong results): no state fragments are requested
-#endif
-#ifndef MMK_SQ_LOCALSRC
-#define MMK_SQ_LOCALSRC 0      // timing experiment only (wrong results): every fragment is read from the caller's state (never poisoned)
-#endif
-#ifndef MMK_SQ_NOCELL
-#define MMK_SQ_NOCELL 0        // timing experiment only (wrong results): the cell does not read the partial sums
-#endif
-#ifndef MMK_SQ_NOCHECK
-#define MMK_SQ_NOCHECK 0       // experiment only (wrong results possible): no poison check
-#endif
-#ifndef MMK_SQ_BUBBLE
-#define MMK_SQ_BUBBLE 0        // s_nop behind every second MFMA (what the per-step kernel needs to let its weight stream land)
+constexpr int kSqAheadAt = 5;                   // the next phase's requests start at chunk CPW * kSqAheadAt / 8 of a phase's products
+
+// timing experiments (results wrong): 1 no state fragments requested, 2 every fragment read from the caller's state (never poisoned),
+// 4 the cell does not read the partial sums, 8 no poison check
+#ifndef MMK_SQ_ABL
+#define MMK_SQ_ABL 0
 #endif
 
 typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
 
 // any of the four words still the poison pattern (the largest unsigned value: one v_max3, one v_max, one compare)
 __device__ __forceinline__ bool sq_poisoned(const u32x4s& v) {
-#if !MMK_SQ_MAX3
-  return (v.x == kSqPoison) | (v.y == kSqPoison) | (v.z == kSqPoison) | (v.w == kSqPoison);
-#endif
   unsigned m;
   asm("v_max3_u32 %0, %1, %2, %3" : "=v"(m) : "v"(v.x), "v"(v.y), "v"(v.z));
   return max(m, v.w) == kSqPoison;
@@ -95,12 +60,7 @@ __device__ __forceinline__ float sq_tanh(float x) { return fmaf(__builtin_amdgcn
 // copies of a register is the live one
 template <int CPW, int FROM = 0>
 __device__ __forceinline__ void sq_request(u32x4s (&set)[CPW], const __amdgpu_buffer_rsrc_t& image, int byte_off) {
-  if (MMK_SQ_NOLOAD) return;
-#pragma unroll
-  for (int u = FROM; u < CPW; ++u) set[u] = __builtin_amdgcn_raw_buffer_load_b128(image, byte_off, u * 64, MMK_SQ_FIRST_SC1 ? 16 : 0);
-}
-template <int CPW, int FROM>
-__device__ __forceinline__ void sq_rerequest(u32x4s (&set)[CPW], const __amdgpu_buffer_rsrc_t& image, int byte_off) {
+  if (MMK_SQ_ABL & 1) return;
 #pragma unroll
   for (int u = FROM; u < CPW; ++u) set[u] = __builtin_amdgcn_raw_buffer_load_b128(image, byte_off, u * 64, 16);
 }
@@ -163,7 +123,7 @@ __global__ __launch_bounds__(kSqThreads) void lstm_seq_kernel(const LstmSeqArgs 
     hoff[rb] = (int)(((int64_t)(m_first + (m < mg ? m : 0)) * H + c0 * 16 + 4 * (lane >> 4)) * sizeof(float));
   }
   auto image_of = [&](int s_src) {     // the state a step reads: the caller's before step 0, else the image step s_src - 1 wrote
-    const float* base = (s_src == 0 || MMK_SQ_LOCALSRC) ? d.h : a.xch + (int64_t)((s_src - 1) * 2 + di) * image;
+    const float* base = (s_src == 0 || (MMK_SQ_ABL & 2)) ? d.h : a.xch + (int64_t)((s_src - 1) * 2 + di) * image;
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, -1, 0x00020000);
   };
   bool check = true;                                // false once this wave has given up: the launch only drains
@@ -176,8 +136,8 @@ __global__ __launch_bounds__(kSqThreads) void lstm_seq_kernel(const LstmSeqArgs 
   // The state fragments of a phase are requested during the phase before (two register sets, RB == 2): block 1's fragments of step s
   // while block 0's products of step s run, block 0's of step s + 1 during block 1's.  With one block there is nothing to overlap:
   // the fragments are requested where the phase starts.
-  constexpr bool kAhead = RB == 2 && MMK_SQ_AHEAD;
-  constexpr int kAheadAt = (CPW * MMK_SQ_AHEAD_AT) / 8;     // chunk in front of whose products the next phase's requests go out
+  constexpr bool kAhead = RB == 2;
+  constexpr int kAheadAt = (CPW * kSqAheadAt) / 8;         // chunk in front of whose products the next phase's requests go out
   u32x4s hv[RB][CPW];
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb)
@@ -226,52 +186,34 @@ __global__ __launch_bounds__(kSqThreads) void lstm_seq_kernel(const LstmSeqArgs 
 #pragma unroll
         for (int v = 0; v < CPW; ++v)
           if (kAheadAt + (v * span) / CPW == u) {
-            if (MMK_SQ_NOLOAD) continue;
-            if constexpr (rb == 0 && RB == 2) hv[nrb][v] = __builtin_amdgcn_raw_buffer_load_b128(src_now, hoff[nrb], v * 64, MMK_SQ_FIRST_SC1 ? 16 : 0);
-            else hv[nrb][v] = __builtin_amdgcn_raw_buffer_load_b128(src_next, hoff[nrb], v * 64, MMK_SQ_FIRST_SC1 ? 16 : 0);
+            if (MMK_SQ_ABL & 1) continue;
+            if constexpr (rb == 0 && RB == 2) hv[nrb][v] = __builtin_amdgcn_raw_buffer_load_b128(src_now, hoff[nrb], v * 64, 16);
+            else hv[nrb][v] = __builtin_amdgcn_raw_buffer_load_b128(src_next, hoff[nrb], v * 64, 16);
           }
       };
       f32x4 acc[4];
 #pragma unroll
       for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-#if MMK_SQ_ACC2
-      f32x4 acc2[4];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) acc2[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-#endif
       if (product) {
         if (!kAhead) sq_request<CPW>(hv[rb], src_now, hoff[rb]);
         auto chunk = [&](auto uc) {
           constexpr int u = decltype(uc)::value;
           if constexpr (u < CPW) {
-            if constexpr (kAhead && MMK_SQ_SPREAD && u >= kAheadAt) {
+            if constexpr (kAhead && u >= kAheadAt) {
               request_next_part(uc);
               __builtin_amdgcn_sched_barrier(0);
-            } else if constexpr (kAhead && !MMK_SQ_SPREAD && u == kAheadAt) {
-              request_next();
-              __builtin_amdgcn_sched_barrier(0);
             }
-            constexpr int kGroup = MMK_SQ_CHECK_GROUP < CPW ? MMK_SQ_CHECK_GROUP : CPW;     // fragments checked together
-            if (u % kGroup == 0 && polled && check && !MMK_SQ_NOCHECK && !MMK_SQ_NOLOAD) {
+            if (polled && check && !(MMK_SQ_ABL & 8) && !(MMK_SQ_ABL & 1)) {
               unsigned spins = 0;
-              auto group_poisoned = [&]() {
-                unsigned m = 0;
-#pragma unroll
-                for (int v = u; v < u + kGroup && v < CPW; ++v) {
-                  asm("v_max3_u32 %0, %1, %2, %3" : "=v"(m) : "v"(m), "v"(hv[rb][v].x), "v"(hv[rb][v].y));
-                  asm("v_max3_u32 %0, %1, %2, %3" : "=v"(m) : "v"(m), "v"(hv[rb][v].z), "v"(hv[rb][v].w));
-                }
-                return m == kSqPoison;
-              };
-              while (__builtin_amdgcn_ballot_w64(kGroup == 1 ? sq_poisoned(hv[rb][u]) : group_poisoned()) != 0) {
+              while (__builtin_amdgcn_ballot_w64(sq_poisoned(hv[rb][u])) != 0) {
                 // not there yet: ask again for this fragment and the ones behind it (their producers are as late), past the L2
-                sq_rerequest<CPW, u>(hv[rb], src_now, hoff[rb]);
+                sq_request<CPW, u>(hv[rb], src_now, hoff[rb]);
                 // (all of them landed before the check: the compiler's count of what is pending where the loop is left then is the
                 //  straight path's, not "whatever this loop may have requested last")
 #pragma unroll
                 for (int v = u; v < CPW; ++v) asm volatile("" : "+v"(hv[rb][v]));
                 if (STAMPS) ++rerequests;
-                if (++spins > kSqSpinLimit || (MMK_WAIT_ERR_LOOK && (spins & 63u) == 0 && __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
+                if (++spins > kSqSpinLimit) {
                   if (lane == 0) atomicOr(a.err, 1u);
                   check = false;
                   break;
@@ -282,18 +224,7 @@ __global__ __launch_bounds__(kSqThreads) void lstm_seq_kernel(const LstmSeqArgs 
             for (int i = 0; i < 4; ++i) {
 #pragma unroll
               for (int g = 0; g < 4; ++g) {
-#if MMK_SQ_ACC2
-                if (i & 1) acc2[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(hv[rb][u][i]), w[u][g][i], acc2[g], 0, 0, 0);
-                else
-#endif
                 acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(hv[rb][u][i]), w[u][g][i], acc[g], 0, 0, 0);
-#if MMK_SQ_BUBBLE
-                if (g & 1) {
-                  __builtin_amdgcn_sched_barrier(0);
-                  asm volatile("s_nop 7");
-                  __builtin_amdgcn_sched_barrier(0);
-                }
-#endif
               }
             }
             __builtin_amdgcn_sched_barrier(0);     // the next chunk's wait stays behind these MFMAs
@@ -303,10 +234,6 @@ __global__ __launch_bounds__(kSqThreads) void lstm_seq_kernel(const LstmSeqArgs 
         chunk(std::integral_constant<int, 3>{}); chunk(std::integral_constant<int, 4>{}); chunk(std::integral_constant<int, 5>{});
         chunk(std::integral_constant<int, 6>{}); chunk(std::integral_constant<int, 7>{});
         static_assert(CPW <= 8, "H <= 1024");
-#if MMK_SQ_ACC2
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g] += acc2[g];
-#endif
 #pragma unroll
         for (int g = 0; g < 4; ++g) red[((slot * 4 + g) * kSqWaves + wave) * 64 + lane] = acc[g];
       } else if (kAhead) {
@@ -330,7 +257,7 @@ __global__ __launch_bounds__(kSqThreads) void lstm_seq_kernel(const LstmSeqArgs 
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           float v = 0.f;
-          if (product && !MMK_SQ_NOCELL) {
+          if (product && !(MMK_SQ_ABL & 4)) {
             const float* f = reinterpret_cast<const float*>(red + (slot * 4 + g) * kSqWaves * 64) + frag;
 #pragma unroll
             for (int wv = 0; wv < kSqWaves; ++wv) v += f[wv * 256];
@@ -340,15 +267,9 @@ __global__ __launch_bounds__(kSqThreads) void lstm_seq_kernel(const LstmSeqArgs 
         if (cell) {
 #pragma unroll
           for (int g = 0; g < 4; ++g) sum[g] += ga[g];
-#if MMK_SQ_FAST_RCP
           const float ig = sq_sigmoid(sum[0]), fg = sq_sigmoid(sum[1]), cg = sq_tanh(sum[2]), og = sq_sigmoid(sum[3]);
           c_reg = fg * c_reg + ig * cg;
           const float hn = og * sq_tanh(c_reg);
-#else
-          const float ig = sigmoid_fast(sum[0]), fg = sigmoid_fast(sum[1]), cg = tanh_fast(sum[2]), og = sigmoid_fast(sum[3]);
-          c_reg = fg * c_reg + ig * cg;
-          const float hn = og * tanh_fast(c_reg);
-#endif
           if (last) {
             hout[row * H + unit] = hn;
             d.c[row * H + unit] = c_reg;

@@ -398,7 +398,7 @@ __global__ __launch_bounds__(kGruThreads) void srnn_gru_kernel(const SrnnGruArgs
         for (int k = 0; k < 2 * CPW; ++k) all = all && g[k][1] == epoch && g[k][3] == epoch;
         if (all) break;
         // ~1 s: a workgroup of the grid never became resident (the launcher checks the grid against the CU count)
-        if (++spins > (1u << 20) || (MMK_WAIT_ERR_LOOK && (spins & 255u) == 0 && a.err && __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
+        if (++spins > (1u << 20)) {
           if (a.err) atomicExch(a.err, 3);
           break;
         }
@@ -452,15 +452,8 @@ __global__ __launch_bounds__(kGruThreads) void srnn_gru_kernel(const SrnnGruArgs
       }
       __syncthreads();
     };
-#ifndef MMK_SRNN_UP_ONE
-#define MMK_SRNN_UP_ONE 0      // all preloaded tiles as ONE batch (one reduction round instead of two; slot 0 goes out later, the launch ends sooner)
-#endif
-    if (MMK_SRNN_UP_ONE) {
-      run_batch(std::integral_constant<int, 0>{}, 0, min(up_tiles, UB));
-    } else {
-      run_batch(std::integral_constant<int, 0>{}, 0, 1);
-      if (up_tiles > 1) run_batch(std::integral_constant<int, 1>{}, 1, min(up_tiles, UB) - 1);
-    }
+    run_batch(std::integral_constant<int, 0>{}, 0, 1);
+    if (up_tiles > 1) run_batch(std::integral_constant<int, 1>{}, 1, min(up_tiles, UB) - 1);
     for (int jb = UB; jb < up_tiles; jb += UB) run_batch(std::integral_constant<int, -1>{}, jb, min(UB, up_tiles - jb));
   }
   stamp(6);   // up-sampler

@@ -50,20 +50,15 @@ __device__ __forceinline__ u64 res_gload(const u64* p) { return __hip_atomic_loa
 __device__ __forceinline__ void res_gstore(u64* p, unsigned tag, unsigned bits) {
   __hip_atomic_store(p, ((u64)tag << 32) | (u64)bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-#ifndef MMK_SRNN_RES_POLL_SLEEP
-#define MMK_SRNN_RES_POLL_SLEEP 1      // s_sleep units between two looks at a granule that is not there yet
-#endif
-#ifndef MMK_SRNN_RES_ERR_LOOK
-#define MMK_SRNN_RES_ERR_LOOK 0        // 1: a waiting wave looks at the error word every 256 polls; 0: its own time-out only - one exit less in every wait loop (cfg 3: 3.63 -> 3.44 us per step)
-#endif
-__device__ __forceinline__ void res_pause() { if (MMK_SRNN_RES_POLL_SLEEP > 0) __builtin_amdgcn_s_sleep(MMK_SRNN_RES_POLL_SLEEP); }
+constexpr int kResPollSleep = 1;      // s_sleep units between two looks at a granule that is not there yet
+__device__ __forceinline__ void res_pause() { __builtin_amdgcn_s_sleep(kResPollSleep); }
+// a waiting wave gives up after its own time-out only (one exit in every wait loop)
 __device__ __forceinline__ bool res_give_up(unsigned& spins, int* err, int code) {
   if (++spins > kResSpinLimit) {
     if (err) atomicCAS(err, 0, code);
     return true;
   }
-  if (!MMK_SRNN_RES_ERR_LOOK) return false;
-  return (spins & 255u) == 0 && err && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;   // another wait has failed: do not pile up
+  return false;
 }
 // one granule, polled until its tag is `tag`
 __device__ __forceinline__ unsigned res_wait(const u64* src, unsigned tag, int* err, int code) {

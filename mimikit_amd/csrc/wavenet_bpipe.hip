@@ -52,12 +52,7 @@ constexpr int kLgStride = 260;
 #ifndef MMK_BP_ABL
 #define MMK_BP_ABL 0      // timing experiments (results wrong): 1 no known-term products, 2 no hidden-unit products, 4 no early products, 8 no early gather either, 16 no residual products
 #endif
-#ifndef MMK_BP_LOOK_SLEEP
-#define MMK_BP_LOOK_SLEEP 0      // s_sleep units (64 cycles) between two looks at a message part that is not complete (a look is a whole L2 round trip: 0 / 2 / 6 -> 106.9 / 107.4 / 108.0 us per step at 128 clips)
-#endif
-#ifndef MMK_BP_CHAIN_PRIO
-#define MMK_BP_CHAIN_PRIO 2
-#endif
+constexpr int kChainPrio = 2;
 
 // word of element (k, n) - channel / unit k, clip n of the group - in a B-operand image of 16 n: the lane (k % 4 / 1 .. = K sub-step, n) of
 // k-step k / 4 reads it in one 16-byte read together with the three k-steps beside it
@@ -94,7 +89,7 @@ __device__ __forceinline__ bool wait_min(const unsigned* p, unsigned want, int32
     for (int i = 1; i < N; ++i) m = min(m, __hip_atomic_load(p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
     if (m >= want) break;
     __builtin_amdgcn_s_sleep(1);
-    if (++spins > kSpin || (MMK_WAIT_ERR_LOOK && (spins & 4095u) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
+    if (++spins > kSpin) {
       atomicCAS(err, 0, 1);
       return false;
     }
@@ -225,8 +220,7 @@ __device__ __forceinline__ bool gather(const unsigned* src, float* dst, int lane
   for (;;) {
     load4_sc1(src + 4 * lane, r[0], r[1], r[2], r[3]);
     if (__all(clean4(r[0], r[1], r[2], r[3]))) break;
-    if (MMK_BP_LOOK_SLEEP > 0) __builtin_amdgcn_s_sleep(MMK_BP_LOOK_SLEEP);
-    if (++spins > kSpin || (MMK_WAIT_ERR_LOOK && (spins & 1023u) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
+    if (++spins > kSpin) {
       atomicMax(err, 0x10000 | tag);      // (diagnosis: which look never saw its message)
       return false;
     }
@@ -259,7 +253,7 @@ __device__ __forceinline__ void chain_role(const WnBpipeArgs& a, BpLds& S, int s
   const int late_off = stage == 0 ? 0 : 4096;      // stage 0's newest operand is the embedded class (the x part of its message)
   const int64_t V = a.n_steps * G;
   int t = 0, g = 0;
-  __builtin_amdgcn_s_setprio(MMK_BP_CHAIN_PRIO);      // (ahead of the helper wave of the same SIMD, whose products are off the chain)
+  __builtin_amdgcn_s_setprio(kChainPrio);      // (ahead of the helper wave of the same SIMD, whose products are off the chain)
   BpStamp st;
   st.on = a.stamps != nullptr && stage == a.stamp_stage && p == 0 && w == 0;
   if (a.stamps != nullptr && stage == a.stamp_stage && p == 0 && (w == 0 || w == 2)) st.tr = a.stamps + 160 + 24 * (w >> 1);
@@ -432,7 +426,7 @@ __device__ __forceinline__ void helper_role(const WnBpipeArgs& a, BpLds& S, int 
         load4_sc1(src + 4 * lane, r[0], r[1], r[2], r[3]);
         if (__all(clean4(r[0], r[1], r[2], r[3]))) break;
         __builtin_amdgcn_s_sleep(2);
-        if (++spins > kSpin || (MMK_WAIT_ERR_LOOK && (spins & 1023u) == 0 && __hip_atomic_load(a.err_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
+        if (++spins > kSpin) {
           atomicMax(a.err_flag, 0x10000 | (64 * 17 + stage));
           return false;
         }
@@ -518,7 +512,7 @@ __device__ __forceinline__ void helper_role(const WnBpipeArgs& a, BpLds& S, int 
             break;
           }
           __builtin_amdgcn_s_sleep(2);
-          if (++spins > kSpin || (MMK_WAIT_ERR_LOOK && (spins & 1023u) == 0 && __hip_atomic_load(a.err_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
+          if (++spins > kSpin) {
             atomicCAS(a.err_flag, 0, 0x20000 | stage);
             return;
           }
@@ -591,7 +585,7 @@ __device__ __forceinline__ void helper_role(const WnBpipeArgs& a, BpLds& S, int 
               break;
             }
             __builtin_amdgcn_s_sleep(2);
-            if (++spins > kSpin || (MMK_WAIT_ERR_LOOK && (spins & 1023u) == 0 && __hip_atomic_load(a.err_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
+            if (++spins > kSpin) {
               atomicCAS(a.err_flag, 0, 0x20000 | stage);
               return false;
             }
@@ -705,7 +699,7 @@ __device__ __forceinline__ void head_role(const WnBpipeArgs& a, unsigned char* l
                        : "memory");
           if (__all(clean4(r[0], r[1], r[2], r[2]))) break;
           __builtin_amdgcn_s_sleep(2);
-          if (++spins > kSpin || (MMK_WAIT_ERR_LOOK && (spins & 1023u) == 0 && __hip_atomic_load(a.err_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
+          if (++spins > kSpin) {
             atomicCAS(a.err_flag, 0, 0x20000 | a.L);
             *s_fail = 1;
             break;

@@ -48,99 +48,29 @@ constexpr int kThreads = 512;
 constexpr int kCuPerStage = kC / 32;          // 8
 constexpr int kWavesPerStage = kC / 8;        // 32 chain waves (and as many helpers)
 constexpr int kMsgFloats = 2 * kC;            // 512
-#ifndef MMK_SP_EARLY_Y
-#define MMK_SP_EARLY_Y 1
-#endif
-#ifndef MMK_SP_HOIST_ADDR
-#define MMK_SP_HOIST_ADDR 1
-#endif
-#ifndef MMK_SP_XSLICE20
-#define MMK_SP_XSLICE20 1      // the LDS image of a message as 16 slices of 16 channels + 4 floats of padding (the chain lanes' 16-byte reads of 16 different slices then
-                               // cover the 64 banks once); 0: round 3's blocks of 32 channels + 4, whose slices collide pairwise (31 % of the LDS-active cycles at 128 clips:
-                               // profiles/r06_v2_pmc_sq_single_clips128_summary.csv)
-#endif
-constexpr int kPadBlk = 36;                   // 32 channels + 4 floats of padding: the K slices of a broadcast read fall on different banks
+// the LDS image of a message: 16 slices of 16 channels + 4 floats of padding (the chain lanes' 16-byte reads of 16 different slices then cover the
+// 64 banks once; round 3's blocks of 32 channels + 4 collided pairwise: profiles/r06_v2_pmc_sq_single_clips128_summary.csv)
 constexpr int kXSlice = 20;                   // 16 channels + 4 floats of padding
-constexpr int kHalf = MMK_SP_XSLICE20 ? 16 * kXSlice : (kC / 32) * kPadBlk;    // 320 (288) floats: one padded vector of C channels
+constexpr int kHalf = 16 * kXSlice;           // 320 floats: one padded vector of C channels
 constexpr int kXyRing = 8;
 constexpr int kChainRegs = 44, kHelperRegs = 32;   // float4 registers per lane in the stage images
 constexpr unsigned kSpinLimit = 1u << 22;
-#ifndef MMK_SP_POLL_GAP
-#define MMK_SP_POLL_GAP 1
-#endif
-constexpr int kPollGap = MMK_SP_POLL_GAP;     // s_sleep units (64 cycles) between two looks at a message that has not arrived
-#ifndef MMK_SP_LDS_SLEEP
-#define MMK_SP_LDS_SLEEP 1      // (round 4, helpers look and stage: helpers 1 / chain waves 2 -> 50.85 us per cfg-4 step, 5 / 5 -> 51.45, 1 / 10 -> 51.4, 0 / 5 -> 51.0)
-#endif
-#ifndef MMK_SP_CHAIN_SLEEP
-#define MMK_SP_CHAIN_SLEEP 2    // the same inside the chain waves' wait for their message (the helpers' waits keep MMK_SP_LDS_SLEEP)
-#endif
-constexpr int kChainSleep = MMK_SP_CHAIN_SLEEP;
-constexpr int kLdsSleep = MMK_SP_LDS_SLEEP;   // s_sleep units inside the spins on LDS counters: with the chain waves' wait as three FLAT loads 0 / 1 / 3 / 6 / 10 -> 55.7 / 55.6 / 55.3 / 55.9 / 56.5 us per step; as ds_reads (55.3 -> 54.4) 0 / 1 / 2 / 3 / 5 / 7 / 10 / 15 -> 54.3 / 54.9 / 54.6 / 54.3 / 53.9 / 54.1 / 54.2 / 54.7
-#ifndef MMK_SP_SLOT_SHIFT
-#define MMK_SP_SLOT_SHIFT 0     // empty slots in front of layer 0 (which layers are the first and the last of an XCD).  Measured on cfg 4: 1 -> 58.8 us
-                                // per step against 50.9 (layer 10, a dilation-1 stage, is then the LAST of its XCD; with 0 layers 0 and 20 are the first of theirs)
-#endif
-constexpr int kSlotShift = MMK_SP_SLOT_SHIFT;
-#ifndef MMK_SP_LAG
-#define MMK_SP_LAG 1           // the biases run four iterations behind the messages ...
-#endif
-#ifndef MMK_SP_LAG_CLIPS
-#define MMK_SP_LAG_CLIPS 40    // ... from this many clips on (>= 8).  Measured on one box, cfg 4, us per step: 32 clips 53.2 with the lag, 52.0 without; 64 clips
-                               // (with the early looks) 92.1 with it, 97.3 without: the lag pays where the clips queue up, and costs where one clip's latency binds
-#endif
-#ifndef MMK_SP_CHAIN_PRIO
-#define MMK_SP_CHAIN_PRIO 3
-#endif
-#ifndef MMK_SP_ROWS8
-#define MMK_SP_ROWS8 1         // chain products as 8 gate rows x a K slice of 16 per lane (half the LDS reads, one v_permlane16_swap level more): cfg 4, 32 clips 44.9 -> 44.2 us per step
-#endif
-#ifndef MMK_SP_BACKUP
-#define MMK_SP_BACKUP 0        // the helper halfway between two look duties looks for the current message too, half a round trip behind
-#endif
-#ifndef MMK_SP_G_LOCAL
-#define MMK_SP_G_LOCAL 6       // s_sleep units (64 clocks) by which the second pair of eyes trails: message from this XCD ...
-#endif
-#ifndef MMK_SP_G_REMOTE
-#define MMK_SP_G_REMOTE 16     // ... and from another one
-#endif
-#ifndef MMK_SP_DUTYFIRST
-#define MMK_SP_DUTYFIRST 1     // the helper whose look duty is next looks for that message before it makes the current iteration's bias: cfg 4, 32 clips 52.4 -> 44.9 us per step
-#endif
-#ifndef MMK_SP_EARLY_DEPTH
-#define MMK_SP_EARLY_DEPTH 3   // ... up to this many visits ahead of the message that is being waited for
-#endif
-#ifndef MMK_SP_EARLY
-#define MMK_SP_EARLY 0         // a helper looks for its next message already while it waits for the one before (staged by another helper): cfg 4, 64 clips 99.2 -> 92.1 us
-                               // per step before the next-duty helper looked first; with that, 32 clips 44.9 without the early looks, 46.4 - 47.4 with them
-#endif
-#ifndef MMK_SP_CHAIN_SLEEP_BY_MODE
-#define MMK_SP_CHAIN_SLEEP_BY_MODE 1
-#endif
-#ifndef MMK_SP_POLL_GAP_BY_MODE
-#define MMK_SP_POLL_GAP_BY_MODE 1
-#endif
-#ifndef MMK_SP_MFMA_BIAS
-#define MMK_SP_MFMA_BIAS 1     // four-behind mode: the biases of FOUR consecutive visits as one batch of v_mfma_f32_4x4x1 (helper_role)
-#endif
-#ifndef MMK_SP_LAG1
-#define MMK_SP_LAG1 1          // where the delayed input cannot be asked for early (dilation 1 and 2), its rows are staged TWO iterations after the request instead of one
-#endif
-#ifndef MMK_SP_BIASSHIFT
-#define MMK_SP_BIASSHIFT 1     // the bias of a visit is multiplied one iteration after its rows were staged (no helper waits for another one's staging inside an iteration)
-#endif
-#ifndef MMK_SP_NOARRWAIT
-#define MMK_SP_NOARRWAIT 1     // helpers off duty do not wait for the current message (16 clips or more: the rings' own counters bound how far they run ahead)
-#endif
+constexpr int kPollGap = 1;                   // s_sleep units (64 cycles) between two looks at a message that has not arrived
+// s_sleep units inside the spins on LDS counters (round 4, helpers look and stage: helpers 1 / chain waves 2 -> 50.85 us per cfg-4 step, 5 / 5 -> 51.45,
+// 1 / 10 -> 51.4, 0 / 5 -> 51.0; with the chain waves' wait as three FLAT loads 0 / 1 / 3 / 6 / 10 -> 55.7 / 55.6 / 55.3 / 55.9 / 56.5 us per step; as ds_reads
+// (55.3 -> 54.4) 0 / 1 / 2 / 3 / 5 / 7 / 10 / 15 -> 54.3 / 54.9 / 54.6 / 54.3 / 53.9 / 54.1 / 54.2 / 54.7)
+constexpr int kLdsSleep = 1;
+constexpr int kChainSleep = 2;                // the same inside the chain waves' wait for their message
+// the biases run four iterations behind the messages from this many clips on.  Measured on one box, cfg 4, us per step: 32 clips 53.2 with the
+// lag, 52.0 without; 64 clips 92.1 with it, 97.3 without: the lag pays where the clips queue up, and costs where one clip's latency binds
+constexpr int kLagClips = 40;
+static_assert(kLagClips >= 12, "the four-behind form needs 12 clips or more");
+constexpr int kChainPrio = 3;
 #ifndef MMK_SP_ABL
 #define MMK_SP_ABL 0           // timing builds only (results are wrong): the diagnostic build's dbg bits 1 / 2 / 4 / 8 / 16 / 32 / 128 / 256 as a compile-time mask of the product kernel
 #endif
 #define SP_ABL(bit) ((STAMPS && (a.dbg & (bit))) || (MMK_SP_ABL & (bit)))
-#ifndef MMK_SP_WAKEUP
-#define MMK_SP_WAKEUP 1        // the looking helper wakes the chain waves out of their s_sleep when it has staged a message
-#endif
-__device__ __forceinline__ int pad_of(int ch) { return MMK_SP_XSLICE20 ? (ch >> 4) * kXSlice + (ch & 15) : (ch >> 5) * kPadBlk + (ch & 31); }
-static_assert(!MMK_SP_XSLICE20 || MMK_SP_ROWS8, "the 20-float slices belong to the 8-row form of the chain products");
+__device__ __forceinline__ int pad_of(int ch) { return (ch >> 4) * kXSlice + (ch & 15); }
 
 __device__ __forceinline__ float dpp_quad_sum(float v) {
   v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
@@ -196,9 +126,6 @@ __device__ __forceinline__ float row_reduce_scatter8(const float (&v)[8], int ks
 }
 
 __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-
-// layers + head + the empty slots have to fit the chip's 32 slots
-__device__ __forceinline__ int slot_shift(const WnSpipeArgs& a) { return a.L + 1 + kSlotShift <= 32 ? kSlotShift : 0; }
 
 // LDS counters: written by one lane of one wave, read by all; LDS serves a wave's operations in issue order, so data written before
 // the counter is visible to whoever has read the new counter value.  The signal fences only pin the compiler's order.
@@ -260,7 +187,7 @@ constexpr int kBRow = 528;                    // 512 floats + 16: the four visit
 struct Lds {
   float xy[kXyRing][2 * kHalf];               // the newest messages of this stage: [x padded | y padded]
   float rows[kRowRing][2][kRowPad];           // [visit][x_s[t - d] | c[t]]: what the biases of the next visits are multiplied with
-  float rowsb[2][4][kBRow];                   // the same rows of a BATCH of four visits, [x_s[t - d] (256) | c[t] (256)] + padding, two batches (MMK_SP_MFMA_BIAS)
+  float rowsb[2][4][kBRow];                   // the same rows of a BATCH of four visits, [x_s[t - d] (256) | c[t] (256)] + padding, two batches (four-behind mode: helper_role)
   unsigned arrived[4];                        // [v mod 4]: v + 1 once the message of visit v is staged into xy (by helper v mod 4)
   unsigned hdone[4];                          // per chain wave: visits whose xy image it no longer needs
   unsigned rows_ready[4];                     // [v mod 4]: v + 1 once the rows of visit v are staged (by helper v mod 4: every word has ONE writer, so it only grows)
@@ -281,9 +208,6 @@ struct Stamps {
 // ------------------------------------------------------------------------------------------------------------------------------------
 // the two things a chain wave waits for in LDS before it computes visit v, read together: the message staged by the polling helper, this
 // wave's bias prepared
-#ifndef MMK_SP_TIGHT_WAIT
-#define MMK_SP_TIGHT_WAIT 1
-#endif
 // up to 2^24 looks (~1 s) at ONE LDS counter in a loop of six instructions (read, wait, compare, branch out / count, branch back); returns the last value read.  The compiler's
 // form of the loop below - two reads, a minimum, the time-out's bookkeeping and three exits - leaves ~10 scalar instructions between the look that sees the message
 // and the first LDS read of the visit, on every visit's chain.
@@ -310,7 +234,6 @@ __device__ __forceinline__ unsigned lds_spin_ge(const unsigned* p, unsigned want
 template <int SLEEP>
 __device__ __forceinline__ bool chain_wait(const Lds& S, int q, unsigned v, int32_t* err) {
   unsigned spins = 0;
-#if MMK_SP_TIGHT_WAIT
   if (SLEEP == 0) {      // (the trip-bound regime: no pause between two looks)
     // the bias of a visit is made a step ahead: it is there, or it is waited for first - then ONE counter is looked at
     while (__hip_atomic_load(&S.ready[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < v + 1) {
@@ -329,7 +252,6 @@ __device__ __forceinline__ bool chain_wait(const Lds& S, int q, unsigned v, int3
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
     return true;
   }
-#endif
   for (;;) {
     const unsigned arr = __hip_atomic_load(&S.arrived[v & 3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     const unsigned rd = __hip_atomic_load(&S.ready[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -349,7 +271,7 @@ __device__ __forceinline__ bool chain_wait(const Lds& S, int q, unsigned v, int3
 template <bool STAMPS, bool LAG4>
 __device__ void chain_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int q, int lane) {
   const int W = 4 * p + q;
-  // products: a lane holds 4 gate rows x one K slice of 32 of [x | y] (and 2 residual rows x 16 of y); the rows' totals come out of a
+  // products: a lane holds 8 gate rows x one K slice of 16 of [x | y] (and 2 residual rows x 16 of y); the rows' totals come out of a
   // reduce-scatter over the DPP row, so that lane l ends with gate row l / 4 and residual channel l / 8 of the wave
   const int ks = lane & 15;
   const int j = lane >> 2, j8 = lane >> 3;
@@ -379,22 +301,18 @@ __device__ void chain_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int q
   // added up INSIDE an XCD only (a hand-over from another XCD is a 0.8-us load): the first stage of an XCD starts a new sum, the last one
   // writes the XCD's sum where the head collects the (at most eight) of them.
   const int64_t hid_words = (int64_t)a.Bmax * kSpSlots * kH1;
-  const int grp = (stage + slot_shift(a)) >> 2;
-  const bool hid_chain_in = stage >= 2 && ((stage - 1 + slot_shift(a)) >> 2) == grp;
-  const bool hid_last = stage == a.L - 1 || ((stage + 1 + slot_shift(a)) >> 2) != grp;
-  const bool hid_local = hid_last ? grp == ((a.L + slot_shift(a)) >> 2) : true;      // (the head's own XCD: its L2 is the meeting point)
+  const int grp = stage >> 2;
+  const bool hid_chain_in = stage >= 2 && ((stage - 1) >> 2) == grp;
+  const bool hid_last = stage == a.L - 1 || ((stage + 1) >> 2) != grp;
+  const bool hid_local = hid_last ? grp == (a.L >> 2) : true;      // (the head's own XCD: its L2 is the meeting point)
   unsigned* hid_out = (hid_last ? a.hidgrp + (int64_t)grp * hid_words : a.hidmsg + (int64_t)(stage + 1) * hid_words) + 4 * W + (lane >> 4);
   const bool g_row = (j & 1) != 0;
   const float gate_scale = g_row ? -1.4426950408889634f : -2.8853900817779268f;
   const float gate_k = g_row ? 1.f : 2.f, gate_shift = g_row ? 0.f : -1.f;
-  const bool local_next = ((stage + 1 + slot_shift(a)) >> 2) == ((stage + slot_shift(a)) >> 2);
+  const bool local_next = ((stage + 1) >> 2) == (stage >> 2);
   const int64_t stage_words = (int64_t)a.Bmax * kSpSlots * kMsgFloats;
   unsigned* msg_out = a.msg + (int64_t)(stage + 1) * stage_words;
-#if MMK_SP_ROWS8
   const int kso = ((lane & 16) ? kHalf : 0) + pad_of(16 * ks);        // K slice lane & 31 of 16: x[16 ks ..] in the even rows of 16 lanes, y[16 ks ..] in the odd ones
-#else
-  const int kso = (ks < 8 ? 0 : kHalf) + (ks & 7) * kPadBlk;           // K slice ks: x[32 ks ..] for ks < 8, y[32 (ks - 8) ..] above
-#endif
   const int xr_off = kHalf + pad_of(16 * ks);                          // y[16 ks ..]
   const int xin_off = pad_of(8 * W + j8);
   const bool pub_lane = (lane & 7) < 2;
@@ -411,7 +329,6 @@ __device__ void chain_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int q
     const int slot = s & 3, pslot = (s + 2) & 3;
     for (int c = 0; c < B; ++c, ++v) {
       if (STAMPS && !(a.dbg & 64)) t0c = __builtin_amdgcn_s_memtime();
-#if MMK_SP_HOIST_ADDR
       // where this visit reads and writes, worked out BEFORE the wait for its message (the compiler puts these eight scalar / vector instructions behind the wait,
       // in front of the first LDS read - on every visit's chain)
       typedef const __attribute__((address_space(3))) float* lds_cf;
@@ -421,9 +338,8 @@ __device__ void chain_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int q
       lds_cf p_b = (lds_cf)(&S.bias[bias_off(q, s & 1, c, j, Bcap)]);
       int64_t o_dst = ((int64_t)c * kSpSlots + slot) * kMsgFloats + pub_off;
       asm volatile("" : "+v"(p_z), "+v"(p_y), "+v"(p_in), "+v"(p_b), "+v"(o_dst));
-#endif
-      if (!chain_wait<MMK_SP_CHAIN_SLEEP_BY_MODE ? (LAG4 ? kChainSleep : 0) : kChainSleep>(S, q, v, a.err_flag)) return;
-      __builtin_amdgcn_s_setprio(MMK_SP_CHAIN_PRIO);              // (low while it spins: the helper wave of this SIMD gets the issue slots)
+      if (!chain_wait<LAG4 ? kChainSleep : 0>(S, q, v, a.err_flag)) return;
+      __builtin_amdgcn_s_setprio(kChainPrio);              // (low while it spins: the helper wave of this SIMD gets the issue slots)
       if (STAMPS && !(a.dbg & 64)) {
         const u64 t = __builtin_amdgcn_s_memtime(); st.t_wait += t - t0c; t0c = t;
         if (a.stamps && c == 0 && s + 1 == n_steps && p == 0 && q == 0 && lane == 0) a.stamps[112 + stage] = __builtin_amdgcn_s_memrealtime();
@@ -434,102 +350,52 @@ __device__ void chain_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int q
         continue;
       }
       // what the helper prepared a step ahead: W0 x[t - d] + conditioning + biases
-#if MMK_SP_HOIST_ADDR
       const float bzv = *p_b;
       const float* xb = &S.xy[0][0] + o_img;
-#else
-      const float bzv = S.bias[bias_off(q, s & 1, c, j, Bcap)];
-      const float* xb = S.xy[v & (kXyRing - 1)];
-#endif
-#if MMK_SP_ROWS8
       // ---- z = [W1 | W1 R] . [x ; y]: 8 gate rows x ONE K slice of 16 per lane: 4 reads of 4 inputs (half of what 4 rows x 32 inputs read:
       //      the four chain waves' reads share one LDS), 64 packed FMAs; the two rows of 16 lanes that hold the same 8 gate rows swap
       //      halves (v_permlane16_swap: even rows keep gate rows 0-3, odd rows 4-7), then the row's reduce-scatter as before -----------------
       f32x2 acc8[8];
 #pragma unroll
       for (int cc = 0; cc < 8; ++cc) acc8[cc] = f32x2{0.f, 0.f};
-#if MMK_SP_EARLY_Y
       // the y slice of the residual product and the layer's own input are asked for NOW, with the gate products' reads: left to the compiler they go out behind the
       // 64 gate products (it re-uses their registers) and are waited for at once - an LDS round trip in front of the residual product, on every visit's chain
       f32x4s xv4[4], yv4[4];
-#if MMK_SP_HOIST_ADDR
 #pragma unroll
       for (int i = 0; i < 4; ++i) xv4[i] = ((lds_cf4)p_z)[i];
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int i = 0; i < 4; ++i) yv4[i] = ((lds_cf4)p_y)[i];
-      const float xin_early = *p_in;
-#else
-#pragma unroll
-      for (int i = 0; i < 4; ++i) xv4[i] = *reinterpret_cast<const f32x4s*>(xb + kso + i * 4);
+      const float xin = *p_in;
       __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) yv4[i] = *reinterpret_cast<const f32x4s*>(xb + xr_off + i * 4);
-      const float xin_early = xb[xin_off];
-#endif
-      __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-#if MMK_SP_EARLY_Y
         const f32x4s xv = xv4[i];
-#else
-        const f32x4s xv = *reinterpret_cast<const f32x4s*>(xb + kso + i * 4);
-#endif
 #pragma unroll
         for (int cc = 0; cc < 8; ++cc) {
           acc8[cc] = fma2(f32x2{wz[cc * 4 + i][0], wz[cc * 4 + i][1]}, f32x2{xv[0], xv[1]}, acc8[cc]);
           acc8[cc] = fma2(f32x2{wz[cc * 4 + i][2], wz[cc * 4 + i][3]}, f32x2{xv[2], xv[3]}, acc8[cc]);
         }
       }
-#else
-      // ---- z = [W1 | W1 R] . [x ; y]: 8 reads of 4 inputs, 64 packed FMAs (4 rows x 32 inputs per lane) ---------------------------------
-      f32x2 acc[4][2];
-#pragma unroll
-      for (int cc = 0; cc < 4; ++cc) acc[cc][0] = acc[cc][1] = f32x2{0.f, 0.f};
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const f32x4s xv = *reinterpret_cast<const f32x4s*>(xb + kso + i * 4);
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) {
-          acc[cc][0] = fma2(f32x2{wz[cc * 8 + i][0], wz[cc * 8 + i][1]}, f32x2{xv[0], xv[1]}, acc[cc][0]);
-          acc[cc][1] = fma2(f32x2{wz[cc * 8 + i][2], wz[cc * 8 + i][3]}, f32x2{xv[2], xv[3]}, acc[cc][1]);
-        }
-      }
-#endif
       // ---- the layer's own input x_s = x_{s-1} + (R y + br): 2 channels x 16 inputs per lane ---------------------------------------------
       f32x2 rac[2][2];
 #pragma unroll
       for (int cc = 0; cc < 2; ++cc) rac[cc][0] = rac[cc][1] = f32x2{0.f, 0.f};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-#if MMK_SP_EARLY_Y && MMK_SP_ROWS8
         const f32x4s yv = yv4[i];
-#else
-        const f32x4s yv = *reinterpret_cast<const f32x4s*>(xb + xr_off + i * 4);
-#endif
 #pragma unroll
         for (int cc = 0; cc < 2; ++cc) {
           rac[cc][0] = fma2(f32x2{wr[cc * 4 + i][0], wr[cc * 4 + i][1]}, f32x2{yv[0], yv[1]}, rac[cc][0]);
           rac[cc][1] = fma2(f32x2{wr[cc * 4 + i][2], wr[cc * 4 + i][3]}, f32x2{yv[2], yv[3]}, rac[cc][1]);
         }
       }
-#if MMK_SP_EARLY_Y && MMK_SP_ROWS8
-      const float xin = xin_early;
-#else
-      const float xin = xb[xin_off];
-#endif
       float zc[4];
-#if MMK_SP_ROWS8
 #pragma unroll
       for (int cc = 0; cc < 4; ++cc) {
         const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc8[cc][0] + acc8[cc][1]), __float_as_uint(acc8[4 + cc][0] + acc8[4 + cc][1]), false, false);
         zc[cc] = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
       }
-#else
-#pragma unroll
-      for (int cc = 0; cc < 4; ++cc) zc[cc] = (acc[cc][0][0] + acc[cc][0][1]) + (acc[cc][1][0] + acc[cc][1][1]);
-#endif
       float z = row_reduce_scatter4(zc[0], zc[1], zc[2], zc[3], ks);
       const float xs = row_reduce_scatter2((rac[0][0][0] + rac[0][0][1]) + (rac[0][1][0] + rac[0][1][1]),
                                            (rac[1][0][0] + rac[1][0][1]) + (rac[1][1][0] + rac[1][1][1]), ks);
@@ -541,11 +407,7 @@ __device__ void chain_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int q
       const float y = act * other;
       // ---- publish 8 x | 8 y, re-poison the same words two steps ahead, keep x_s for the delayed taps -------------------------------------
       if (pub_lane) {
-#if MMK_SP_HOIST_ADDR
         unsigned* dst = msg_out + o_dst;
-#else
-        unsigned* dst = msg_out + ((int64_t)c * kSpSlots + slot) * kMsgFloats + pub_off;
-#endif
         msg_store(dst, msg_bits((lane & 1) ? y : xnew), local_next);
       }
       if (STAMPS && !(a.dbg & 64)) {
@@ -627,7 +489,7 @@ __device__ void helper_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int 
   // 4 K residues; lane 4 b + i carries row 4 (b & 3) + i as the A operand and visit i of the batch as the B operand, block b's share of K
   // is the floats 16 m + 4 (b >> 2) .. + 3 of every 16.  128 products per batch and helper on the matrix pipe (which the chain wave of the
   // SIMD does not use) instead of 4 x 64 packed FMAs + 4 reduce-scatters on the vector ALU it shares with it, and one hand-shake per four visits.
-  constexpr bool MF = LAG4 && (MMK_SP_MFMA_BIAS != 0);
+  constexpr bool MF = LAG4;
   f32x4s w0[16], wc[16];
   {
     const f32x4s* img = reinterpret_cast<const f32x4s*>(a.img_helper) + ((int64_t)stage * kWavesPerStage + W) * kHelperRegs * 64;
@@ -664,7 +526,7 @@ __device__ void helper_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int 
   const int B = a.B, Bcap = bias_cap(a.B);
   const int n_visits = (int)a.n_steps * B;
   const int64_t hid_words = (int64_t)a.Bmax * kSpSlots * kH1;
-  const bool hid_chain_in = stage >= 2 && ((stage - 1 + slot_shift(a)) >> 2) == ((stage + slot_shift(a)) >> 2);      // (as in the chain role)
+  const bool hid_chain_in = stage >= 2 && ((stage - 1) >> 2) == (stage >> 2);      // (as in the chain role)
   // The rows a bias is multiplied with - this stage's delayed input and the projected conditioning row, 1 KB each - come into the CU ONCE:
   // helper v mod 4 asks for those of visit v (lane l: floats 4 l .. 4 l + 3 of each) and stages them in LDS, all four helpers read their
   // K slices from there.  (Every lane asking for its own 2 x 64 bytes - the form of round 3 - moves 32 KB per visit through the CU's
@@ -681,7 +543,7 @@ __device__ void helper_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int 
   // (one iteration behind where the rows cannot be asked for ahead of time - dilation 1 and 2: a row asked for at the end of the duty
   //  iteration and staged at the start of the next one is waited for, ~0.3 us in front of everything that helper does in that iteration;
   //  in a free run - nothing waits for messages - those stages take 1.60 - 1.66 us per visit against 1.54, and the slowest stage is the ring's beat)
-  const int lag = LAG4 ? 4 : ((MMK_SP_LAG1 && B >= 8 && ahead == 0) ? 1 : 0);
+  const int lag = LAG4 ? 4 : ((B >= 8 && ahead == 0) ? 1 : 0);
   const int roff = lag == 4 ? B - 1 : B + ahead;          // the rows of visit it + roff are asked for in iteration it
   // who asks for (and stages) the rows of visit v: the helper that looks in iteration v - B + 1 (lag 4) or v - B - ahead (no lag), right after
   // its look duty
@@ -697,7 +559,7 @@ __device__ void helper_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int 
   };
   // (diagnostic build, dbg 4: nothing waits for a message - every stage runs at the pace of its own work; results are wrong, the
   //  per-stage times say what a stage's service time is when its inbox is never empty)
-  constexpr int kGap = MMK_SP_POLL_GAP_BY_MODE ? (LAG4 ? kPollGap : 0) : kPollGap;
+  constexpr int kGap = LAG4 ? kPollGap : 0;
   const bool freerun = SP_ABL(4);
   if (STAMPS && a.stamps && freerun && p == 0 && h == 0 && lane == 0) a.stamps[182 + stage] = __builtin_amdgcn_s_memrealtime();
   auto landed = [&](const u32x4s& lo, const u32x4s& hi) {
@@ -885,13 +747,6 @@ __device__ void helper_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int 
   // fewer clips, four visits ahead is up to four STEPS ahead - a slot that still holds the message of four steps ago.
   const bool lookahead = B >= 4;
   bool staged_next = false;                       // my next message is staged already (in the iteration before the duty)
-#ifndef MMK_SP_SHIFT_ALL
-#define MMK_SP_SHIFT_ALL 0      // (experiment: the shift below 40 clips too - valid from 9 clips on only)
-#endif
-  constexpr int shift = (MMK_SP_BIASSHIFT && (LAG4 || MMK_SP_SHIFT_ALL)) ? 1 : 0;      // the biases one iteration behind their rows' staging (with the four-iteration lag: 64 clips 84.9 -> 82.7 us per step)
-  int spb = 0, cpb = 0;                           // (the visit staged in the iteration before)
-  // this stage's message comes from another XCD (or, stage 0, from the head): a look is a ~0.8-us round trip there, ~0.3 inside an XCD
-  const bool remote_in = stage == 0 ? ((a.L + slot_shift(a)) >> 2) != (slot_shift(a) >> 2) : ((stage - 1 + slot_shift(a)) >> 2) != ((stage + slot_shift(a)) >> 2);
   if (lookahead && h < n_visits) look(((((h % B) * kSpSlots + ((h / B) & 3)) * kMsgFloats) * 4) + look_off, pre_lo, pre_hi);   // the first look at "my" first message
   else pre_lo[0] = kSpPoison;
   for (int it = 0; it < n_visits; ++it) {
@@ -927,9 +782,7 @@ __device__ void helper_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int 
       if (STAMPS && a.stamps && cc == 0 && ss + 1 == (int)a.n_steps && p == 0 && lane == 0) a.stamps[64 + stage] = __builtin_amdgcn_s_memrealtime();
       if (STAMPS && a.stamps && ss == (int)a.n_steps / 2 && p == 0 && lane == 0 && cc < 32) a.stamps[256 + 1024 + stage * 32 + cc] = __builtin_amdgcn_s_memrealtime();   // seen, every clip, the launch's middle step
       lds_signal(&S.arrived[vv & 3], (unsigned)vv + 1, lane);
-#if MMK_SP_WAKEUP
       asm volatile("s_wakeup");            // the other waves of the workgroup out of their s_sleep: they look at the counter again at once
-#endif
     };
     if (duty) {
       if (!staged_next) {
@@ -954,57 +807,7 @@ __device__ void helper_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int 
       staged_next = false;
       if (lookahead && it + 4 < n_visits) look(((cl * kSpSlots + (sl & 3)) * kMsgFloats) * 4 + look_off, pre_lo, pre_hi);
       else pre_lo[0] = kSpPoison;
-    } else if (MMK_SP_EARLY && (MMK_SP_EARLY == 1 || remote_in) && it + ((h - it) & 3) < n_visits && (((h - it) & 3) <= MMK_SP_EARLY_DEPTH) && (((h - it) & 3) == 1 || lookahead)) {
-      // not my look duty: while message `it` is not staged (by its helper), I look for MY next one already (1 - 3 visits ahead) - when the
-      // clips queue up it is there, and a look at another XCD's memory is a ~0.8-us round trip that would otherwise start only when the
-      // messages before it have been staged one after the other: the four helpers' looks then run side by side
-      const int nahead = (h - it) & 3, nd = it + nahead;
-      const int cn = c + nahead >= B ? c + nahead - B : c + nahead, sn = c + nahead >= B ? s + 1 : s;
-      const int off = ((cn * kSpSlots + (sn & 3)) * kMsgFloats) * 4 + look_off;
-      unsigned spins = 0;
-      while (__hip_atomic_load(&S.arrived[it & 3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < (unsigned)it + 1) {
-        if (!staged_next) {
-          if (landed(pre_lo, pre_hi)) {
-            if (nd < kXyRing - 2 || lds_min4(S.hdone) + (kXyRing - 2) >= (unsigned)nd + 1) {
-              stage_message(nd, cn, sn, pre_lo, pre_hi);
-              if (!fetch_hid(nd, cn, sn)) return;
-              staged_next = true;
-            } else if (kLdsSleep > 0) __builtin_amdgcn_s_sleep(kLdsSleep);
-          } else {
-            look(off, pre_lo, pre_hi);
-          }
-        } else if (kLdsSleep > 0) __builtin_amdgcn_s_sleep(kLdsSleep);
-        if (++spins > kSpinLimit || ((spins & 1023u) == 0 && __hip_atomic_load(a.err_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-          atomicExch(a.err_flag, 1);
-          return;
-        }
-      }
-      __atomic_signal_fence(__ATOMIC_SEQ_CST);
-    } else if (MMK_SP_BACKUP && (MMK_SP_BACKUP == 1 || remote_in) && ((it + 2) & 3) == h && it >= 2) {
-      // Halfway between two look duties: a SECOND pair of eyes on message `it`, half a look's round trip behind the helper on duty, in
-      // registers of its own (the first look at this helper's next message is in flight in the others).  A CU then looks twice per round
-      // trip, and what a stage waits for is the slowest of its eight CUs: the mean of that maximum shrinks with the looks' period.
-      // Whoever sees the message first stages it; the other one finds S.arrived set, or stages the same bytes once more.
-      if (it >= kXyRing - 2 && !lds_wait4(S.hdone, (unsigned)it - (kXyRing - 2) + 1, a.err_flag)) return;
-      const int off = ((c * kSpSlots + (s & 3)) * kMsgFloats) * 4 + look_off;
-      u32x4s bk_lo, bk_hi;
-      unsigned spins = 0;
-      if (remote_in) __builtin_amdgcn_s_sleep(MMK_SP_G_REMOTE); else __builtin_amdgcn_s_sleep(MMK_SP_G_LOCAL);
-      while (__hip_atomic_load(&S.arrived[it & 3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < (unsigned)it + 1) {
-        look(off, bk_lo, bk_hi);
-        if (landed(bk_lo, bk_hi)) {
-          stage_message(it, c, s, bk_lo, bk_hi);
-          if (!fetch_hid(it, c, s)) return;
-          break;
-        }
-        if (++spins > kSpinLimit || ((spins & 1023u) == 0 && __hip_atomic_load(a.err_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-          atomicExch(a.err_flag, 1);
-          return;
-        }
-        if (kPollGap > 0) __builtin_amdgcn_s_sleep(kPollGap);
-      }
-      __atomic_signal_fence(__ATOMIC_SEQ_CST);
-    } else if (!(MMK_SP_NOARRWAIT && (LAG4 || B >= 16)) && !lds_wait1(&S.arrived[it & 3], (unsigned)it + 1, a.err_flag)) return;
+    } else if (!(LAG4 || B >= 16) && !lds_wait1(&S.arrived[it & 3], (unsigned)it + 1, a.err_flag)) return;
     hstamp(1);
     // ---- 2. the bias of visit it - 1 - lag + B (its rows were asked for one, three or four iterations ago) -------------------------------------
     if (it >= 1 + lag && it - 1 - lag + B < n_visits) {
@@ -1024,7 +827,6 @@ __device__ void helper_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int 
       }
     }
     hstamp(4);
-#if MMK_SP_DUTYFIRST
     // My look duty is the NEXT visit: I look for that message NOW and make this iteration's bias afterwards (it has B - 2 visits of
     // slack).  Otherwise all four helpers start their products when message `it` is staged, and nobody looks for message it + 1 until
     // the helper whose duty it is has finished them: a stage then takes (products + look) per visit however few clips wait - with 32
@@ -1048,7 +850,6 @@ __device__ void helper_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int 
       if (!fetch_hid(vn, cn, sn)) return;
       staged_next = true;
     }
-#endif
     if constexpr (MF) {
       // the batch before the one that visit it + B - 5 (staged in this iteration) belongs to: a quarter of its products per iteration
       const int u = it + B - 5, kbc = (u >> 2) - 1;
@@ -1056,12 +857,6 @@ __device__ void helper_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int 
         if (!mf_chunk(kbc, u & 3, B, n_visits)) return;
         hstamp(5);
       }
-    } else if (shift) {
-      if (it >= 2 + lag && it - 2 - lag + B < n_visits) {
-        if (!bias_of((unsigned)(it - 2 - lag + B), spb, cpb)) return;
-        hstamp(5);
-      }
-      spb = sp; cpb = cp;
     } else if (it >= 1 + lag && it - 1 - lag + B < n_visits) {
       const unsigned v3 = (unsigned)(it - 1 - lag + B);
       if (!bias_of(v3, sp, cp)) return;
@@ -1128,7 +923,7 @@ __device__ void head_role(const WnSpipeArgs& a, int p) {
   const unsigned* msg_in = a.msg + (int64_t)L * stage_words;
   unsigned* msg_out = a.msg;                                               // stage 0's inbox (another XCD: written through)
   // the XCDs' sums of hidden pre-activations (layers 0 .. L - 2): groups g_first .. g_last, thread (o, kq) adds up those with g = g_first + kq (mod 4)
-  const int g_first = (1 + slot_shift(a)) >> 2, g_last = (L - 1 + slot_shift(a)) >> 2;
+  const int g_first = 0, g_last = (L - 1) >> 2;
   const bool last_mine = L >= 2 && ((g_last - g_first) & 3) == kq;
   u64 hs_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hs_t0 = 0;      // diagnostic build: cycles in the phases of a visit (workgroup 0)
   auto hstamp = [&](int k) {
@@ -1347,8 +1142,8 @@ __global__ __launch_bounds__(kThreads) void wavenet_spipe_kernel(const WnSpipeAr
   __syncthreads();
   const int role = s_role;
   if (role < 0) return;
-  // slot = role / 8 of the chip's 32 (four per XCD); the first kSlotShift slots stay empty, so that layer l sits in slot l + kSlotShift
-  const int stage = (role >> 3) - slot_shift(a), p = role & 7;
+  // slot = role / 8 of the chip's 32 (four per XCD): layer l sits in slot l, the head in slot L
+  const int stage = role >> 3, p = role & 7;
   if (stage < 0 || stage > a.L) return;
   if (stage == a.L) {
     head_role<STAMPS>(a, p);
@@ -1386,21 +1181,13 @@ __global__ __launch_bounds__(256) void spipe_image_kernel(const WnSpRaw* __restr
       const WnSpRaw r = raw[s];
       float out[4] = {0.f, 0.f, 0.f, 0.f};
       if (qi < 32) {
-#if MMK_SP_ROWS8
         // register cc * 4 + i: gate row 8 (lane / 32) + cc of the wave, inputs 16 (lane & 15) + 4 i .. of x (even rows of 16 lanes) or y (odd rows).
         // After the swap of halves even rows hold the sums of cc = 0 .. 3, odd rows of cc = 4 .. 7, and the row's reduce-scatter leaves lane l
-        // with gate row 8 (l / 32) + 4 (l / 16 & 1) + (l & 15) / 4 = l / 4, as in the other form.
+        // with gate row 8 (l / 32) + 4 (l / 16 & 1) + (l & 15) / 4 = l / 4.
         const int ks = lane & 15, cc = qi >> 2, i = qi & 3, n = gate_raw_row(W, 8 * (lane >> 5) + cc);
         const bool xpart = (lane & 16) == 0;
         for (int e = 0; e < 4; ++e) {
           const int k = 16 * ks + 4 * i + e;
-#else
-        // register cc * 8 + i: gate row 4 (lane / 16) + cc of the wave, inputs 32 (ks & 7) + 4 i .. of x (ks < 8) or y
-        const int ks = lane & 15, cc = qi >> 3, i = qi & 7, n = gate_raw_row(W, 4 * (lane >> 4) + cc);
-        const bool xpart = ks < 8;
-        for (int e = 0; e < 4; ++e) {
-          const int k = 32 * (ks & 7) + 4 * i + e;
-#endif
           if (xpart) out[e] = r.wd[((int64_t)n * kC + k) * 2 + 1];                                                        // W1[n][k]
           else if (s >= 1 && raw[s - 1].wr) out[e] = (float)dot_cols(r.wd + (int64_t)n * kC * 2 + 1, 2, raw[s - 1].wr + k, kC, kC);   // (W1 R)[n][k]
         }
@@ -1512,7 +1299,7 @@ int launch_wavenet_spipe(const WnSpipeArgs& a, hipStream_t stream) {
     MMK_HIP(hipGetLastError());
     return MMK_OK;
   }
-  const bool lag4 = MMK_SP_LAG && a.B >= MMK_SP_LAG_CLIPS && a.B >= 12;      // (the biases four iterations behind the messages: helper_role)
+  const bool lag4 = a.B >= kLagClips;      // (the biases four iterations behind the messages: helper_role)
 #ifdef MMK_DIAG
   if (a.stamps) {      // the stamped instantiation (and its timing switches) exist in the diagnostic build only
     if (lag4) hipLaunchKernelGGL((wavenet_spipe_kernel<true, true>), dim3(256), dim3(kThreads), lds, stream, a);

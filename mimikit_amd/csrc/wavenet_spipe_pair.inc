@@ -22,13 +22,7 @@ constexpr int kSlice2 = 36;                    // a K slice of 16 channels x 2 c
 constexpr int kHalf2 = 16 * kSlice2;           // 576 floats: C channels of two clips, {clip 0, clip 1} per channel
 __device__ __forceinline__ int pad2_of(int ch) { return (ch >> 4) * kSlice2 + (ch & 15) * 2; }
 
-#ifndef MMK_SP_PAIR_ROWS_DMA
-#define MMK_SP_PAIR_ROWS_DMA 0     // 1: the rows of the biases straight into LDS (loads with the lds bit: no registers that live across four iterations).  Measured, 128 / 96 clips: 110.8 / 84.5 us per step against 102.5 / 80.6 with the rows in registers (helpers alone: equal) - a timing switch
-#endif
-#ifndef MMK_SP_ROWSB_DEPTH
-#define MMK_SP_ROWSB_DEPTH (MMK_SP_PAIR_ROWS_DMA ? 4 : 2)      // (register form: 4 deep 128 clips 103.2 -> 105.2 us per step; the DMA form asks for a slot two batches before it is staged)
-#endif
-constexpr int kRowsbDepth = MMK_SP_ROWSB_DEPTH;      // a power of two
+constexpr int kRowsbDepth = 2;                 // a power of two (4 deep: 128 clips 103.2 -> 105.2 us per step)
 struct Lds2 {
   float xy[kXyRing][2 * kHalf2];              // the newest visits' messages: [x | y], two clips interleaved
   float rowsb[kRowsbDepth][4][kBRow];         // the rows of a BATCH of four clip-visits (= two visits): [x_s[t - d] (256) | c[t] (256)] + padding; a batch's rows are staged
@@ -76,41 +70,14 @@ __device__ __forceinline__ float row_reduce_scatter2_pair(float a0, float a1, fl
   return (b1 ? tb : ta) + dpp_xor2(b1 ? ta : tb);
 }
 
-#ifndef MMK_SP_PAIR_HID_LATE
-#define MMK_SP_PAIR_HID_LATE 1
-#endif
-#ifndef MMK_SP_PAIR_HOIST
-#define MMK_SP_PAIR_HOIST 1
-#endif
-#ifndef MMK_SP_PAIR_ROLL
-#define MMK_SP_PAIR_ROLL 2          // 1: always, 2: only where the step is one visit's trip, 0: never (measured: 64 clips 64.2 -> 63.5 us per step, 128 clips 102.0 -> 102.9)
-#endif
-#ifndef MMK_SP_PAIR_ROWDUTY
-#define MMK_SP_PAIR_ROWDUTY 1
-#endif
-#ifndef MMK_SP_PAIR_HID_PRE
-#define MMK_SP_PAIR_HID_PRE 1
-#endif
+// timing builds only (results wrong): 1 every bias product twice, 8 no look loads, 16 no row loads, 32 the rows' buffer is not waited for,
+// 64 the row loads go into registers nobody reads and are never waited for by their data
 #ifndef MMK_SP_PAIR_TIMING
 #define MMK_SP_PAIR_TIMING 0
 #endif
-#ifndef MMK_SP_PAIR_TRIP_GAP
-#define MMK_SP_PAIR_TRIP_GAP 0
-#endif
-#ifndef MMK_SP_PAIR_LOOKS
-#define MMK_SP_PAIR_LOOKS 1          // looks in flight while a helper waits for its messages in the trip-bound regime (1: a look goes out when the one before has come back).
-                                     // Measured, 64 clips: 1 / 2 / 3 looks in flight 65.5 / 86.1 / 107.1 us per step - every further look of a stage's eight CUs at the lines
-                                     // their producers are storing to costs the hop 0.7 us; the pipelined form stays as a timing switch
-#endif
-#ifndef MMK_SP_PAIR_LOOK_GAP
-#define MMK_SP_PAIR_LOOK_GAP 4       // s_sleep units (64 clocks) between the first looks of such a set: about a third of a look's round trip
-#endif
-#ifndef MMK_SP_PAIR_TRIP_VISITS
-#define MMK_SP_PAIR_TRIP_VISITS 40   // fewer visits per step than this: the step is one visit's trip round the ring, and nobody pauses between two looks (as the one-clip form below 40 clips)
-#endif
+constexpr int kPairTripVisits = 40;   // fewer visits per step than this: the step is one visit's trip round the ring, and nobody pauses between two looks (as the one-clip form below 40 clips)
 __device__ __forceinline__ bool chain_wait2(const Lds2& S, int q, unsigned v, bool nap, int32_t* err) {
   unsigned spins = 0;
-#if MMK_SP_TIGHT_WAIT
   if (!nap) {      // (the trip-bound regime: the bias first - it is there a step ahead -, then ONE counter in the six-instruction loop of chain_wait)
     while (__hip_atomic_load(&S.ready[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < 2 * v + 2) {
       if (++spins > kSpinLimit || ((spins & 4095u) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
@@ -125,7 +92,6 @@ __device__ __forceinline__ bool chain_wait2(const Lds2& S, int q, unsigned v, bo
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
     return true;
   }
-#endif
   for (;;) {
     const unsigned arr = __hip_atomic_load(&S.arrived[v & 3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     const unsigned rd = __hip_atomic_load(&S.ready[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -168,15 +134,15 @@ __device__ void chain_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, int
   for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(wh[i]));
   asm volatile("" : "+v"(bx));
   const int64_t hid_words = (int64_t)a.Bmax * kSpSlots * kH1;
-  const int grp = (stage + slot_shift(a)) >> 2;
-  const bool hid_chain_in = stage >= 2 && ((stage - 1 + slot_shift(a)) >> 2) == grp;
-  const bool hid_last = stage == a.L - 1 || ((stage + 1 + slot_shift(a)) >> 2) != grp;
-  const bool hid_local = hid_last ? grp == ((a.L + slot_shift(a)) >> 2) : true;
+  const int grp = stage >> 2;
+  const bool hid_chain_in = stage >= 2 && ((stage - 1) >> 2) == grp;
+  const bool hid_last = stage == a.L - 1 || ((stage + 1) >> 2) != grp;
+  const bool hid_local = hid_last ? grp == (a.L >> 2) : true;
   unsigned* hid_out = (hid_last ? a.hidgrp + (int64_t)grp * hid_words : a.hidmsg + (int64_t)(stage + 1) * hid_words) + 4 * W + (lane >> 4);
   const bool g_row = (j & 1) != 0;
   const float gate_scale = g_row ? -1.4426950408889634f : -2.8853900817779268f;
   const float gate_k = g_row ? 1.f : 2.f, gate_shift = g_row ? 0.f : -1.f;
-  const bool local_next = ((stage + 1 + slot_shift(a)) >> 2) == ((stage + slot_shift(a)) >> 2);
+  const bool local_next = ((stage + 1) >> 2) == (stage >> 2);
   const int64_t stage_words = (int64_t)a.Bmax * kSpSlots * kMsgFloats;
   unsigned* msg_out = a.msg + (int64_t)(stage + 1) * stage_words;
   const int kso = ((lane & 16) ? kHalf2 : 0) + ks * kSlice2;          // K slice lane & 31 of 16 channels: x in the even rows of 16 lanes, y in the odd ones
@@ -188,18 +154,14 @@ __device__ void chain_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, int
   float* hist = a.hist[stage];
   const int64_t slot_stride = (int64_t)a.Bmax * kC;
   const int V = a.B >> 1, n_steps = (int)a.n_steps, Bcap = bias_cap(a.B);
-#ifdef MMK_SP_PAIR_NAP_CONST
-  constexpr bool nap = true;
-#else
-  const bool nap = V >= MMK_SP_PAIR_TRIP_VISITS;
-#endif
+  const bool nap = V >= kPairTripVisits;
   unsigned v = 0;
   for (int s = 0; s < n_steps; ++s) {
     const int64_t tau = a.t0 - 1 + s;
     const int slot = s & 3, pslot = (s + 2) & 3;
     for (int cv = 0; cv < V; ++cv, ++v) {
       if (!chain_wait2(S, q, v, nap, a.err_flag)) return;
-      __builtin_amdgcn_s_setprio(MMK_SP_CHAIN_PRIO);
+      __builtin_amdgcn_s_setprio(kChainPrio);
       if (MMK_SP_ABL & 16) {          // (timing builds only: the chain waves do nothing)
         lds_signal(&S.hdone[q], v + 1, lane);
         continue;
@@ -213,84 +175,74 @@ __device__ void chain_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, int
       for (int cc = 0; cc < 8; ++cc) acc[cc] = f32x2{0.f, 0.f};
       f32x2 rac[2] = {f32x2{0.f, 0.f}, f32x2{0.f, 0.f}};
       float xin;
-#if MMK_SP_PAIR_ROLL == 2
       if (!nap) {      // (the rolling window where the step is one visit's trip: 64 clips -1 %; at a stage's beat it costs 1 %: 128 clips)
-#endif
-#if MMK_SP_PAIR_ROLL
-      // The 16 reads of a visit's products in a rolling window of four: reads k + 2 and k + 3 go out when the products of read pair k are through - left to the compiler,
-      // the next pair went out behind the products of TWO pairs (it re-uses their registers) and was waited for at once: an LDS round trip three times per visit.
-      // Pairs 0 - 3: the gate products' K slice; pairs 4 - 7: the y slice of the residual product.
-      f32x4s ra[2], rc[2];
-      auto rd = [&](int k, int b) {
-        const float* src = k < 4 ? xb + kso + 8 * k : xb + yr_off + 8 * (k - 4);
-        ra[b] = *reinterpret_cast<const f32x4s*>(src);
-        rc[b] = *reinterpret_cast<const f32x4s*>(src + 4);
-      };
-      rd(0, 0);
-      rd(1, 1);
-      xin = xb[xin_off];
-      __builtin_amdgcn_sched_barrier(0);
+        // The 16 reads of a visit's products in a rolling window of four: reads k + 2 and k + 3 go out when the products of read pair k are through - left to the compiler,
+        // the next pair went out behind the products of TWO pairs (it re-uses their registers) and was waited for at once: an LDS round trip three times per visit.
+        // Pairs 0 - 3: the gate products' K slice; pairs 4 - 7: the y slice of the residual product.
+        f32x4s ra[2], rc[2];
+        auto rd = [&](int k, int b) {
+          const float* src = k < 4 ? xb + kso + 8 * k : xb + yr_off + 8 * (k - 4);
+          ra[b] = *reinterpret_cast<const f32x4s*>(src);
+          rc[b] = *reinterpret_cast<const f32x4s*>(src + 4);
+        };
+        rd(0, 0);
+        rd(1, 1);
+        xin = xb[xin_off];
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const f32x4s xa = ra[k & 1], xc = rc[k & 1];
-        if (k < 4) {
+        for (int k = 0; k < 8; ++k) {
+          const f32x4s xa = ra[k & 1], xc = rc[k & 1];
+          if (k < 4) {
+#pragma unroll
+            for (int cc = 0; cc < 8; ++cc) {
+              const f32x4s wq = wz[cc * 4 + k];
+              pk_lo(acc[cc], f32x2{wq[0], wq[1]}, f32x2{xa[0], xa[1]});
+              pk_hi(acc[cc], f32x2{wq[0], wq[1]}, f32x2{xa[2], xa[3]});
+              pk_lo(acc[cc], f32x2{wq[2], wq[3]}, f32x2{xc[0], xc[1]});
+              pk_hi(acc[cc], f32x2{wq[2], wq[3]}, f32x2{xc[2], xc[3]});
+            }
+          } else {
+#pragma unroll
+            for (int cc = 0; cc < 2; ++cc) {
+              const f32x4s wq = wr[cc * 4 + (k - 4)];
+              pk_lo(rac[cc], f32x2{wq[0], wq[1]}, f32x2{xa[0], xa[1]});
+              pk_hi(rac[cc], f32x2{wq[0], wq[1]}, f32x2{xa[2], xa[3]});
+              pk_lo(rac[cc], f32x2{wq[2], wq[3]}, f32x2{xc[0], xc[1]});
+              pk_hi(rac[cc], f32x2{wq[2], wq[3]}, f32x2{xc[2], xc[3]});
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          if (k + 2 < 8) rd(k + 2, k & 1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const f32x4s xa = *reinterpret_cast<const f32x4s*>(xb + kso + 8 * i), xc = *reinterpret_cast<const f32x4s*>(xb + kso + 8 * i + 4);
 #pragma unroll
           for (int cc = 0; cc < 8; ++cc) {
-            const f32x4s wq = wz[cc * 4 + k];
+            const f32x4s wq = wz[cc * 4 + i];
             pk_lo(acc[cc], f32x2{wq[0], wq[1]}, f32x2{xa[0], xa[1]});
             pk_hi(acc[cc], f32x2{wq[0], wq[1]}, f32x2{xa[2], xa[3]});
             pk_lo(acc[cc], f32x2{wq[2], wq[3]}, f32x2{xc[0], xc[1]});
             pk_hi(acc[cc], f32x2{wq[2], wq[3]}, f32x2{xc[2], xc[3]});
           }
-        } else {
+        }
+        // ---- the layer's own input x_s = x_{s-1} + (R y + br): 2 channels x 16 inputs per lane, both clips ----------------------------------
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const f32x4s ya = *reinterpret_cast<const f32x4s*>(xb + yr_off + 8 * i), yc = *reinterpret_cast<const f32x4s*>(xb + yr_off + 8 * i + 4);
 #pragma unroll
           for (int cc = 0; cc < 2; ++cc) {
-            const f32x4s wq = wr[cc * 4 + (k - 4)];
-            pk_lo(rac[cc], f32x2{wq[0], wq[1]}, f32x2{xa[0], xa[1]});
-            pk_hi(rac[cc], f32x2{wq[0], wq[1]}, f32x2{xa[2], xa[3]});
-            pk_lo(rac[cc], f32x2{wq[2], wq[3]}, f32x2{xc[0], xc[1]});
-            pk_hi(rac[cc], f32x2{wq[2], wq[3]}, f32x2{xc[2], xc[3]});
+            const f32x4s wq = wr[cc * 4 + i];
+            pk_lo(rac[cc], f32x2{wq[0], wq[1]}, f32x2{ya[0], ya[1]});
+            pk_hi(rac[cc], f32x2{wq[0], wq[1]}, f32x2{ya[2], ya[3]});
+            pk_lo(rac[cc], f32x2{wq[2], wq[3]}, f32x2{yc[0], yc[1]});
+            pk_hi(rac[cc], f32x2{wq[2], wq[3]}, f32x2{yc[2], yc[3]});
           }
         }
-        __builtin_amdgcn_sched_barrier(0);
-        if (k + 2 < 8) rd(k + 2, k & 1);
-        __builtin_amdgcn_sched_barrier(0);
+        xin = xb[xin_off];
       }
-#endif
-#if MMK_SP_PAIR_ROLL == 2
-      } else {
-#endif
-#if MMK_SP_PAIR_ROLL != 1
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const f32x4s xa = *reinterpret_cast<const f32x4s*>(xb + kso + 8 * i), xc = *reinterpret_cast<const f32x4s*>(xb + kso + 8 * i + 4);
-#pragma unroll
-        for (int cc = 0; cc < 8; ++cc) {
-          const f32x4s wq = wz[cc * 4 + i];
-          pk_lo(acc[cc], f32x2{wq[0], wq[1]}, f32x2{xa[0], xa[1]});
-          pk_hi(acc[cc], f32x2{wq[0], wq[1]}, f32x2{xa[2], xa[3]});
-          pk_lo(acc[cc], f32x2{wq[2], wq[3]}, f32x2{xc[0], xc[1]});
-          pk_hi(acc[cc], f32x2{wq[2], wq[3]}, f32x2{xc[2], xc[3]});
-        }
-      }
-      // ---- the layer's own input x_s = x_{s-1} + (R y + br): 2 channels x 16 inputs per lane, both clips ----------------------------------
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const f32x4s ya = *reinterpret_cast<const f32x4s*>(xb + yr_off + 8 * i), yc = *reinterpret_cast<const f32x4s*>(xb + yr_off + 8 * i + 4);
-#pragma unroll
-        for (int cc = 0; cc < 2; ++cc) {
-          const f32x4s wq = wr[cc * 4 + i];
-          pk_lo(rac[cc], f32x2{wq[0], wq[1]}, f32x2{ya[0], ya[1]});
-          pk_hi(rac[cc], f32x2{wq[0], wq[1]}, f32x2{ya[2], ya[3]});
-          pk_lo(rac[cc], f32x2{wq[2], wq[3]}, f32x2{yc[0], yc[1]});
-          pk_hi(rac[cc], f32x2{wq[2], wq[3]}, f32x2{yc[2], yc[3]});
-        }
-      }
-      xin = xb[xin_off];
-#endif
-#if MMK_SP_PAIR_ROLL == 2
-      }
-#endif
       // the two rows of 16 lanes that hold the same 8 gate rows swap halves (even rows keep gate rows 0-3, odd rows 4-7), per clip
       float zc0[4], zc1[4];
 #pragma unroll
@@ -381,12 +333,8 @@ __device__ void helper_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, in
   const int B = a.B, Bcap = bias_cap(a.B), V = a.B >> 1;
   const int n_vis = (int)a.n_steps * V, n_cv = (int)a.n_steps * B;
   const int64_t hid_words = (int64_t)a.Bmax * kSpSlots * kH1;
-  const bool hid_chain_in = stage >= 2 && ((stage - 1 + slot_shift(a)) >> 2) == ((stage + slot_shift(a)) >> 2);
-#ifdef MMK_SP_PAIR_NAP_CONST
-  constexpr bool nap = true;
-#else
-  const bool nap = V >= MMK_SP_PAIR_TRIP_VISITS;
-#endif
+  const bool hid_chain_in = stage >= 2 && ((stage - 1) >> 2) == (stage >> 2);
+  const bool nap = V >= kPairTripVisits;
   const int roff = V - 1;                       // the rows of visit it + roff are asked for in iteration it (by the helper on duty) and staged in its next duty, it + 4
   const __amdgpu_buffer_rsrc_t inbox = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned*>(a.msg + (int64_t)stage * stage_words), 0, -1, 0x00020000);
   const int look_off = 32 * lane;
@@ -446,57 +394,6 @@ __device__ void helper_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, in
     lds_signal(&S.rows_ready[cvv & 7], cvv + 1, lane);
     return true;
   };
-#if MMK_SP_PAIR_ROWS_DMA
-  // The same rows WITHOUT registers: 16 bytes per lane from memory straight into the batch's LDS slot (lane l's bytes land at slot + 16 l: the staged layout).  Registers
-  // that a row is loaded into live across four iterations of this loop, and the compiler waits for such a register - and before it is overwritten - with a count of zero,
-  // behind every load the wave has in flight (helpers alone, 128 clips: 88 us per step with the rows in registers, 69 without the rows' loads, 74 with the loads sent
-  // into registers nobody reads).  The slot is asked for when the request goes out (two batches earlier than in the register form: the buffer is four batches deep).
-  // d = 1: the stage's own newest message - possibly not published yet: checked for poison in LDS when the rows are due, asked for again if so.
-  auto x_row_src = [&](int s2, int c2) -> const float* {
-    if (d == 1) return reinterpret_cast<const float*>(a.msg + (int64_t)(stage + 1) * stage_words) + ((int64_t)c2 * kSpSlots + ((s2 - 1) & 3)) * kMsgFloats + (lane >> 1) * 16 + (lane & 1) * 4;
-    const int64_t tp = (MMK_SP_PAIR_TIMING & 128) ? 0 : a.t0 - 1 + s2 - d;      // (timing builds only, 128: one and the same ring row / conditioning row - the loads hit the L2)
-    return tp >= 0 ? a.hist[stage] + (tp & ring_mask) * slot_stride + (int64_t)((MMK_SP_PAIR_TIMING & 128) ? 0 : c2) * kC + 4 * lane : nullptr;
-  };
-  auto rows_slot = [&](unsigned cvv) -> float* { return &S.rowsb[(cvv >> 2) & (kRowsbDepth - 1)][cvv & 3][0]; };
-  auto dma16_sc1 = [&](const float* src, float* dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 16);
-  };
-  auto request_rows_dma = [&](int s2, int c2, unsigned cvv) -> bool {
-    const unsigned kb = cvv >> 2;
-    if (kb >= (unsigned)kRowsbDepth && !lds_wait4(S.ready, 4 * (kb - kRowsbDepth) + 4, a.err_flag)) return false;
-    float* slot = rows_slot(cvv);
-    const float* src = x_row_src(s2, c2);
-    if (src) dma16_sc1(src, slot);
-    else *reinterpret_cast<f32x4s*>(slot + 4 * lane) = f32x4s{0.f, 0.f, 0.f, 0.f};      // in front of the sequence
-    if (cond_lane && !(MMK_SP_ABL & 1))
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.cproj + ((MMK_SP_PAIR_TIMING & 128) ? 0 : ((int64_t)c2 * a.cond_steps + s2) * a.C1) + 4 * lane),
-                                       (__attribute__((address_space(3))) void*)(slot + 256), 16, 0, 0);
-    return true;
-  };
-  // the rows of clip-visits cvv, cvv + 1 (= visit (cu, su)) are due: everything this wave has in flight is waited for once, here
-  auto complete_rows_dma = [&](unsigned cvv, int s2, int c2) -> bool {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (d == 1) {
-      unsigned spins = 0;
-      for (;;) {
-        const u32x4s w0 = *reinterpret_cast<const u32x4s*>(rows_slot(cvv) + 4 * lane), w1 = *reinterpret_cast<const u32x4s*>(rows_slot(cvv + 1) + 4 * lane);
-        if (freerun || __all(w0[0] != kSpPoison && w0[1] != kSpPoison && w0[2] != kSpPoison && w0[3] != kSpPoison && w1[0] != kSpPoison && w1[1] != kSpPoison &&
-                             w1[2] != kSpPoison && w1[3] != kSpPoison)) break;
-        if (++spins > kSpinLimit || ((spins & 1023u) == 0 && __hip_atomic_load(a.err_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-          atomicExch(a.err_flag, 1);
-          return false;
-        }
-        __atomic_signal_fence(__ATOMIC_SEQ_CST);
-        dma16_sc1(x_row_src(s2, c2), rows_slot(cvv));
-        dma16_sc1(x_row_src(s2, c2 + 1), rows_slot(cvv + 1));
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-    }
-    lds_signal(&S.rows_ready[cvv & 7], cvv + 1, lane);
-    lds_signal(&S.rows_ready[(cvv + 1) & 7], cvv + 2, lane);
-    return true;
-  };
-#endif
   // a quarter of batch kb's products (see helper_role): clip-visits in [v_lo, v_hi) exist
   f32x4s macc[4] = {f32x4s{0.f, 0.f, 0.f, 0.f}, f32x4s{0.f, 0.f, 0.f, 0.f}, f32x4s{0.f, 0.f, 0.f, 0.f}, f32x4s{0.f, 0.f, 0.f, 0.f}};
   auto mf_chunk = [&](int kb, int ch, int v_lo, int v_hi) -> bool {
@@ -520,7 +417,6 @@ __device__ void helper_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, in
       const float* xb = &S.rowsb[kb & (kRowsbDepth - 1)][lane & 3][(CH >> 1) * 256 + 4 * (lane >> 4)];
       constexpr int m0 = (CH & 1) * 8;
       // (all eight reads of the chunk first: with a read two products ahead of its use the chunk starts with a full LDS round trip in front of its first product)
-#if MMK_SP_PAIR_HOIST
       f32x4s xv[8];
 #pragma unroll
       for (int mm = 0; mm < 8; ++mm) xv[mm] = *reinterpret_cast<const f32x4s*>(xb + 16 * (m0 + mm));
@@ -530,20 +426,6 @@ __device__ void helper_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, in
 #pragma unroll
         for (int e = 0; e < 4; ++e) macc[e] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[e], xv[mm][e], macc[e], 0, 0, 0);
       }
-#else
-#pragma unroll
-      for (int mm = 0; mm < 8; ++mm) {
-#if MMK_SP_PAIR_TIMING & 2      // (timing builds only: the products without their LDS reads)
-        f32x4s xv = bz4;
-        asm volatile("" : "+v"(xv));
-#else
-        const f32x4s xv = *reinterpret_cast<const f32x4s*>(xb + 16 * (m0 + mm));
-#endif
-        const f32x4s wv = (CH >> 1) ? wc[m0 + mm] : w0[m0 + mm];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) macc[e] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[e], xv[e], macc[e], 0, 0, 0);
-      }
-#endif
     };
     if (!(MMK_SP_ABL & 8))
     for (int rep = 0; rep < ((MMK_SP_PAIR_TIMING & 1) ? 2 : 1); ++rep)      // (timing builds only: every product twice)
@@ -589,16 +471,12 @@ __device__ void helper_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, in
   int sl = 4 / V, cl = 4 % V;                     // visit it + 4: the messages whose first look goes out in iteration it
   u32x4s m[4];
   bool staged_next = false;
-  const bool remote_in = stage == 0 ? ((a.L + slot_shift(a)) >> 2) != (slot_shift(a) >> 2) : ((stage - 1 + slot_shift(a)) >> 2) != ((stage + slot_shift(a)) >> 2);
-  (void)remote_in;
   // the hidden units' hand-over of a visit is asked for together with the FIRST look at its messages (four visits ahead): where the clips queue up it is there
   // when the messages are staged - asked for at the staging it was a round trip per duty in front of everything the four helpers do in lock step (the beat, 96+ clips)
   const unsigned* hid_base = a.hidmsg + (int64_t)stage * hid_words + 16 * p + (lane & 15);
   unsigned hid_pre = kSpPoison;
   auto pre_ask_hid = [&](int cc, int ss) {
-#if MMK_SP_PAIR_HID_PRE
     if (hid_chain_in && !(MMK_SP_ABL & 32)) hid_pre = msg_load(hid_base + ((int64_t)(2 * cc + ((lane >> 4) & 1)) * kSpSlots + (ss & 3)) * kH1);
-#endif
   };
   if (h < n_vis) { look2(h % V, (h / V) & 3, m); pre_ask_hid(h % V, h / V); }
   else m[0][0] = kSpPoison;
@@ -615,14 +493,12 @@ __device__ void helper_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, in
     }
     // lanes 0-15: clip 2 cc, lanes 16-31: clip 2 cc + 1 (the upper half of the wave looks at the same words)
     hid_src = hid_base + ((int64_t)(2 * cc + ((lane >> 4) & 1)) * kSpSlots + (ss & 3)) * kH1;
-#if MMK_SP_PAIR_HID_PRE
     if (__all(hid_pre != kSpPoison)) {      // (asked for with the first look, and there)
       if (lane < 32) S.hidin[vv & (kXyRing - 1)][lane >> 4][lane & 15] = __uint_as_float(hid_pre);
       lds_signal(&S.hidin_ready[vv & 3], (unsigned)vv + 1, lane);
       hid_pre = kSpPoison;
       return;
     }
-#endif
     hid_w = msg_load(hid_src);
     hid_vv = vv;
   };
@@ -652,55 +528,11 @@ __device__ void helper_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, in
     if (a.stamps && vv / V == (int)a.n_steps / 2 && p == 0 && lane == 0 && vv % V < 32) a.stamps[256 + 1024 + stage * 32 + vv % V] = __builtin_amdgcn_s_memrealtime();
 #endif
     lds_signal(&S.arrived[vv & 3], (unsigned)vv + 1, lane);
-#if MMK_SP_WAKEUP
     asm volatile("s_wakeup");
-#endif
   };
   // look at the pair of messages of visit (cc, ss) until they are there, then stage them (the first look is in the registers already)
   auto await_and_stage = [&](int vv, int cc, int ss) -> bool {
     if (vv >= kXyRing - 2 && !lds_wait4(S.hdone, (unsigned)vv - (kXyRing - 2) + 1, a.err_flag)) return false;
-#if MMK_SP_PAIR_LOOKS >= 2
-    // Few visits per step - the step is one visit's trip, and what a hop waits for is the LAST of the eight CUs of a stage to see its messages: with one
-    // look out at a time a CU that has just missed them sees them a whole round trip later (diagnostic build, 64 clips: the first word of a pair is seen
-    // 0.3 - 0.5 us after the publish, the last CU's staging 1.0).  So several looks are in flight, a third of a round trip apart; they come back in the
-    // order they went out, and each is checked when it is there - the compiler counts the loads behind it (three register sets, the rotation unrolled).
-    if (!nap && !landed2(m)) {
-      u32x4s mb[4];
-#if MMK_SP_PAIR_LOOKS >= 3
-      u32x4s mc[4];
-#endif
-      look2(cc, ss & 3, m);
-      __builtin_amdgcn_s_sleep(MMK_SP_PAIR_LOOK_GAP);
-      look2(cc, ss & 3, mb);
-#if MMK_SP_PAIR_LOOKS >= 3
-      __builtin_amdgcn_s_sleep(MMK_SP_PAIR_LOOK_GAP);
-      look2(cc, ss & 3, mc);
-#endif
-      unsigned spins2 = 0;
-      for (;;) {
-        if (landed2(m)) break;
-        look2(cc, ss & 3, m);
-        if (landed2(mb)) {
-          stage_message(vv, mb);
-          ask_hid(vv, cc, ss);
-          return true;
-        }
-        look2(cc, ss & 3, mb);
-#if MMK_SP_PAIR_LOOKS >= 3
-        if (landed2(mc)) {
-          stage_message(vv, mc);
-          ask_hid(vv, cc, ss);
-          return true;
-        }
-        look2(cc, ss & 3, mc);
-#endif
-        if (++spins2 > kSpinLimit || ((spins2 & 1023u) == 0 && __hip_atomic_load(a.err_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-          atomicExch(a.err_flag, 1);
-          return false;
-        }
-      }
-    }
-#endif
     unsigned spins = 0;
 #if defined(MMK_DIAG) && defined(MMK_SP_PAIR_STAMP_ANY)
     bool any_seen = false;      // (timing variant of the diagnostic build: the "seen" stamp is the first look that shows ANY word of the pair - the rest of publish -> seen is the producers' spread)
@@ -722,9 +554,6 @@ __device__ void helper_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, in
         return false;
       }
       if (kPollGap > 0 && nap && spins > 1) __builtin_amdgcn_s_sleep(kPollGap);
-#if MMK_SP_PAIR_TRIP_GAP
-      if (!nap && spins > 1) __builtin_amdgcn_s_sleep(MMK_SP_PAIR_TRIP_GAP);
-#endif
       look2(cc, ss & 3, m);
     }
 #if defined(MMK_DIAG) && defined(MMK_SP_PAIR_STAMP_ANY)
@@ -732,19 +561,15 @@ __device__ void helper_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, in
 #endif
     stage_message(vv, m);
     ask_hid(vv, cc, ss);
-#if !MMK_SP_PAIR_HID_LATE
-    return take_hid();
-#else
     return true;
-#endif
   };
   for (int it = 0; it < n_vis; ++it) {
     const bool duty = (it & 3) == h;
-    // The rows are asked for and staged by the helper whose look duty was the visit BEFORE (MMK_SP_PAIR_ROWDUTY 1; 0: by the helper on look duty).  The registers
+    // The rows are asked for and staged by the helper whose look duty was the visit BEFORE, not by the helper on look duty.  The registers
     // a row is loaded into live across four iterations, so the compiler waits for them - and before they are overwritten - with a count of ZERO: behind every load
     // the wave has in flight.  On the look-duty helper that was the first look at the messages of visit it + 4, sent out a moment before: a full round trip per
     // visit in front of what the four helpers do in lock step.  One iteration later that look has long come back.
-    const bool rowduty = MMK_SP_PAIR_ROWDUTY ? ((it - 1) & 3) == h : duty;
+    const bool rowduty = ((it - 1) & 3) == h;
     // ---- 1. the visit's messages --------------------------------------------------------------------------------------------------------------
     if (duty) {
       if (!staged_next && !await_and_stage(it, cv, s)) return;
@@ -754,11 +579,6 @@ __device__ void helper_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, in
     //      are waited for with a count of zero (the loop's loads are not countable at compile time), i.e. behind every load in flight - with the look in front of it
     //      that wait was a full round trip of the look, once per visit, in front of everything the four helpers do in lock step (helpers alone, 128 clips: 88 -> 67 us
     //      per step without the rows' loads)
-#if MMK_SP_PAIR_ROWS_DMA
-    if (rowduty && it >= 5 && it + V - 5 < n_vis) {
-      if (!complete_rows_dma(2u * (unsigned)(it + V - 5), su, 2 * cu)) return;
-    }
-#else
     if (rowduty && it >= 5 && it + V - 5 < n_vis) {
       const unsigned u = (unsigned)(it + V - 5);
       if (d == 1) {
@@ -775,7 +595,6 @@ __device__ void helper_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, in
       }
       if (!stage_rows(2 * u, xr0, cr0) || !stage_rows(2 * u + 1, xr1, cr1)) return;
     }
-#endif
     if (duty) {
       if (it + 4 < n_vis) { look2(cl, sl & 3, m); pre_ask_hid(cl, sl); }
       else m[0][0] = kSpPoison;
@@ -796,17 +615,10 @@ __device__ void helper_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, in
     }
     if (!take_hid()) return;
     // ---- 3. the rows of visit it + roff (the helper that looked: its next look duty is four visits away) ------------------------------------------
-#if MMK_SP_PAIR_ROWS_DMA
-    if (rowduty && sa >= 1 && it + roff < n_vis) {
-      const unsigned cvr = 2u * (unsigned)(it + roff);
-      if (!request_rows_dma(sa, 2 * ca, cvr) || !request_rows_dma(sa, 2 * ca + 1, cvr + 1)) return;
-    }
-#else
     if (rowduty && sa >= 1 && it + roff < n_vis) {
       request_rows(sa, 2 * ca, d == 1, xr0, cr0);
       request_rows(sa, 2 * ca + 1, d == 1, xr1, cr1);
     }
-#endif
     if (++ca == V) { ca = 0; ++sa; }
     if (++cu == V) { cu = 0; ++su; }
     if (++cl == V) { cl = 0; ++sl; }
@@ -834,7 +646,7 @@ __global__ __launch_bounds__(kThreads) void wavenet_spipe_pair_kernel(const WnSp
   __syncthreads();
   const int role = s_role;
   if (role < 0) return;
-  const int stage = (role >> 3) - slot_shift(a), p = role & 7;
+  const int stage = role >> 3, p = role & 7;
   if (stage < 0 || stage > a.L) return;
   if (stage == a.L) {
     head_role<false>(a, p);

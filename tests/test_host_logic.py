@@ -226,6 +226,18 @@ def test_execution_switches_travel_in_the_config_not_in_the_environment(monkeypa
         assert text.count("getenv(") == (1 if src == "plan_util.h" else 0), f"{src} reads the environment"
 
 
+def test_kernels_keep_only_the_listed_build_switches():
+    """the kernels' `-D` overrides are the measurement instruments and the genuine build inputs; an experiment's switch is measured, its
+    winner kept unconditionally and the switch retired (docs/history.md, "Retired build switches") - not left in the kernel"""
+    keep = {"MMK_DIAG", "MMK_SOURCE_DIGEST", "MMK_FAST_RCP",
+            "MMK_SP_ABL", "MMK_SP_PAIR_TIMING", "MMK_BP_ABL", "MMK_STFT_ABL", "MMK_SQ_ABL", "MMK_IP_ABL"}
+    csrc = os.path.join(ROOT, "mimikit_amd", "csrc")
+    found = set()
+    for src in os.listdir(csrc):
+        found |= set(re.findall(r"^\s*#\s*if(?:n?def)\s+(MMK_\w+)", open(os.path.join(csrc, src)).read(), re.M))
+    assert found == keep
+
+
 def test_abi_argument_validation_needs_no_gpu():
     lib = native.load_library()
     cfg = native.WaveNetConfig()
