@@ -32,9 +32,10 @@
 extern "C" {
 #endif
 
-#define MMK_ABI_VERSION 4   /* 2: exec_mode in the WaveNet / SampleRNN / Seq2Seq configs, mmk_*_sync_status for all three, mmk_*_inject_sync_error;
+#define MMK_ABI_VERSION 5   /* 2: exec_mode in the WaveNet / SampleRNN / Seq2Seq configs, mmk_*_sync_status for all three, mmk_*_inject_sync_error;
                               * 3: `tuning` text at the end of the three configs - the library reads no environment variable;
-                              * 4: act_f / act_g in the WaveNet config, mlp_act in all three, mmk_srnn_resident_warmups */
+                              * 4: act_f / act_g in the WaveNet config, mlp_act in all three, mmk_srnn_resident_warmups;
+                              * 5: SimpleTransformer plans (mmk_tr_config, mmk_tr_*) */
 /* activations (mimikit/modules/activations.py: ActivationEnum, the members the HIP path evaluates) */
 #define MMK_ACT_IDENTITY 0
 #define MMK_ACT_TANH 1
@@ -64,7 +65,8 @@ extern "C" {
 typedef void* mmk_stream_t; /* hipStream_t */
 
 int mmk_abi_version(void);
-/* sizeof the config struct as this library was compiled: 0 mmk_wavenet_config, 1 mmk_srnn_config, 2 mmk_s2s_config; -1 for any other number -
+/* sizeof the config struct as this library was compiled: 0 mmk_wavenet_config, 1 mmk_srnn_config, 2 mmk_s2s_config, 3 mmk_tr_config; -1 for any
+ * other number -
  * what a binding that mirrors the structs by hand (ctypes, cgo, JNI) compares its own layout with before the first call */
 int64_t mmk_config_bytes(int which);
 /* a digest of the sources this library was compiled from (mimikit_amd/build.py: sha256 over every translation unit and header,
@@ -435,6 +437,57 @@ int mmk_s2s_sync_status(mmk_s2s_plan* plan, mmk_stream_t stream);
 int mmk_s2s_inject_sync_error(mmk_s2s_plan* plan, mmk_stream_t stream);
 /* diagnostic: bi-LSTM layers this plan has run as ONE resident launch since it was created */
 int64_t mmk_s2s_resident_launches(const mmk_s2s_plan* plan);
+
+/* ------------------------------------------------------------------------
+ * SimpleTransformer (mimikit/networks/transformers.py:70-178)
+ *
+ * One step recomputes the whole rf-long window as the reference does: X0 = input(x[t-rf:t]) + pe[0:rf], then num_layers post-norm
+ * nn.TransformerDecoderLayer blocks (causal self-attention, causal cross-attention with memory = X0, ReLU feed-forward, LayerNorm
+ * eps 1e-5), the optional final LayerNorm and the head on the last position only.  There is no state between steps: the positional
+ * encoding is tied to window positions, so every key changes at every step.
+ * ---------------------------------------------------------------------- */
+typedef struct mmk_tr_config {
+  int32_t model_dim;                       /* D: multiple of 16, 16 .. 1024 */
+  int32_t n_heads;                         /* head_dim = D / n_heads: multiple of 4, up to 128 */
+  int32_t feedforward_dim;                 /* 1 .. 4096 */
+  int32_t num_layers;                      /* 1 .. 16 */
+  int32_t rf;                              /* window length, 1 .. 2048 (the reference's positional-encoding length) */
+  int32_t final_norm;                      /* with_layer_norm: model.norm after the last layer */
+  int32_t in_kind;                         /* 0: class indices through nn.Embedding(in_classes, D); 1: frames of in_dim bins through Linear(in_dim, D) */
+  int32_t in_classes;
+  int32_t in_dim;
+  int32_t head_kind;                       /* 0: MLP (networks/mlp.py) + CategoricalSampler over out_dim classes; 1: Linear to out_dim bins [+ Abs] */
+  int32_t out_dim;
+  int32_t out_abs;                         /* head_kind 1: Abs after the Linear (IOSpec.magspec_io) */
+  int32_t mlp_hidden, mlp_n_hidden;        /* head_kind 0: width, number of extra hidden blocks (0 .. 4) */
+  int32_t mlp_act;                         /* head_kind 0: MMK_ACT_* code of MLPIO.activation */
+  int32_t learn_temp;                      /* head_kind 0: one more output, logits / max(sigmoid(it), min_temp) */
+  float min_temp;
+  int32_t max_batch;                       /* 1 .. 512 clips */
+  char tuning[MMK_TUNING_CHARS];           /* execution switches of THIS plan as "NAME=VALUE;..." (none are defined for this plan yet) */
+} mmk_tr_config;
+
+typedef struct mmk_tr_plan mmk_tr_plan;
+
+/* -1 with the offending field named in mmk_last_error for geometry outside the table above, -3 for IO options outside the coverage */
+int mmk_tr_plan_create(const mmk_tr_config* cfg, mmk_tr_plan** out);
+void mmk_tr_plan_destroy(mmk_tr_plan* plan);
+/* state_dict tensors by the reference's key names (model.layers.{l}.self_attn.in_proj_weight, ..., pe.pe as stored: (2048, 1, D)) */
+int mmk_tr_plan_bind(mmk_tr_plan* plan, const char* key, const float* dev_ptr, int64_t numel);
+size_t mmk_tr_workspace_bytes(const mmk_tr_plan* plan);
+int mmk_tr_commit(mmk_tr_plan* plan, void* workspace, size_t workspace_bytes, mmk_stream_t stream);
+/* SimpleTransformer.generate_step == eval forward (:159-178) on one window: x holds rf positions per clip (int64 classes, or fp32
+ * frames of in_dim bins with unit stride along the bins), `time_stride` elements apart, `batch_stride` between clips.  y receives one
+ * position per clip (a class, or out_dim bins), `y_batch_stride` apart.  temperature == NULL: argmax; else one temperature and one
+ * uniform per clip (uniforms[clip]) drive the inverse-CDF draw of mmk_categorical_sample_f32_i64. */
+int mmk_tr_step(mmk_tr_plan* plan, int32_t batch, const void* x, int64_t x_batch_stride, int64_t x_time_stride, void* y,
+                int64_t y_batch_stride, const float* temperature, const float* uniforms, mmk_stream_t stream);
+/* n_steps successive steps in place on the loop's (batch, T[, in_dim]) tensor: step t reads positions [t - rf, t) and writes position t,
+ * t = t0 .. t0 + n_steps - 1 (t0 >= rf; class tensors need time_stride 1).  uniforms: (batch, n_steps) row-major, column = step. */
+int mmk_tr_generate(mmk_tr_plan* plan, int32_t batch, void* data, int64_t batch_stride, int64_t time_stride, int64_t t0, int64_t n_steps,
+                    const float* temperature, const float* uniforms, mmk_stream_t stream);
+/* head_kind 0: the MLP's raw outputs of the last step, (batch, out_dim + learn_temp) rows copied to `out` with leading dimension out_ld */
+int mmk_tr_last_logits(mmk_tr_plan* plan, int32_t batch, float* out, int64_t out_ld, mmk_stream_t stream);
 
 #ifdef __cplusplus
 }

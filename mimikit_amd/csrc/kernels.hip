@@ -336,7 +336,8 @@ extern "C" int mmk_abi_version(void) { return MMK_ABI_VERSION; }
 static const char kBuildDigest[] = "mmk-source-digest:" MMK_SOURCE_DIGEST;
 extern "C" const char* mmk_build_digest(void) { return kBuildDigest + 18; }
 extern "C" int64_t mmk_config_bytes(int which) {
-  return which == 0 ? (int64_t)sizeof(mmk_wavenet_config) : which == 1 ? (int64_t)sizeof(mmk_srnn_config) : which == 2 ? (int64_t)sizeof(mmk_s2s_config) : -1;
+  return which == 0 ? (int64_t)sizeof(mmk_wavenet_config) : which == 1 ? (int64_t)sizeof(mmk_srnn_config) : which == 2 ? (int64_t)sizeof(mmk_s2s_config)
+       : which == 3 ? (int64_t)sizeof(mmk_tr_config) : -1;
 }
 extern "C" const char* mmk_last_error(void) { return mmk::g_err; }
 

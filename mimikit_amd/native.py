@@ -24,7 +24,7 @@ if DIAGNOSTIC and _DIAG != "1" and not _DIAG.endswith(".so"):
     raise ImportError(f"MMK_DIAG_LIB={_DIAG!r}: expected 1 (the diagnostic build) or the path of a library variant (*.so)")
 
 MAX_LAYERS, MAX_COND, MAX_TIERS, MAX_STREAMS = 128, 4, 8, 4
-ABI_VERSION = 4          # include/mmk.h: MMK_ABI_VERSION (bumped whenever a config struct or a signature changes)
+ABI_VERSION = 5          # include/mmk.h: MMK_ABI_VERSION (bumped whenever a config struct or a signature changes)
 ACT = {"none": 0, None: 0, "Identity": 0, "Tanh": 1, "Sigmoid": 2, "Mish": 3, "Abs": 4, "ReLU": 5, "Softplus": 6, "Sin": 7, "Cos": 8}      # include/mmk.h: MMK_ACT_*
 
 i32, i64, f32, vp, cp = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_char_p
@@ -135,6 +135,15 @@ class S2SConfig(C.Structure):
     ]
 
 
+class TransformerConfig(C.Structure):
+    _fields_ = [
+        ("model_dim", i32), ("n_heads", i32), ("feedforward_dim", i32), ("num_layers", i32), ("rf", i32), ("final_norm", i32),
+        ("in_kind", i32), ("in_classes", i32), ("in_dim", i32), ("head_kind", i32), ("out_dim", i32), ("out_abs", i32),
+        ("mlp_hidden", i32), ("mlp_n_hidden", i32), ("mlp_act", i32), ("learn_temp", i32), ("min_temp", f32), ("max_batch", i32),
+        ("tuning", C.c_char * TUNING_CHARS),
+    ]
+
+
 _SIGNATURES = {
     "mmk_abi_version": (i32, []),
     "mmk_config_bytes": (i64, [i32]),
@@ -204,6 +213,14 @@ _SIGNATURES = {
     "mmk_s2s_sync_status": (i32, [vp, vp]),
     "mmk_s2s_inject_sync_error": (i32, [vp, vp]),
     "mmk_s2s_resident_launches": (i64, [vp]),
+    "mmk_tr_plan_create": (i32, [C.POINTER(TransformerConfig), C.POINTER(vp)]),
+    "mmk_tr_plan_destroy": (None, [vp]),
+    "mmk_tr_plan_bind": (i32, [vp, cp, vp, i64]),
+    "mmk_tr_workspace_bytes": (C.c_size_t, [vp]),
+    "mmk_tr_commit": (i32, [vp, vp, C.c_size_t, vp]),
+    "mmk_tr_step": (i32, [vp, i32, vp, i64, i64, vp, i64, vp, vp, vp]),
+    "mmk_tr_generate": (i32, [vp, i32, vp, i64, i64, i64, i64, vp, vp, vp]),
+    "mmk_tr_last_logits": (i32, [vp, i32, vp, i64, vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -235,7 +252,7 @@ def load_library(path: Optional[str] = None):
         if have != want:
             raise NativeError(f"{path} was built from other sources (digest {have}, the tree's is {want}): rebuild with "
                               "`python -m mimikit_amd.build`")
-    for which, struct in enumerate((WaveNetConfig, SrnnConfig, S2SConfig)):
+    for which, struct in enumerate((WaveNetConfig, SrnnConfig, S2SConfig, TransformerConfig)):
         if lib.mmk_config_bytes(which) != C.sizeof(struct):
             raise NativeError(f"{struct.__name__} is {C.sizeof(struct)} bytes here and {lib.mmk_config_bytes(which)} in the library "
                               "(a stale libmmk_hip.so: rebuild with `python -m mimikit_amd.build`)")
@@ -890,4 +907,60 @@ class S2SPlan(_Plan):
         n = self.cfg.out_dim + (1 if self.cfg.learn_temp else 0)
         out = torch.empty((batch, self.cfg.hop, n), dtype=torch.float32, device=self.device)
         check(self._lib.mmk_s2s_last_logits(self.handle, batch, ptr(out), n, stream_ptr(self.device)), "mmk_s2s_last_logits")
+        return out
+
+
+class TransformerPlan(_Plan):
+    """SimpleTransformer (csrc/transformer_plan.hip): the state_dict is bound by the reference's key names, ``pe.pe`` as stored.
+    Class tensors are int64 (batch, T) with unit stride along time; frame tensors fp32 (batch, T, n_bins) with unit stride along the bins."""
+    _prefix = "mmk_tr"
+
+    def _check(self, x: torch.Tensor, what: str):
+        require_device(x)
+        if self.cfg.in_kind == 0:
+            if x.dtype != torch.int64 or x.dim() != 2 or x.stride(1) != 1:
+                raise ValueError(f"{what} must be int64 class indices (batch, T) with unit stride along time")
+        elif x.dtype != torch.float32 or x.dim() != 3 or x.stride(2) != 1 or x.shape[2] != self.cfg.in_dim:
+            raise ValueError(f"{what} must be fp32 frames (batch, T, {self.cfg.in_dim}) with unit stride along the bins")
+
+    def _sampling(self, batch: int, n: int, temperature, uniforms):
+        require_device(temperature, uniforms)
+        if temperature is None:
+            return None, None
+        if temperature.dtype != torch.float32 or not temperature.is_contiguous() or temperature.numel() != batch:
+            raise ValueError("temperature must be contiguous fp32, one per clip")
+        if uniforms is None or uniforms.dtype != torch.float32 or not uniforms.is_contiguous() or uniforms.numel() != batch * n:
+            raise ValueError(f"uniforms must be contiguous fp32 of shape ({batch}, {n})")
+        return ptr(temperature), ptr(uniforms)
+
+    def step(self, x: torch.Tensor, temperature: Optional[torch.Tensor] = None, uniforms: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x: the (batch, rf[, n_bins]) window -> (batch,) classes or (batch, n_bins) frames of the position after it"""
+        self._check(x, "the window")
+        if x.shape[1] != self.cfg.rf:
+            raise ValueError(f"the window holds {x.shape[1]} positions, rf is {self.cfg.rf}")
+        batch = x.shape[0]
+        if self.cfg.in_kind == 0:
+            y = torch.empty(batch, dtype=torch.int64, device=x.device)
+        else:
+            y = torch.empty((batch, self.cfg.out_dim), dtype=torch.float32, device=x.device)
+        tp, up = self._sampling(batch, 1, temperature, uniforms)
+        check(self._lib.mmk_tr_step(self.handle, batch, ptr(x), x.stride(0), x.stride(1), ptr(y), y.stride(0), tp, up,
+                                    stream_ptr(self.device)), "mmk_tr_step")
+        return y
+
+    def generate(self, data: torch.Tensor, t0: int, n_steps: int, temperature: Optional[torch.Tensor] = None,
+                 uniforms: Optional[torch.Tensor] = None):
+        """steps t0 .. t0 + n_steps - 1 in place on the loop's tensor; uniforms (batch, n_steps)"""
+        self._check(data, "the generated tensor")
+        if t0 < self.cfg.rf or n_steps < 0 or t0 + n_steps > data.shape[1]:
+            raise ValueError(f"steps [{t0}, {t0 + n_steps}) need rf={self.cfg.rf} positions before them and must lie in the tensor's {data.shape[1]}")
+        tp, up = self._sampling(data.shape[0], n_steps, temperature, uniforms)
+        check(self._lib.mmk_tr_generate(self.handle, data.shape[0], ptr(data), data.stride(0), data.stride(1), t0, n_steps, tp, up,
+                                        stream_ptr(self.device)), "mmk_tr_generate")
+
+    def last_logits(self, batch: int) -> torch.Tensor:
+        """the MLP head's raw outputs of the last step, (batch, out_dim + learn_temp)"""
+        n = self.cfg.out_dim + (1 if self.cfg.learn_temp else 0)
+        out = torch.empty((batch, n), dtype=torch.float32, device=self.device)
+        check(self._lib.mmk_tr_last_logits(self.handle, batch, ptr(out), n, stream_ptr(self.device)), "mmk_tr_last_logits")
         return out
