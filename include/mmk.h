@@ -32,10 +32,12 @@
 extern "C" {
 #endif
 
-#define MMK_ABI_VERSION 5   /* 2: exec_mode in the WaveNet / SampleRNN / Seq2Seq configs, mmk_*_sync_status for all three, mmk_*_inject_sync_error;
+#define MMK_ABI_VERSION 6   /* 2: exec_mode in the WaveNet / SampleRNN / Seq2Seq configs, mmk_*_sync_status for all three, mmk_*_inject_sync_error;
                               * 3: `tuning` text at the end of the three configs - the library reads no environment variable;
                               * 4: act_f / act_g in the WaveNet config, mlp_act in all three, mmk_srnn_resident_warmups;
-                              * 5: SimpleTransformer plans (mmk_tr_config, mmk_tr_*) */
+                              * 5: SimpleTransformer plans (mmk_tr_config, mmk_tr_*);
+                              * 6: building-block entry points mmk_gemm_f32, mmk_gemm_bias_act_f32, mmk_gemm_partial_floats,
+                              *    mmk_skinny_linear_f32, mmk_tr_attention_f32, mmk_tr_add_ln_f32; an `act` outside 0..8 is MMK_ERR_INVALID */
 /* activations (mimikit/modules/activations.py: ActivationEnum, the members the HIP path evaluates) */
 #define MMK_ACT_IDENTITY 0
 #define MMK_ACT_TANH 1
@@ -177,10 +179,44 @@ int64_t mmk_packed_weight_floats(int32_t n_rows, int32_t k_cols);
 /* W: (N, K) row-major fp32 with leading dimension ldw -> packed order */
 int mmk_pack_weight_f32(const float* w, int64_t ldw, int32_t n_rows, int32_t k_cols, float* packed,
                         mmk_stream_t stream);
-/* Y[M,N] = act(X[M,K] @ W^T + bias); act: 0 none, 1 tanh, 2 sigmoid, 3 mish, 4 abs, 5 relu
- * (nn.Linear / 1x1 nn.Conv1d as used by modules/io.py, networks/mlp.py) */
+/* Y[M,N] = act(X[M,K] @ W^T + bias); act: an MMK_ACT_* code, 0 none, 1 tanh, 2 sigmoid, 3 mish, 4 abs, 5 relu, 6 softplus
+ * (beta 1, threshold 20), 7 sin, 8 cos - any other code is MMK_ERR_INVALID (nn.Linear / 1x1 nn.Conv1d as used by modules/io.py,
+ * networks/mlp.py).  bias may be NULL. */
 int mmk_linear_f32(const float* x, int64_t ldx, int32_t m_rows, const float* packed_w, const float* bias,
                    int32_t n_rows, int32_t k_cols, float* y, int64_t ldy, int32_t act, mmk_stream_t stream);
+
+/* The kernels the plans are built from, each behind its own entry point so that it can be tested alone.  W is always a packed
+ * matrix of mmk_pack_weight_f32(.., n_rows, k_cols, ..); A must be 16-byte aligned with lda % 4 == 0 (MMK_ERR_UNSUPPORTED otherwise).
+ *
+ * C[b][M, N] = A[b][M, K] @ W^T for b < batch; A and C advance a_batch / c_batch floats per b (a_batch % 4 == 0).  The 64-row block
+ * of A is staged in LDS: K up to 624 (MMK_ERR_UNSUPPORTED beyond).  An ldc % 4 != 0 stores element by element. */
+int mmk_gemm_f32(const float* a, int64_t lda, int64_t a_batch, const float* packed_w, int32_t n_rows, int32_t k_cols, float* c,
+                 int64_t ldc, int64_t c_batch, int32_t m_rows, int32_t batch, mmk_stream_t stream);
+/* floats of the `partial` buffer mmk_gemm_bias_act_f32 needs to split K k_split ways (0: the launch's own choice; more ways than
+ * the K loop has 64-column stages: one per stage); 0 when that launch does not split */
+int64_t mmk_gemm_partial_floats(int32_t m_rows, int32_t n_rows, int32_t k_cols, int32_t k_split);
+/* C = act(A[M, K] @ W^T + bias), M >= 128 and K >= 16 (MMK_ERR_UNSUPPORTED otherwise - there is no other kernel behind it), bias may
+ * be NULL.  group > 0 scatters the rows: row m = (g, i), g = m / group, i = m % group, goes to c + g group_stride + i row_stride and
+ * rows with i >= kept are not written (ldc is then unused); group == 0: rows ldc apart.  partial: NULL (K is not split) or
+ * partial_floats >= mmk_gemm_partial_floats(m_rows, n_rows, k_cols, k_split) floats (MMK_ERR_WORKSPACE otherwise); k_split as
+ * there.  A split launch adds its partial sums in a fixed order: the result does not depend on the run. */
+int mmk_gemm_bias_act_f32(const float* a, int64_t lda, int32_t m_rows, const float* packed_w, const float* bias, int32_t n_rows,
+                          int32_t k_cols, float* c, int64_t ldc, int32_t act, int32_t group, int32_t kept, int64_t group_stride,
+                          int64_t row_stride, float* partial, int64_t partial_floats, int32_t k_split, mmk_stream_t stream);
+/* C = act(A[M, K] @ W^T + bias) for 1 <= M <= 64 and K a multiple of 128 up to 1024 (MMK_ERR_UNSUPPORTED otherwise); bias may be NULL */
+int mmk_skinny_linear_f32(const float* a, int64_t lda, int32_t m_rows, const float* packed_w, const float* bias, int32_t n_rows,
+                          int32_t k_cols, float* c, int64_t ldc, int32_t act, mmk_stream_t stream);
+/* Causal multi-head attention (csrc/transformer.h: TrAttnArgs): query row i < n_q of clip b at q + b q_cs + i q_ld is window
+ * position q_pos0 + i and sees keys 0 .. min(q_pos0 + i, n_keys - 1); key / value row j at k / v + b kv_cs + j kv_ld; head h uses the
+ * columns [h head_dim, (h + 1) head_dim) of every row; out row i at out + b o_cs + i o_ld; softmax(scale q k^T) v.
+ * head_dim: a multiple of 4 in [4, 128]; q_pos0 >= 0; n_keys >= 1 (MMK_ERR_INVALID otherwise). */
+int mmk_tr_attention_f32(const float* q, int64_t q_ld, int64_t q_cs, const float* k, const float* v, int64_t kv_ld, int64_t kv_cs,
+                         float* out, int64_t o_ld, int64_t o_cs, int32_t n_q, int32_t q_pos0, int32_t n_keys, int32_t n_heads,
+                         int32_t head_dim, float scale, int32_t batch, mmk_stream_t stream);
+/* out[r] = LayerNorm(y[r] + res[r]) * w + b over d columns, biased variance, eps 1e-5; res may be NULL (no residual) and out may be
+ * res (the same rows).  1 <= d <= 1024 (MMK_ERR_INVALID otherwise). */
+int mmk_tr_add_ln_f32(const float* y, int64_t y_ld, const float* res, int64_t res_ld, const float* w, const float* b, float* out,
+                      int64_t out_ld, int32_t rows, int32_t d, mmk_stream_t stream);
 
 /* MLP temperature column + CategoricalSampler
  * (mimikit/networks/mlp.py:58-63, mimikit/modules/targets.py:37-52).

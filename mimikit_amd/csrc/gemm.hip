@@ -366,3 +366,46 @@ int launch_gemm_bias_act(const float* A, int64_t lda, const float* Wp, const flo
 }
 
 }  // namespace mmk
+
+// ---- C ABI (include/mmk.h: building blocks) ----------------------------------------------------------------------------------
+extern "C" int mmk_gemm_f32(const float* a, int64_t lda, int64_t a_batch, const float* packed_w, int32_t n_rows, int32_t k_cols, float* c,
+                            int64_t ldc, int64_t c_batch, int32_t m_rows, int32_t batch, mmk_stream_t stream) {
+  using namespace mmk;
+  if (!a || !packed_w || !c || m_rows <= 0 || n_rows <= 0 || k_cols <= 0 || batch <= 0 || lda < k_cols || ldc < n_rows || a_batch < 0 ||
+      c_batch < 0)
+    return fail(MMK_ERR_INVALID, "gemm: bad arguments");
+  if (batch > 1 && (a_batch % 4) != 0) return fail(MMK_ERR_UNSUPPORTED, "gemm: a_batch %% 4 != 0");
+  return launch_gemm_f32(a, lda, a_batch, packed_w, (n_rows + 15) / 16, (k_cols + 15) / 16, n_rows, k_cols, c, ldc, c_batch, m_rows, batch,
+                         (hipStream_t)stream);
+}
+
+extern "C" int64_t mmk_gemm_partial_floats(int32_t m_rows, int32_t n_rows, int32_t k_cols, int32_t k_split) {
+  if (m_rows <= 0 || n_rows <= 0 || k_cols <= 0 || k_split < 0) return 0;
+  const int n_tiles = (n_rows + 15) / 16;
+  const int ks = mmk::gemm_bias_act_k_split(m_rows, n_tiles, (k_cols + 15) / 16, k_split);
+  return ks > 1 ? (int64_t)ks * m_rows * n_tiles * 16 : 0;
+}
+
+extern "C" int mmk_gemm_bias_act_f32(const float* a, int64_t lda, int32_t m_rows, const float* packed_w, const float* bias, int32_t n_rows,
+                                     int32_t k_cols, float* c, int64_t ldc, int32_t act, int32_t group, int32_t kept, int64_t group_stride,
+                                     int64_t row_stride, float* partial, int64_t partial_floats, int32_t k_split, mmk_stream_t stream) {
+  using namespace mmk;
+  if (!a || !packed_w || !c || m_rows <= 0 || n_rows <= 0 || k_cols <= 0 || lda < k_cols || k_split < 0 || group < 0 ||
+      (group == 0 && ldc < n_rows) || (group > 0 && (kept < 0 || kept > group || row_stride < n_rows || group_stride < 0)))
+    return fail(MMK_ERR_INVALID, "gemm_bias_act: bad arguments");
+  if (!act_code_ok(act)) return fail(MMK_ERR_INVALID, "gemm_bias_act: activation code %d", act);
+  if (!gemm_bias_act_supported(a, lda, m_rows, k_cols))
+    return fail(MMK_ERR_UNSUPPORTED, "gemm_bias_act: needs M >= 128, K >= 16 and a 16-byte aligned A with lda %% 4 == 0 (M=%d K=%d)", m_rows,
+                k_cols);
+  const int64_t need = mmk_gemm_partial_floats(m_rows, n_rows, k_cols, k_split);
+  if (partial && partial_floats < need) return fail(MMK_ERR_WORKSPACE, "gemm_bias_act: partial buffer of %lld floats, %lld needed",
+                                                    (long long)partial_floats, (long long)need);
+  if (!partial && k_split > 1 && need > 0) return fail(MMK_ERR_WORKSPACE, "gemm_bias_act: a %d-way split needs a partial buffer", k_split);
+  GemmRowMap rm;
+  rm.group = group;
+  rm.kept = kept;
+  rm.group_stride = group_stride;
+  rm.row_stride = row_stride;
+  return launch_gemm_bias_act(a, lda, packed_w, bias, (n_rows + 15) / 16, (k_cols + 15) / 16, n_rows, k_cols, c, ldc, m_rows, act,
+                              (hipStream_t)stream, rm, partial, partial_floats, k_split);
+}

@@ -455,6 +455,7 @@ extern "C" int mmk_linear_f32(const float* x, int64_t ldx, int32_t m_rows, const
   using namespace mmk;
   if (!x || !packed_w || !y || m_rows <= 0 || n_rows <= 0 || k_cols <= 0)
     return fail(MMK_ERR_INVALID, "linear: bad arguments");
+  if (!act_code_ok(act)) return fail(MMK_ERR_INVALID, "linear: activation code %d", act);
   LinearArgs a = {};
   a.nseg = 1;
   a.seg[0].x = addr_static(x);

@@ -96,6 +96,8 @@ __device__ __forceinline__ float mmk_rcp(float x) {
 }
 
 enum Act : int32_t { ACT_NONE = 0, ACT_TANH = 1, ACT_SIGMOID = 2, ACT_MISH = 3, ACT_ABS = 4, ACT_RELU = 5, ACT_SOFTPLUS = 6, ACT_SIN = 7, ACT_COS = 8 };      // (include/mmk.h: MMK_ACT_*)
+// what the entry points that take an `act` accept (apply_act passes any other code through unchanged)
+inline bool act_code_ok(int act) { return act >= ACT_NONE && act <= ACT_COS; }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float mishf_(float x) { return x * tanhf(log1pf(expf(x))); }

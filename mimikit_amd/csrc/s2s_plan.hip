@@ -278,6 +278,7 @@ static int derive(mmk_s2s_plan* p) {
 
 extern "C" int mmk_s2s_plan_create(const mmk_s2s_config* cfg, mmk_s2s_plan** out) {
   if (!cfg || !out) return fail(MMK_ERR_INVALID, "s2s_plan_create: null argument");
+  if (cfg->mlp_act < ACT_NONE || cfg->mlp_act > ACT_COS) return fail(MMK_ERR_INVALID, "s2s_plan_create: mlp_act %d outside MMK_ACT_*", cfg->mlp_act);
   mmk_s2s_plan* p = new mmk_s2s_plan();
   p->cfg = *cfg;
   p->tune.parse(cfg->tuning, sizeof(cfg->tuning));

@@ -115,3 +115,13 @@ int launch_skinny_linear(const float* A, int64_t lda, const float* Wp, const flo
 }
 
 }  // namespace mmk
+
+extern "C" int mmk_skinny_linear_f32(const float* a, int64_t lda, int32_t m_rows, const float* packed_w, const float* bias, int32_t n_rows,
+                                     int32_t k_cols, float* c, int64_t ldc, int32_t act, mmk_stream_t stream) {
+  using namespace mmk;
+  if (!a || !packed_w || !c || m_rows <= 0 || n_rows <= 0 || k_cols <= 0 || lda < k_cols || ldc < n_rows)
+    return fail(MMK_ERR_INVALID, "skinny linear: bad arguments");
+  if (!act_code_ok(act)) return fail(MMK_ERR_INVALID, "skinny linear: activation code %d", act);
+  return launch_skinny_linear(a, lda, packed_w, bias, (n_rows + 15) / 16, (k_cols + 15) / 16, n_rows, k_cols, c, ldc, m_rows, act,
+                              (hipStream_t)stream);
+}

@@ -289,6 +289,7 @@ static int derive(mmk_srnn_plan* p) {
 
 extern "C" int mmk_srnn_plan_create(const mmk_srnn_config* cfg, mmk_srnn_plan** out) {
   if (!cfg || !out) return fail(MMK_ERR_INVALID, "srnn_plan_create: null argument");
+  if (cfg->mlp_act < ACT_NONE || cfg->mlp_act > ACT_COS) return fail(MMK_ERR_INVALID, "srnn_plan_create: mlp_act %d outside MMK_ACT_*", cfg->mlp_act);
   mmk_srnn_plan* p = new mmk_srnn_plan();
   p->cfg = *cfg;
   p->tune.parse(cfg->tuning, sizeof(cfg->tuning));

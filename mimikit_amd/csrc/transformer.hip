@@ -133,7 +133,8 @@ __global__ __launch_bounds__(256) void tr_attention_kernel(const TrAttnArgs a) {
 size_t tr_attention_lds_bytes(int head_dim) { return (size_t)2 * kAttnKeys * (head_dim + 1) * sizeof(float); }
 
 int prepare_tr_attention(int head_dim) {
-  // head_dim 128: 66 KiB of dynamic LDS, above the 64 KiB a launch gets without asking (the CU has 160 KiB)
+  // head_dim 128: 66 KiB of dynamic LDS.  ROCm launches a kernel with up to the CU's 160 KiB without this attribute (gemm_f32_kernel asks
+  // for 157 KiB at K = 624 and sets none: tests/test_gpu_kernels_f64.py); it is set anyway, as the API's way of asking for more than 64 KiB
   const size_t lds = tr_attention_lds_bytes(head_dim);
   if (lds > 65536)
     MMK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tr_attention_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -272,3 +273,28 @@ int launch_tr_add_pe(float* x, const float* pe, int B, int rf, int D, hipStream_
 }
 
 }  // namespace mmk
+
+extern "C" int mmk_tr_attention_f32(const float* q, int64_t q_ld, int64_t q_cs, const float* k, const float* v, int64_t kv_ld, int64_t kv_cs,
+                                    float* out, int64_t o_ld, int64_t o_cs, int32_t n_q, int32_t q_pos0, int32_t n_keys, int32_t n_heads,
+                                    int32_t head_dim, float scale, int32_t batch, mmk_stream_t stream) {
+  using namespace mmk;
+  if (!q || !k || !v || !out || n_q < 0 || q_pos0 < 0 || n_heads < 1 || batch < 0)
+    return fail(MMK_ERR_INVALID, "tr attention: bad arguments");
+  if (head_dim < 4 || head_dim > 128 || head_dim % 4 != 0 || n_keys < 1)
+    return fail(MMK_ERR_INVALID, "tr attention: head_dim %d, %d keys", head_dim, n_keys);
+  MMK_TRY(prepare_tr_attention(head_dim));
+  TrAttnArgs a;
+  a.q = q; a.q_ld = q_ld; a.q_cs = q_cs;
+  a.k = k; a.v = v; a.kv_ld = kv_ld; a.kv_cs = kv_cs;
+  a.out = out; a.o_ld = o_ld; a.o_cs = o_cs;
+  a.n_q = n_q; a.q_pos0 = q_pos0; a.n_keys = n_keys; a.n_heads = n_heads; a.head_dim = head_dim;
+  a.scale = scale;
+  return launch_tr_attention(a, batch, (hipStream_t)stream);
+}
+
+extern "C" int mmk_tr_add_ln_f32(const float* y, int64_t y_ld, const float* res, int64_t res_ld, const float* w, const float* b, float* out,
+                                 int64_t out_ld, int32_t rows, int32_t d, mmk_stream_t stream) {
+  using namespace mmk;
+  if (!y || !w || !b || !out || rows < 0) return fail(MMK_ERR_INVALID, "tr layer norm: bad arguments");
+  return launch_tr_add_ln(y, y_ld, res, res_ld, w, b, out, out_ld, rows, d, (hipStream_t)stream);
+}

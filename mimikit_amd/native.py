@@ -24,7 +24,7 @@ if DIAGNOSTIC and _DIAG != "1" and not _DIAG.endswith(".so"):
     raise ImportError(f"MMK_DIAG_LIB={_DIAG!r}: expected 1 (the diagnostic build) or the path of a library variant (*.so)")
 
 MAX_LAYERS, MAX_COND, MAX_TIERS, MAX_STREAMS = 128, 4, 8, 4
-ABI_VERSION = 5          # include/mmk.h: MMK_ABI_VERSION (bumped whenever a config struct or a signature changes)
+ABI_VERSION = 6          # include/mmk.h: MMK_ABI_VERSION (bumped whenever a config struct or a signature changes)
 ACT = {"none": 0, None: 0, "Identity": 0, "Tanh": 1, "Sigmoid": 2, "Mish": 3, "Abs": 4, "ReLU": 5, "Softplus": 6, "Sin": 7, "Cos": 8}      # include/mmk.h: MMK_ACT_*
 
 i32, i64, f32, vp, cp = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_char_p
@@ -167,6 +167,12 @@ _SIGNATURES = {
     "mmk_packed_weight_floats": (i64, [i32, i32]),
     "mmk_pack_weight_f32": (i32, [vp, i64, i32, i32, vp, vp]),
     "mmk_linear_f32": (i32, [vp, i64, i32, vp, vp, i32, i32, vp, i64, i32, vp]),
+    "mmk_gemm_f32": (i32, [vp, i64, i64, vp, i32, i32, vp, i64, i64, i32, i32, vp]),
+    "mmk_gemm_partial_floats": (i64, [i32, i32, i32, i32]),
+    "mmk_gemm_bias_act_f32": (i32, [vp, i64, i32, vp, vp, i32, i32, vp, i64, i32, i32, i32, i64, i64, vp, i64, i32, vp]),
+    "mmk_skinny_linear_f32": (i32, [vp, i64, i32, vp, vp, i32, i32, vp, i64, i32, vp]),
+    "mmk_tr_attention_f32": (i32, [vp, i64, i64, vp, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, f32, i32, vp]),
+    "mmk_tr_add_ln_f32": (i32, [vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, vp]),
     "mmk_categorical_sample_f32_i64": (i32, [vp, i64, i32, i32, i32, f32, vp, vp, vp, i64, vp]),
     "mmk_wavenet_plan_create": (i32, [C.POINTER(WaveNetConfig), C.POINTER(vp)]),
     "mmk_wavenet_plan_destroy": (None, [vp]),
@@ -436,16 +442,71 @@ def pack_weight(w: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _act_code(act) -> int:
+    """an ACT name, or an MMK_ACT_* code passed through as it is (the library refuses codes outside 0..8)"""
+    return act if isinstance(act, int) else ACT[act]
+
+
 def linear(x: torch.Tensor, packed_w: torch.Tensor, bias: Optional[torch.Tensor], n: int, k: int,
-           act: str = "none") -> torch.Tensor:
+           act="none") -> torch.Tensor:
     require_device(x, packed_w, bias)
     x2 = x.reshape(-1, x.shape[-1])
     if x2.stride(-1) != 1:
         x2 = x2.contiguous()
     y = torch.empty((x2.shape[0], n), dtype=torch.float32, device=x.device)
     check(lib().mmk_linear_f32(ptr(x2), x2.stride(0), x2.shape[0], ptr(packed_w), ptr(bias), n, k, ptr(y), y.stride(0),
-                               ACT[act], stream_ptr(x.device)), "mmk_linear_f32")
+                               _act_code(act), stream_ptr(x.device)), "mmk_linear_f32")
     return y.reshape(*x.shape[:-1], n)
+
+
+# The single kernels behind the plans (include/mmk.h: building blocks), for the unit tests.  They write into caller-owned tensors at
+# the strides (in elements) they are given: the caller sizes the buffers, exactly as a C caller would.
+def gemm_f32(a: torch.Tensor, lda: int, a_batch: int, packed_w: torch.Tensor, n: int, k: int, c: torch.Tensor, ldc: int, c_batch: int,
+             m: int, batch: int = 1):
+    """C[b][m, n] = A[b][m, k] @ W^T (csrc/gemm.hip: gemm_f32_kernel)"""
+    require_device(a, packed_w, c)
+    check(lib().mmk_gemm_f32(ptr(a), lda, a_batch, ptr(packed_w), n, k, ptr(c), ldc, c_batch, m, batch, stream_ptr(a.device)),
+          "mmk_gemm_f32")
+
+
+def gemm_partial_floats(m: int, n: int, k: int, k_split: int = 0) -> int:
+    return int(lib().mmk_gemm_partial_floats(m, n, k, k_split))
+
+
+def gemm_bias_act(a: torch.Tensor, lda: int, m: int, packed_w: torch.Tensor, bias: Optional[torch.Tensor], n: int, k: int,
+                  c: torch.Tensor, ldc: int, act="none", row_map=(0, 0, 0, 0), partial: Optional[torch.Tensor] = None,
+                  k_split: int = 0):
+    """C = act(A @ W^T + bias) (csrc/gemm.hip: gemm_bias_act_kernel, gemm_split_reduce_kernel); row_map = (group, kept,
+    group_stride, row_stride); partial: gemm_partial_floats(m, n, k, k_split) floats, or None"""
+    require_device(a, packed_w, bias, c, partial)
+    group, kept, group_stride, row_stride = row_map
+    check(lib().mmk_gemm_bias_act_f32(ptr(a), lda, m, ptr(packed_w), ptr(bias), n, k, ptr(c), ldc, _act_code(act), group, kept,
+                                      group_stride, row_stride, ptr(partial), 0 if partial is None else partial.numel(), k_split,
+                                      stream_ptr(a.device)), "mmk_gemm_bias_act_f32")
+
+
+def skinny_linear(a: torch.Tensor, lda: int, m: int, packed_w: torch.Tensor, bias: Optional[torch.Tensor], n: int, k: int,
+                  c: torch.Tensor, ldc: int, act="none"):
+    """C = act(A @ W^T + bias) for m <= 64 (csrc/skinny.hip)"""
+    require_device(a, packed_w, bias, c)
+    check(lib().mmk_skinny_linear_f32(ptr(a), lda, m, ptr(packed_w), ptr(bias), n, k, ptr(c), ldc, _act_code(act),
+                                      stream_ptr(a.device)), "mmk_skinny_linear_f32")
+
+
+def tr_attention(q: torch.Tensor, q_ld: int, q_cs: int, k: torch.Tensor, v: torch.Tensor, kv_ld: int, kv_cs: int, out: torch.Tensor,
+                 o_ld: int, o_cs: int, n_q: int, q_pos0: int, n_keys: int, n_heads: int, head_dim: int, scale: float, batch: int):
+    """causal multi-head attention (csrc/transformer.hip: tr_attention_kernel); q / k / v / out point at row 0, column 0 of clip 0"""
+    require_device(q, k, v, out)
+    check(lib().mmk_tr_attention_f32(ptr(q), q_ld, q_cs, ptr(k), ptr(v), kv_ld, kv_cs, ptr(out), o_ld, o_cs, n_q, q_pos0, n_keys,
+                                     n_heads, head_dim, scale, batch, stream_ptr(q.device)), "mmk_tr_attention_f32")
+
+
+def tr_add_ln(y: torch.Tensor, y_ld: int, res: Optional[torch.Tensor], res_ld: int, w: torch.Tensor, b: torch.Tensor,
+              out: torch.Tensor, out_ld: int, rows: int, d: int):
+    """out = LayerNorm(y + res) * w + b, eps 1e-5 (csrc/transformer.hip: tr_add_ln_kernel); res None: no residual; out may be res"""
+    require_device(y, res, w, b, out)
+    check(lib().mmk_tr_add_ln_f32(ptr(y), y_ld, ptr(res), res_ld, ptr(w), ptr(b), ptr(out), out_ld, rows, d, stream_ptr(y.device)),
+          "mmk_tr_add_ln_f32")
 
 
 def categorical_sample(logits: torch.Tensor, n_classes: int, has_temp_col: bool, min_temp: float,

@@ -538,3 +538,15 @@ def test_several_inputs_and_targets_are_described_or_refused_by_name():
     wn = mmk.WaveNet.from_config(mmk.WaveNet.Config(io_spec=io_bad, blocks=(3,), dims_dilated=(32,), dims_1x1=(16,), residuals_dim=32, skips_dim=32)).eval()
     with pytest.raises(NotImplementedError, match="target 1"):
         wn._describe(4)
+
+
+@pytest.mark.parametrize("config,create", [("SrnnConfig", "mmk_srnn_plan_create"), ("S2SConfig", "mmk_s2s_plan_create")])
+@pytest.mark.parametrize("act", [-1, 9])
+def test_plan_create_refuses_an_unknown_mlp_act(config, create, act):
+    """an MLP activation outside MMK_ACT_* is refused where the plan is made (apply_act would pass it through as identity)"""
+    lib = native.load_library()
+    cfg = getattr(native, config)()
+    cfg.mlp_act = act
+    handle = native.vp()
+    assert getattr(lib, create)(native.C.byref(cfg), native.C.byref(handle)) == -1
+    assert b"mlp_act" in lib.mmk_last_error()
