@@ -148,7 +148,9 @@ int mmk_stft_f32(const float* x, int64_t x_row_stride, int32_t batch, int64_t n_
  * spec: (batch, n_frames, n_fft/2+1, 2) contiguous; coordinate 0: (real, imag), 1: (abs, angle)
  * [the reference's 'pol': abs * exp(1j * angle)].  out: (batch, hop * (n_frames - 1)).
  * work: mmk_istft_workspace_floats() floats of device scratch (0 for n_fft = 1024, where it may be NULL).
- * n_fft: a power of two in [64, 4096]; 1 <= hop < n_fft; n_frames >= 2. */
+ * n_fft: a power of two in [64, 4096]; 1 <= hop < n_fft; n_frames >= 2.
+ * out and work need no alignment beyond that of a float: the kernels that move 16 bytes at a time are taken only when both are
+ * 16-byte aligned, the element-wise forms otherwise. */
 int64_t mmk_istft_n_samples(int64_t n_frames, int32_t n_fft, int32_t hop);
 size_t mmk_istft_workspace_floats(int32_t batch, int64_t n_frames, int32_t n_fft);
 int mmk_istft_f32(const float* spec, int32_t coordinate, int32_t batch, int64_t n_frames, int32_t n_fft,
@@ -165,7 +167,7 @@ int mmk_istft_f32(const float* spec, int32_t coordinate, int32_t batch, int64_t 
  * init: (batch, n_frames, n_fft/2+1, 2) initial complex "angles" (torchaudio draws torch.rand of a
  * complex dtype: both parts uniform in [0, 1)), or NULL for rand_init=False (all 1 + 0i).
  * out: (batch, hop * (n_frames - 1)), which must exceed n_fft/2 (reflect padding).
- * work: mmk_gla_workspace_floats() floats of device scratch. */
+ * work: mmk_gla_workspace_floats() floats of device scratch, 8-byte aligned (MMK_ERR_WORKSPACE otherwise). */
 size_t mmk_gla_workspace_floats(int32_t batch, int64_t n_frames, int32_t n_fft, int32_t hop);
 int mmk_gla_f32(const float* mag, const float* init, int32_t batch, int64_t n_frames, int32_t n_fft,
                 int32_t hop, int32_t n_iter, float momentum, float* work, float* out, mmk_stream_t stream);

@@ -1251,7 +1251,8 @@ static int launch_istft_generic(const float* spec, const float* mag, int mode, i
   MMK_HIP(hipGetLastError());
   const int64_t n_out = (int64_t)hop * (n_frames - 1);
   if (n_out <= 0) return MMK_OK;
-  const bool v4 = (hop % 4) == 0;
+  // the vector form moves 16 bytes at a time through `work` and `out`: an `out` off that grid (mmk.h asks for no alignment) takes the scalar form
+  const bool v4 = (hop % 4) == 0 && ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(work)) & 15) == 0;
   const int64_t total = (int64_t)batch * (v4 ? n_out / 4 : n_out);
   int64_t blocks = (total + 255) / 256;
   blocks = blocks > 4096 ? 4096 : blocks;
@@ -1317,8 +1318,9 @@ extern "C" size_t mmk_gla_workspace_floats(int32_t batch, int64_t n_frames, int3
   const size_t wave = (size_t)hop * (size_t)(n_frames > 0 ? n_frames - 1 : 0);
   // n_fft = 1024 / 2048: two waveforms and two previous spectra (ping-pong of the fused iteration kernels);
   // other sizes: the waveform, phase estimates, previous spectrum and the windowed frames
-  return (size_t)batch * (((n_fft == 1024 || n_fft == 2048) ? 2 : 1) * wave + 4 * (size_t)n_frames * bins) +
-         mmk_istft_workspace_floats(batch, n_frames, n_fft);
+  // (the waveform region is padded to an even number of floats: the complex planes behind it are read and written 8 bytes at a time)
+  const size_t waves = ((size_t)batch * ((n_fft == 1024 || n_fft == 2048) ? 2 : 1) * wave + 1) & ~(size_t)1;
+  return waves + (size_t)batch * 4 * (size_t)n_frames * bins + mmk_istft_workspace_floats(batch, n_frames, n_fft);
 }
 
 extern "C" int mmk_gla_f32(const float* mag, const float* init, int32_t batch, int64_t n_frames, int32_t n_fft, int32_t hop, int32_t n_iter,
@@ -1327,6 +1329,7 @@ extern "C" int mmk_gla_f32(const float* mag, const float* init, int32_t batch, i
   if (!mag || !work || !out || batch <= 0 || n_frames <= 0 || n_iter < 0) return fail(MMK_ERR_INVALID, "gla: bad arguments");
   if (int rc = check_fft("gla", n_fft, hop)) return rc;
   if (!(momentum >= 0.f && momentum < 1.f)) return fail(MMK_ERR_INVALID, "gla: momentum must be in [0, 1), got %g", (double)momentum);
+  if (reinterpret_cast<uintptr_t>(work) & 7) return fail(MMK_ERR_WORKSPACE, "gla: work must be 8-byte aligned (complex planes)");
   const int64_t n_out = (int64_t)hop * (n_frames - 1);
   if (n_out <= n_fft / 2) return fail(MMK_ERR_INVALID, "gla: %lld frames give %lld samples, reflect padding needs more than %d",
                                       (long long)n_frames, (long long)n_out, n_fft / 2);
@@ -1392,7 +1395,7 @@ extern "C" int mmk_gla_f32(const float* mag, const float* init, int32_t batch, i
     return MMK_OK;
   }
   float* wave = work;
-  float* angles = wave + (size_t)batch * n_out;
+  float* angles = wave + (((size_t)batch * n_out + 1) & ~(size_t)1);      // 8-byte aligned for an odd batch * n_out too
   float* tprev = angles + spec_floats;
   float* frames = tprev + spec_floats;
   if (init) MMK_HIP(hipMemcpyAsync(angles, init, spec_floats * sizeof(float), hipMemcpyDeviceToDevice, s));

@@ -17,7 +17,7 @@ import pytest
 import torch
 
 from mimikit_amd import native
-from tests.f64_bounds import ACT_F, attention_bound, attention_ref, check_bound, check_near_miss, gemm_bound, ln_bound, ln_ref
+from tests.f64_bounds import ACT_F, attention_bound, attention_ref, check_bound, check_near_miss, check_written, gemm_bound, ln_bound, ln_ref
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -35,13 +35,6 @@ def gen(seed):
 
 def nan_dev(*shape):
     return torch.full(shape, NAN, dtype=torch.float32, device="cuda")
-
-
-def check_written(buf, mask, what):
-    """the non-NaN elements of the output buffer are exactly the ones the call had to write"""
-    written = ~torch.isnan(buf.cpu())
-    assert torch.equal(written, mask), f"{what}: {int((written & ~mask).sum())} elements written outside the output, " \
-                                       f"{int((mask & ~written).sum())} inside it left unwritten"
 
 
 # ================================================================================================================ dot products
