@@ -529,6 +529,7 @@ def categorical_sample(logits: torch.Tensor, n_classes: int, has_temp_col: bool,
 class _Plan:
     """Owns one native plan handle and its torch-allocated workspace."""
     _prefix = ""
+    _has_sync_status = False    # the library keeps an error word for this plan's waiting kernels (`<prefix>_sync_status`, `<prefix>_inject_sync_error`)
 
     def __init__(self, cfg_struct, device: torch.device):
         self._lib = lib()
@@ -576,6 +577,34 @@ class _Plan:
         check(getattr(self._lib, self._prefix + "_commit")(self.handle, aligned, need, stream_ptr(self.device)),
               self._prefix + "_commit")
         self.workspace_bytes = need
+
+    def sync_status(self):
+        """wait for the stream and raise if a wait between workgroups of one of the plan's kernels (a hand-off of the persistent
+        WaveNet kernels, the resident SampleRNN and bi-LSTM kernels) timed out"""
+        if not self._has_sync_status:
+            raise AttributeError(f"{type(self).__name__} has no sync_status: its kernels do not wait for each other")
+        check(getattr(self._lib, self._prefix + "_sync_status")(self.handle, stream_ptr(self.device)), self._prefix + "_sync_status")
+
+    def inject_sync_error(self):
+        """fault injection for tests: the next ``sync_status`` fails as after a timed-out wait (include/mmk.h)"""
+        if not self._has_sync_status:
+            raise AttributeError(f"{type(self).__name__} has no inject_sync_error: its kernels do not wait for each other")
+        check(getattr(self._lib, self._prefix + "_inject_sync_error")(self.handle, stream_ptr(self.device)),
+              self._prefix + "_inject_sync_error")
+
+    def _logit_columns(self, classes: str, target: int) -> int:
+        """columns of target k's raw head outputs: its classes (config field ``classes``, ``x_<classes>`` from target 1 on) and
+        the learned temperature's column"""
+        c = self.cfg
+        if target == 0:
+            return getattr(c, classes) + (1 if c.learn_temp else 0)
+        return getattr(c, "x_" + classes)[target] + (1 if c.x_learn_temp[target] else 0)
+
+    def _check_uniforms(self, uniforms: Optional[torch.Tensor], batch: int, n_steps: int):
+        n_tgt = max(int(self.cfg.n_targets), 1)
+        if uniforms is not None and (uniforms.dtype != torch.float32 or not uniforms.is_contiguous()
+                                     or uniforms.numel() != n_tgt * batch * n_steps):
+            raise ValueError("uniforms must be contiguous fp32 of shape (batch, n_steps) - (n_targets, batch, n_steps) with several targets")
 
 
 def pack_launch_count() -> int:
@@ -644,6 +673,8 @@ class WaveNetPlan(_Plan):
     """``in0`` / ``cond`` arguments are (batch, T[, dim]) tensors (or views) whose column 0 is
     absolute time ``t_first``; all ``t`` arguments are absolute times."""
     _prefix = "mmk_wavenet"
+    _has_sync_status = True
+    MODE_CHAIN, MODE_LPIPE, MODE_SPIPE, MODE_BPIPE = 2, 4, 5, 6      # mmk_wavenet_mode (include/mmk.h); 0: the per-layer launch path
 
     @property
     def rf(self) -> int:
@@ -677,10 +708,7 @@ class WaveNetPlan(_Plan):
                  t_first: int = 0):
         self._check_inputs(in0, cond)
         require_device(temperature, uniforms)
-        n_tgt = max(int(self.cfg.n_targets), 1)
-        if uniforms is not None and (uniforms.dtype != torch.float32 or not uniforms.is_contiguous()
-                                     or uniforms.numel() != n_tgt * in0.shape[0] * n_steps):
-            raise ValueError("uniforms must be contiguous fp32 of shape (batch, n_steps) - (n_targets, batch, n_steps) with several targets")
+        self._check_uniforms(uniforms, in0.shape[0], n_steps)
         ptrs, strides = _cond_arrays(cond, t_first)
         check(self._lib.mmk_wavenet_generate(self.handle, in0.shape[0], abs_ptr(in0, t_first), in0.stride(0), ptrs,
                                              strides, t0, n_steps, ptr(temperature), ptr(uniforms),
@@ -693,18 +721,18 @@ class WaveNetPlan(_Plan):
     @property
     def chain(self) -> bool:
         """persistent mode with one hand-off per layer (csrc/wavenet_chain.hip)"""
-        return self._lib.mmk_wavenet_mode(self.handle) == 2
+        return self._lib.mmk_wavenet_mode(self.handle) == self.MODE_CHAIN
 
     @property
     def layer_pipelined(self) -> bool:
         """persistent mode with four workgroups per clip that own whole layers (csrc/wavenet_lpipe.hip)"""
-        return self._lib.mmk_wavenet_mode(self.handle) == 4
+        return self._lib.mmk_wavenet_mode(self.handle) == self.MODE_LPIPE
 
     @property
     def stage_pipelined(self) -> bool:
         """persistent mode with one layer per stage of 8 CUs: the clips streamed through one at a time (csrc/wavenet_spipe.hip) or,
         large batches, in groups of 16 (csrc/wavenet_bpipe.hip)"""
-        return self._lib.mmk_wavenet_mode(self.handle) in (5, 6)
+        return self._lib.mmk_wavenet_mode(self.handle) in (self.MODE_SPIPE, self.MODE_BPIPE)
 
     @property
     def pair_visits(self) -> bool:
@@ -714,15 +742,7 @@ class WaveNetPlan(_Plan):
     @property
     def batch_pipelined(self) -> bool:
         """the stage pipeline with groups of 16 clips per visit on the matrix pipe (csrc/wavenet_bpipe.hip)"""
-        return self._lib.mmk_wavenet_mode(self.handle) == 6
-
-    def sync_status(self):
-        """wait for the stream and raise if a hand-off inside the persistent kernel timed out"""
-        check(self._lib.mmk_wavenet_sync_status(self.handle, stream_ptr(self.device)), "mmk_wavenet_sync_status")
-
-    def inject_sync_error(self):
-        """fault injection for tests: the next ``sync_status`` fails as after a timed-out hand-off (include/mmk.h)"""
-        check(self._lib.mmk_wavenet_inject_sync_error(self.handle, stream_ptr(self.device)), "mmk_wavenet_inject_sync_error")
+        return self._lib.mmk_wavenet_mode(self.handle) == self.MODE_BPIPE
 
     def profile_steps(self, in0: torch.Tensor, cond: Sequence[torch.Tensor], t0: int, n_steps: int, t_first: int = 0):
         """measurement aid: per-kernel-class device time from HIP events (see include/mmk.h);
@@ -737,9 +757,7 @@ class WaveNetPlan(_Plan):
         return {name: (ms[i], cnt[i]) for i, name in enumerate(("layer_a", "layer_b", "other"))}
 
     def last_logits(self, batch: int, target: int = 0) -> torch.Tensor:
-        c = self.cfg
-        n = (c.out_dim + (1 if c.learn_temp else 0)) if target == 0 else (c.x_out_dim[target] + (1 if c.x_learn_temp[target] else 0))
-        out = torch.empty((batch, n), dtype=torch.float32, device=self.device)
+        out = torch.empty((batch, self._logit_columns("out_dim", target)), dtype=torch.float32, device=self.device)
         check(self._lib.mmk_wavenet_last_logits_of(self.handle, target, batch, ptr(out), out.stride(0), stream_ptr(self.device)),
               "mmk_wavenet_last_logits_of")
         return out
@@ -849,6 +867,7 @@ def make_wavenet_plan(describe, batch: int, device) -> "WaveNetPlan":
 
 class SrnnPlan(_Plan):
     _prefix = "mmk_srnn"
+    _has_sync_status = True
 
     def reset(self):
         check(self._lib.mmk_srnn_reset(self.handle, stream_ptr(self.device)), "mmk_srnn_reset")
@@ -880,23 +899,12 @@ class SrnnPlan(_Plan):
         target k is written into idx[k]); uniforms: (batch, n_steps), (n_targets, batch, n_steps) with several targets"""
         idx = self._streams(idx)
         require_device(temperature, uniforms)
-        n_tgt = max(int(self.cfg.n_targets), 1)
-        if uniforms is not None and (uniforms.dtype != torch.float32 or not uniforms.is_contiguous()
-                                     or uniforms.numel() != n_tgt * idx[0].shape[0] * n_steps):
-            raise ValueError("uniforms must be contiguous fp32 of shape (batch, n_steps) - (n_targets, batch, n_steps) with several targets")
+        self._check_uniforms(uniforms, idx[0].shape[0], n_steps)
         ptrs = (vp * len(idx))(*[abs_ptr(x, t_first) for x in idx])
         strides = (i64 * len(idx))(*[x.stride(0) for x in idx])
         check(self._lib.mmk_srnn_generate_multi(self.handle, idx[0].shape[0], ptrs, strides, t0, n_steps,
                                                 ptr(temperature), ptr(uniforms), stream_ptr(self.device)),
               "mmk_srnn_generate_multi")
-
-    def sync_status(self):
-        """wait for the stream and raise if a wait inside the resident-mode kernels timed out"""
-        check(self._lib.mmk_srnn_sync_status(self.handle, stream_ptr(self.device)), "mmk_srnn_sync_status")
-
-    def inject_sync_error(self):
-        """fault injection for tests: the next ``sync_status`` reports a timed-out wait (include/mmk.h)"""
-        check(self._lib.mmk_srnn_inject_sync_error(self.handle, stream_ptr(self.device)), "mmk_srnn_inject_sync_error")
 
     def resident_blocks(self) -> int:
         """generate blocks run in resident mode so far (diagnostic, see include/mmk.h)"""
@@ -907,9 +915,7 @@ class SrnnPlan(_Plan):
         return int(self._lib.mmk_srnn_resident_warmups(self.handle))
 
     def last_logits(self, batch: int, target: int = 0) -> torch.Tensor:
-        c = self.cfg
-        n = (c.q_levels + (1 if c.learn_temp else 0)) if target == 0 else (c.x_q_levels[target] + (1 if c.x_learn_temp[target] else 0))
-        out = torch.empty((batch, n), dtype=torch.float32, device=self.device)
+        out = torch.empty((batch, self._logit_columns("q_levels", target)), dtype=torch.float32, device=self.device)
         check(self._lib.mmk_srnn_last_logits_of(self.handle, target, batch, ptr(out), out.stride(0), stream_ptr(self.device)),
               "mmk_srnn_last_logits_of")
         return out
@@ -917,6 +923,7 @@ class SrnnPlan(_Plan):
 
 class S2SPlan(_Plan):
     _prefix = "mmk_s2s"
+    _has_sync_status = True
 
     def step(self, x: torch.Tensor) -> torch.Tensor:
         require_device(x)
@@ -950,14 +957,6 @@ class S2SPlan(_Plan):
             raise ValueError("Seq2Seq classes must be int64 (batch, T)")
         check(self._lib.mmk_s2s_generate_classes(self.handle, classes.shape[0], ptr(classes), classes.stride(0), classes.stride(1),
                                                  t0, n_steps, classes.shape[1], stream_ptr(self.device)), "mmk_s2s_generate_classes")
-
-    def sync_status(self):
-        """wait for the stream and raise if a wait inside the resident bi-LSTM kernel timed out"""
-        check(self._lib.mmk_s2s_sync_status(self.handle, stream_ptr(self.device)), "mmk_s2s_sync_status")
-
-    def inject_sync_error(self):
-        """fault injection for tests: the next ``sync_status`` reports a timed-out wait (include/mmk.h)"""
-        check(self._lib.mmk_s2s_inject_sync_error(self.handle, stream_ptr(self.device)), "mmk_s2s_inject_sync_error")
 
     def resident_launches(self) -> int:
         """bi-LSTM layers run as one resident launch so far (diagnostic, see include/mmk.h)"""

@@ -10,7 +10,7 @@ continuous (magspec) frames or class indices (embedding in, MLP head + argmax ou
 """
 import dataclasses as dtc
 from enum import auto
-from typing import Dict, Set, Tuple
+from typing import Set, Tuple
 
 import torch
 import torch.nn as nn
@@ -20,12 +20,11 @@ from ..features.functionals import Continuous
 from ..features.item_spec import ItemSpec
 from ..io_spec import IOSpec
 from ..modules.io import ZipReduceVariables
-from ..modules.misc import Chunk
-from ..modules.mlp import MLP
-from ..modules.targets import CategoricalSampler, per_row_temperature
+from ..modules.targets import per_row_temperature
 from ..modules.resamplers import LinearResampler
 from ..utils import AutoStrEnum
-from .arm import ARMWithHidden, NetworkConfig, fold_weight_norm, weight_norm_leaves
+from .arm import ARMWithHidden, NetworkConfig, weight_norm_leaves
+from .hip_plan import HipPlanned, describe_head
 
 __all__ = ["EncoderLSTM", "DecoderLSTM", "Seq2SeqLSTMNetwork"]
 
@@ -118,7 +117,7 @@ class DecoderLSTM(nn.Module):
         return x
 
 
-class Seq2SeqLSTMNetwork(ARMWithHidden, nn.Module):
+class Seq2SeqLSTMNetwork(HipPlanned, ARMWithHidden, nn.Module):
     @dtc.dataclass
     class Config(NetworkConfig):
         io_spec: IOSpec = None
@@ -160,11 +159,6 @@ class Seq2SeqLSTMNetwork(ARMWithHidden, nn.Module):
         self.dec = decoder
         self.output_module = output_module
         self.output_length = lambda n: n
-        self._plan = None
-        self._plan_batch = 0
-        self._weights = native.WeightsTracker()
-        self.exec_tuning = {}   # execution switches of THIS network's plans ({"MMK_...": "0"}: include/mmk.h `tuning`); merged over native.PLAN_TUNING
-        self._plan_tuning = None            # the tuning text the plan at hand was built with
 
     # -- ARM properties -----------------------------------------------------------
     @property
@@ -228,28 +222,18 @@ class Seq2SeqLSTMNetwork(ARMWithHidden, nn.Module):
         if len(heads) != 1 or (discrete and len(cfg.io_spec.inputs) != 1):
             # (several continuous inputs are just added up, `input_module = sum`, :202-204: done in front of the plan)
             unsupported.append("more than one target, or more than one discrete input")
-        elif discrete:
-            head = heads[0]
-            est = getattr(head, "estimator", None)
-            mlp = est[0] if native.only_mlp(est) else None
-            if not isinstance(mlp, MLP) or not isinstance(getattr(head, "sampler", None), CategoricalSampler):
-                unsupported.append("discrete inputs with a head other than MLPIO + CategoricalSampler")
-            elif native.mlp_head_problem(mlp, self.training) or mlp.n_hidden_layers > 4:
-                unsupported.append(native.mlp_head_problem(mlp, self.training) or "MLP head with more than 4 hidden blocks")
-            else:
-                c.head_kind, c.mlp_hidden, c.mlp_n_hidden, c.mlp_act = 1, mlp.hidden_dim, mlp.n_hidden_layers, native.mlp_act(mlp)
-                c.learn_temp = int(mlp.learn_temperature)
-                c.min_temp = float(mlp.min_temp) if mlp.learn_temperature else 0.
-                c.out_dim = mlp.out_dim - int(mlp.learn_temperature)
         else:
-            head = heads[0]
-            lin = head[0] if isinstance(head, nn.Sequential) else None
-            tail = [m for m in list(head)[1:] if not (isinstance(m, Chunk) and m.chunks == 1)] if lin is not None else []
-            kinds = [type(m).__name__ for m in tail]
-            if not isinstance(lin, nn.Linear) or lin.bias is None or kinds not in ([], ["Abs"]):
+            kind, head, problem = describe_head(heads[0], self.training, need_sampler=discrete)
+            if discrete and kind != "mlp":
+                unsupported.append("discrete inputs with a head other than MLPIO + CategoricalSampler")
+            elif not discrete and (kind != "linear" or problem):
                 unsupported.append("output module other than (Chunked)LinearIO [+ Abs]")
+            elif problem:
+                unsupported.append(problem)
             else:
-                c.out_dim, c.out_abs = lin.out_features, int(kinds == ["Abs"])
+                c.head_kind = int(kind == "mlp")
+                for name, value in head.items():
+                    setattr(c, name, value)
         if unsupported:
             raise NotImplementedError("the HIP generate path does not cover: " + "; ".join(unsupported))
         c.in_dim = self.enc.input_dim
@@ -262,38 +246,27 @@ class Seq2SeqLSTMNetwork(ARMWithHidden, nn.Module):
         c.tuning = native.tuning_text(native.PLAN_TUNING, self.exec_tuning)       # execution switches of this plan (never the environment)
         return c
 
-    _blocks = ()            # generate_block calls since before_generate: (tensor, t0, n_steps)
-    _exec_mode = 0          # 1 while a call is being redone with one launch per frame (mmk_s2s_config.exec_mode)
-    _resident_seen = 0
+    # (the lifecycle: hip_plan.HipPlanned; _exec_mode 1: one bi-LSTM launch per frame; _blocks: (tensor, t0, n_steps))
+    _plan_class = native.S2SPlan
+    _weights_checked_every_call = True
     _plan_stale = False     # the plan is the one-launch-per-frame plan of a repeated call: replaced at the next _ensure_plan
 
-    def _ensure_plan(self, batch: int, refresh_weights: bool):
-        device = self.device
-        if device.type != "cuda":
-            raise RuntimeError("Seq2SeqLSTMNetwork generates on the MI355X only: move the network to the HIP device "
-                               "('cuda'); there is no CPU implementation in this package")
-        rebuilt = False
-        tuning = native.tuning_text(native.PLAN_TUNING, self.exec_tuning)
-        if self._plan is None or self._plan_tuning != tuning or self._plan_batch < batch or self._plan.device != device or (self._plan_stale and self._exec_mode == 0):
-            self._plan_stale = False
-            self._plan = native.S2SPlan(self._describe(max(batch, 1)), device)
-            self._plan_batch = max(batch, 1)
-            self._plan_tuning = tuning
-            self._resident_seen = 0
-            rebuilt = True
-        # every call: a step keeps no state between calls, but the plan holds a re-packed copy of the weights, and eval
-        # forward / generate_step may follow training steps or a load_state_dict at any time (per-epoch validation)
-        # (the content fingerprint - a device reduction and a read-back - only where a generation starts; the steps of one compare
-        # the host-side identity, which training steps and load_state_dict change)
-        if rebuilt or self._weights.changed(self, content=refresh_weights):
-            sd = self.state_dict()
-            for k, head in enumerate(getattr(self.output_module, "heads", [])):      # (a head with dropout modules between its Linears: the plan knows `fc.{2 i}`)
-                est = getattr(head, "estimator", None)
-                if native.only_mlp(est):
-                    sd = native.mlp_linear_keys(sd, f"output_module.heads.{k}.estimator.0.", est[0])
-            self._plan.bind_state_dict(fold_weight_norm(sd) if any(k.endswith("_g") for k in sd) else sd)
-            self._plan.commit()
-            self._weights.committed(self)
+    def _plan_is_stale(self, batch: int, tuning: bytes) -> bool:
+        """the plan of a repeated call (`_checked`) serves until its results were read, and not the call after"""
+        return self._plan_stale and self._exec_mode == 0
+
+    def _plan_rebuilt(self):
+        """a new plan counts its resident launches from 0 and is no longer the repeated call's"""
+        self._plan_stale = False
+        self._resident_seen = 0
+
+    def _heads(self):
+        """the heads sit under the ZipReduceVariables of ``output_module``"""
+        return [(f"output_module.heads.{k}.", head) for k, head in enumerate(getattr(self.output_module, "heads", []))]
+
+    def _folds_weight_norm(self, sd) -> bool:
+        """encoder and decoder take weight norm separately (and the decoder by the reference's mixed-up flag): ask the keys"""
+        return any(k.endswith("_g") for k in sd)
 
     def _checked(self, run, rerun=None):
         """``run()`` on the plan (``rerun`` if what has to be repeated differs); when a wait inside the resident bi-LSTM kernel (csrc/lstm_seq.hip: one launch per layer, its
@@ -375,13 +348,13 @@ class Seq2SeqLSTMNetwork(ARMWithHidden, nn.Module):
                 return None
             self._ensure_plan(frames.size(0), refresh_weights=False)
             self._plan.generate_classes(frames, t0, n_steps)
-            self._blocks = list(self._blocks) + [(frames, t0, n_steps)]
+            self._blocks.append((frames, t0, n_steps))
             return True
         if frames.dtype != torch.float32:
             return None
         self._ensure_plan(frames.size(0), refresh_weights=False)
         self._plan.generate(frames, t0, n_steps)
-        self._blocks = list(self._blocks) + [(frames, t0, n_steps)]
+        self._blocks.append((frames, t0, n_steps))
         return True
 
     def after_generate(self, final_outputs: Tuple[torch.Tensor, ...], batch_index) -> None:

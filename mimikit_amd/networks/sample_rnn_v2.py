@@ -10,7 +10,7 @@ stock differentiable torch graph (out of scope, kept for the trainer).
 """
 import dataclasses as dtc
 from enum import auto
-from typing import Dict, Iterable, List, Optional, Set, Tuple, Union
+from typing import Iterable, List, Optional, Set, Tuple
 
 import torch
 import torch.nn as nn
@@ -20,11 +20,10 @@ from ..features.functionals import Discrete
 from ..features.item_spec import ItemSpec
 from ..io_spec import IOSpec
 from ..modules.io import FramedConv1dIO, FramedLinearIO, ZipMode, ZipReduceVariables
-from ..modules.mlp import MLP
 from ..modules.resamplers import LinearResampler
-from ..modules.targets import OutputWrapper, per_row_temperature
 from ..utils import AutoStrEnum
-from .arm import fold_weight_norm, weight_norm_leaves, ARMWithHidden, NetworkConfig
+from .arm import weight_norm_leaves, ARMWithHidden, NetworkConfig
+from .hip_plan import HipPlanned, describe_head
 
 __all__ = ["SampleRNN", "SampleRNNTier"]
 
@@ -102,7 +101,7 @@ class SampleRNNTier(nn.Module):
         return x
 
 
-class SampleRNN(ARMWithHidden, nn.Module):
+class SampleRNN(HipPlanned, ARMWithHidden, nn.Module):
     @dtc.dataclass
     class Config(NetworkConfig):
         frame_sizes: Tuple[int, ...] = (16, 8, 8)
@@ -153,11 +152,6 @@ class SampleRNN(ARMWithHidden, nn.Module):
             weight_norm_leaves(self.output_modules)
         self.outputs = []
         self.prompt_length = 0
-        self._plan: Optional[native.SrnnPlan] = None
-        self._plan_batch = 0
-        self._weights = native.WeightsTracker()
-        self.exec_tuning = {}   # execution switches of THIS network's plans ({"MMK_...": "0"}: include/mmk.h `tuning`); merged over native.PLAN_TUNING
-        self._plan_tuning = None            # the tuning text the plan at hand was built with
         self._state_batch = 0
         self._next_t: Optional[int] = None
 
@@ -204,8 +198,8 @@ class SampleRNN(ARMWithHidden, nn.Module):
         prev = self.tiers[-1]((tuple(x[:, fs0 - fs:-1] for x in inputs), prev))
         return tuple(mod(prev) for mod in self.output_modules)
 
-    # -- HIP plan ---------------------------------------------------------------------
-    _exec_mode = 0          # 1 while a batch is being redone with the kernels in turns (mmk_srnn_config.exec_mode)
+    # -- HIP plan (the lifecycle: hip_plan.HipPlanned; _exec_mode 1: the tier and bottom kernels in turns, no resident mode) ---
+    _plan_class = native.SrnnPlan
 
     def _describe(self, max_batch: int) -> native.SrnnConfig:
         cfg, io = self._config, self._config.io_spec
@@ -224,37 +218,30 @@ class SampleRNN(ARMWithHidden, nn.Module):
             unsupported.append(f"rnn_class='{cfg.rnn_class}'")
         if len(cfg.frame_sizes) > native.MAX_TIERS:
             unsupported.append("too many tiers")
-        head = self.output_modules[0]
         c = native.SrnnConfig()
-        if isinstance(head, OutputWrapper) and native.only_mlp(head.estimator):
-            mlp: MLP = head.estimator[0]
-            if native.mlp_head_problem(mlp, self.training):
-                unsupported.append(native.mlp_head_problem(mlp, self.training))
-            else:
-                c.mlp_act = native.mlp_act(mlp)
-            if mlp.n_hidden_layers > 4:
-                unsupported.append("n_mlp_layers > 4")
-            c.mlp_hidden, c.mlp_n_hidden, c.learn_temp = mlp.hidden_dim, mlp.n_hidden_layers, int(mlp.learn_temperature)
-            c.q_levels = mlp.out_dim - c.learn_temp
-            c.min_temp = float(mlp.min_temp) if mlp.learn_temperature else 0.
+        kind, head, problem = describe_head(self.output_modules[0], self.training)
+        if kind != "mlp":
+            unsupported.append(f"output module of type {type(self.output_modules[0]).__name__}")
+        elif problem:
+            unsupported.append(problem)
         else:
-            unsupported.append(f"output module of type {type(head).__name__}")
+            c.q_levels = head.pop("out_dim")
+            for name, value in head.items():
+                setattr(c, name, value)
         # several inputs (every tier's ZipReduceVariables, :141-145, :160-173) and targets (:181-182)
         c.n_inputs, c.n_targets = n_in, n_tgt
         c.inputs_mode = {"sum": 0, "mean": 1, "static_mix": 2}[str(cfg.inputs_mode)]
         for m, spec in enumerate(io.inputs[:native.MAX_STREAMS]):
             c.in_class[m] = spec.elem_type.size
         for k in range(1, min(n_tgt, native.MAX_STREAMS)):
-            hk = self.output_modules[k]
-            if not (isinstance(hk, OutputWrapper) and native.only_mlp(hk.estimator)):
-                unsupported.append(f"output module {k} of type {type(hk).__name__}")
-                continue
-            mlp = hk.estimator[0]
-            if native.mlp_head_problem(mlp, self.training) or mlp.n_hidden_layers > 4 or native.mlp_act(mlp) != c.mlp_act:
-                unsupported.append(f"target {k}: {native.mlp_head_problem(mlp, self.training) or 'more than 4 hidden layers, or another activation than target 0'}")
-            c.x_mlp_hidden[k], c.x_mlp_n_hidden[k], c.x_learn_temp[k] = mlp.hidden_dim, mlp.n_hidden_layers, int(mlp.learn_temperature)
-            c.x_q_levels[k] = mlp.out_dim - c.x_learn_temp[k]
-            c.x_min_temp[k] = float(mlp.min_temp) if mlp.learn_temperature else 0.
+            kind_k, hk, problem = describe_head(self.output_modules[k], self.training)
+            if kind_k != "mlp":
+                unsupported.append(f"output module {k} of type {type(self.output_modules[k]).__name__}")
+            elif problem or hk["mlp_act"] != c.mlp_act:
+                unsupported.append(f"target {k}: {problem or 'another activation than target 0'}")
+            else:
+                c.x_mlp_hidden[k], c.x_mlp_n_hidden[k], c.x_learn_temp[k] = hk["mlp_hidden"], hk["mlp_n_hidden"], hk["learn_temp"]
+                c.x_q_levels[k], c.x_min_temp[k] = hk["out_dim"], hk["min_temp"]
         for k in range(min(n_tgt, n_in, native.MAX_STREAMS)):
             if (c.q_levels if k == 0 else c.x_q_levels[k]) > c.in_class[k]:
                 unsupported.append(f"target {k} draws classes that input {k} cannot take")
@@ -273,40 +260,19 @@ class SampleRNN(ARMWithHidden, nn.Module):
         c.max_batch = max_batch
         return c
 
-    def _ensure_plan(self, batch: int, refresh_weights: bool):
-        device = self.device
-        if device.type != "cuda":
-            raise RuntimeError("SampleRNN generates on the MI355X only: move the network to the HIP device ('cuda'); "
-                               "there is no CPU implementation in this package")
-        rebuilt = False
-        tuning = native.tuning_text(native.PLAN_TUNING, self.exec_tuning)
-        if self._plan is None or self._plan_tuning != tuning or self._plan_batch < batch or self._plan.device != device:
-            self._plan = native.SrnnPlan(self._describe(max(batch, 1)), device)
-            self._plan_batch = max(batch, 1)
-            self._plan_tuning = tuning
-            self._resident_seen = 0                          # (the new plan's resident-block counter starts over)
-            rebuilt = True
-        if rebuilt or refresh_weights:
-            if rebuilt or self._weights.changed(self, content=True):      # re-pack only when a parameter changed since the last commit
-                sd = self.state_dict()
-                for k, head in enumerate(self.output_modules):      # (a head with dropout modules between its Linears: the plans know `fc.{2 i}`)
-                    est = getattr(head, "estimator", None)
-                    if native.only_mlp(est):
-                        sd = native.mlp_linear_keys(sd, f"output_modules.{k}.estimator.0.", est[0])
-                self._plan.bind_state_dict(fold_weight_norm(sd) if self._config.weight_norm else sd)
-                self._plan.commit()
-                self._weights.committed(self)
-            else:
-                self._plan.reset()                           # hidden states back to h0, same packed weights
-            self._next_t = None
+    def _plan_rebuilt(self):
+        """the new plan's resident-block counter starts over"""
+        self._resident_seen = 0
 
-    def _sampling(self, batch: int, n_steps: int, parameters: Dict):
-        temperature = parameters.get("temperature", None)
-        if temperature is None:
-            return None, None
-        n_tgt = len(self.output_modules)
-        return (per_row_temperature(temperature, batch, self.device),
-                torch.rand((batch, n_steps) if n_tgt == 1 else (n_tgt, batch, n_steps), device=self.device, dtype=torch.float32))
+    def _weights_checked(self, repacked: bool):
+        """a generation starts from h0: packing the weights leaves the hidden states there, otherwise they are put back"""
+        if not repacked:
+            self._plan.reset()
+        self._next_t = None
+
+    def _folds_weight_norm(self, sd) -> bool:
+        """every parameter is a (g, v) pair when the config asks for weight norm (reference :67-81)"""
+        return bool(self._config.weight_norm)
 
     # -- ARM generation protocol ------------------------------------------------------
     def reset_hidden(self) -> None:
@@ -347,7 +313,7 @@ class SampleRNN(ARMWithHidden, nn.Module):
         for x in inputs:               # scratch copies of the windows with one free column for the produced step
             buf = torch.cat([x[:, -rf:], torch.zeros_like(x[:, :1])], dim=1)
             bufs.append((buf if buf.dtype == torch.int64 else buf.long()).contiguous())
-        temp, uni = self._sampling(batch, 1, parameters)
+        temp, uni = self._sampling(batch, 1, parameters.get("temperature"))
         self._plan.generate(tuple(bufs), t, 1, temp, uni, t_first=t - rf)
         self._next_t = t + 1
         return tuple(bufs[k][:, rf:rf + 1] for k in range(len(self.output_modules)))
@@ -361,40 +327,20 @@ class SampleRNN(ARMWithHidden, nn.Module):
             raise TypeError("generate_block writes in place: the tensors must be int64 class indices")
         if self._plan is None or self._next_t != t0 or self._state_batch != batch:
             self.before_generate(tuple(x[:, :t0] for x in tensors), None)
-        temp, uni = self._sampling(batch, n_steps, parameters)
+        temp, uni = self._sampling(batch, n_steps, parameters.get("temperature"))
         self._plan.generate(tensors, t0, n_steps, temp, uni, t_first=0)
         self._next_t = t0 + n_steps
-        getattr(self, "_blocks", []).append((tensors, t0, n_steps, dict(parameters)))
+        self._blocks.append((tensors, t0, n_steps, dict(parameters)))
         return True
 
     def after_generate(self, final_outputs: Tuple[torch.Tensor, ...], batch_index) -> None:
         self.outputs = []
-        if self._plan is not None and self._plan.resident_blocks() != getattr(self, "_resident_seen", 0):   # (a new plan counts from 0)
+        if self._plan is not None and self._plan.resident_blocks() != self._resident_seen:   # (a new plan counts from 0)
             # resident mode relies on the tier kernels and the bottom kernel running side by side; a wait that timed out (the
             # CUs were held by something else) leaves invalid samples: regenerate the batch once with the kernels in turns
             self._resident_seen = self._plan.resident_blocks()
             try:
                 self._plan.sync_status()
             except native.NativeError as err:
-                self._redo_in_turns(err)
+                self._redo_blocks(err, "with the tier and bottom kernels in turns")
         self.reset_hidden()
-
-    def _redo_in_turns(self, err):
-        import warnings
-        blocks, self._blocks = getattr(self, "_blocks", []), []
-        if not blocks or self._exec_mode == 1:
-            raise err
-        warnings.warn(f"{err}; regenerating this batch with the tier and bottom kernels in turns")
-        self._exec_mode = 1                      # the next plan is created with exec_mode = 1: no resident mode
-        try:
-            self._plan = None
-            first_tensors, first_t0 = blocks[0][0], blocks[0][1]
-            self.before_generate(tuple(x[:, :first_t0] for x in first_tensors), None)
-            for tensors, t0, n_steps, params in blocks:
-                self.generate_block(tensors, t0, n_steps, **params)
-            torch.cuda.synchronize(self.device)
-        finally:
-            self._exec_mode = 0
-            self._blocks = []
-            self._plan = None                    # the next generation may run resident again
-            self._next_t = None

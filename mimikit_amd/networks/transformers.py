@@ -23,9 +23,9 @@ from ..features.item_spec import ItemSpec, Step
 from ..io_spec import IOSpec
 from ..modules.io import ZipReduceVariables
 from ..modules.misc import Chunk
-from ..modules.mlp import MLP
-from ..modules.targets import CategoricalSampler, OutputWrapper, per_row_temperature
+from ..modules.targets import OutputWrapper
 from .arm import ARM, NetworkConfig
+from .hip_plan import HipPlanned, describe_head
 
 __all__ = ["PositionalEncoding", "SimpleTransformer"]
 
@@ -49,7 +49,7 @@ class PositionalEncoding(nn.Module):
         return self.dropout(x)
 
 
-class SimpleTransformer(ARM, nn.Module):
+class SimpleTransformer(HipPlanned, ARM, nn.Module):
     @dtc.dataclass
     class Config(NetworkConfig):
         io_spec: IOSpec = None
@@ -83,11 +83,6 @@ class SimpleTransformer(ARM, nn.Module):
         self.src_mask = None
         self.tgt_padding_mask = None
         self.pe = PositionalEncoding(config.model_dim, dropout=0., max_len=2048)
-        self._plan = None
-        self._plan_batch = 0
-        self._plan_tuning = None
-        self._weights = native.WeightsTracker()
-        self.exec_tuning = {}   # execution switches of THIS network's plans (include/mmk.h `tuning`); merged over native.PLAN_TUNING
 
     # -- ARM properties -----------------------------------------------------------
     @property
@@ -137,7 +132,10 @@ class SimpleTransformer(ARM, nn.Module):
             return self._forward_autograd(src, **parameters)
         return self._device_step(tuple(src), **parameters)
 
-    # -- HIP plan ---------------------------------------------------------------------
+    # -- HIP plan (the lifecycle: hip_plan.HipPlanned) ---------------------------------
+    _plan_class = native.TransformerPlan
+    _weights_checked_every_call = True
+
     def _describe(self, max_batch: int) -> native.TransformerConfig:
         cfg = self._config
         unsupported = []
@@ -155,27 +153,18 @@ class SimpleTransformer(ARM, nn.Module):
                 c.in_kind, c.in_dim = 1, core.in_features
             else:
                 unsupported.append(f"input module {type(core).__name__} (EmbeddingIO or ChunkedLinearIO are covered)")
-            head = self.output_modules[0]
-            if isinstance(head, OutputWrapper):
-                est = head.estimator
-                mlp = est[0] if native.only_mlp(est) else None
-                if not isinstance(mlp, MLP) or not isinstance(head.sampler, CategoricalSampler):
-                    unsupported.append("output module other than MLPIO + CategoricalSampler")
-                elif native.mlp_head_problem(mlp, self.training) or mlp.n_hidden_layers > 4:
-                    unsupported.append(native.mlp_head_problem(mlp, self.training) or "MLP head with more than 4 hidden layers")
-                else:
-                    c.head_kind, c.mlp_hidden, c.mlp_n_hidden, c.mlp_act = 0, mlp.hidden_dim, mlp.n_hidden_layers, native.mlp_act(mlp)
-                    c.learn_temp = int(mlp.learn_temperature)
-                    c.min_temp = float(mlp.min_temp) if mlp.learn_temperature else 0.
-                    c.out_dim = mlp.out_dim - int(mlp.learn_temperature)
+            sampled = isinstance(self.output_modules[0], OutputWrapper)
+            kind, head, problem = describe_head(self.output_modules[0], self.training, need_sampler=True)
+            if sampled and kind != "mlp":
+                unsupported.append("output module other than MLPIO + CategoricalSampler")
+            elif not sampled and (kind != "linear" or problem):
+                unsupported.append("output module other than (Chunked)LinearIO [+ Abs]")
+            elif problem:
+                unsupported.append(problem)
             else:
-                lin = head[0] if isinstance(head, nn.Sequential) else None
-                tail = [m for m in list(head)[1:] if not (isinstance(m, Chunk) and m.chunks == 1)] if lin is not None else []
-                kinds = [type(m).__name__ for m in tail]
-                if not isinstance(lin, nn.Linear) or lin.bias is None or kinds not in ([], ["Abs"]):
-                    unsupported.append("output module other than (Chunked)LinearIO [+ Abs]")
-                else:
-                    c.head_kind, c.out_dim, c.out_abs = 1, lin.out_features, int(kinds == ["Abs"])
+                c.head_kind = int(kind == "linear")
+                for name, value in head.items():
+                    setattr(c, name, value)
             if not unsupported and (c.in_kind == 0) != (c.head_kind == 0):
                 unsupported.append("class indices in with frames out, or frames in with class indices out")
         if unsupported:
@@ -185,36 +174,6 @@ class SimpleTransformer(ARM, nn.Module):
         c.max_batch = max_batch
         c.tuning = native.tuning_text(native.PLAN_TUNING, self.exec_tuning)
         return c
-
-    def _ensure_plan(self, batch: int, refresh_weights: bool):
-        device = self.device
-        if device.type != "cuda":
-            raise RuntimeError("SimpleTransformer generates on the MI355X only: move the network to the HIP device ('cuda'); "
-                               "there is no CPU implementation in this package")
-        rebuilt = False
-        tuning = native.tuning_text(native.PLAN_TUNING, self.exec_tuning)
-        if self._plan is None or self._plan_tuning != tuning or self._plan_batch < batch or self._plan.device != device:
-            self._plan = native.TransformerPlan(self._describe(max(batch, 1)), device)
-            self._plan_batch = max(batch, 1)
-            self._plan_tuning = tuning
-            rebuilt = True
-        # the plan holds a packed copy of the weights: re-bound after load_state_dict, training steps or .to(device) (the content
-        # fingerprint only where a generation starts; the steps of one compare the host-side identity)
-        if rebuilt or self._weights.changed(self, content=refresh_weights):
-            sd = self.state_dict()
-            est = getattr(self.output_modules[0], "estimator", None)
-            if native.only_mlp(est):
-                sd = native.mlp_linear_keys(sd, "output_modules.0.estimator.0.", est[0])
-            self._plan.bind_state_dict(sd)
-            self._plan.commit()
-            self._weights.committed(self)
-
-    def _sampling(self, batch: int, n_steps: int, temperature):
-        if temperature is None:
-            return None, None
-        t = per_row_temperature(temperature, batch, self.device)
-        u = torch.rand((batch, n_steps), device=self.device, dtype=torch.float32)
-        return t, u
 
     def _check_temperature(self, temperature):
         if temperature is not None and not isinstance(self.output_modules[0], OutputWrapper):

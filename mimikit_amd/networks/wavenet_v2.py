@@ -16,7 +16,7 @@ kept only so the network still drops into the reference's trainer).
 import dataclasses as dtc
 import operator
 from itertools import accumulate, chain
-from typing import Dict, Iterable, List, Optional, Set, Tuple
+from typing import Iterable, List, Optional, Set, Tuple
 
 import torch
 import torch.nn as nn
@@ -26,9 +26,8 @@ from ..features.item_spec import ItemSpec, Step
 from ..io_spec import IOSpec
 from ..modules.activations import ActivationConfig, ActivationEnum
 from ..modules.misc import CausalPad, Chunk, Transpose
-from ..modules.mlp import MLP
-from ..modules.targets import OutputWrapper, per_row_temperature
 from .arm import ARM, NetworkConfig
+from .hip_plan import HipPlanned, describe_head
 
 __all__ = ["WNLayer", "WaveNet"]
 
@@ -126,7 +125,7 @@ class WNLayer(nn.Module):
         return y, skips
 
 
-class WaveNet(ARM, nn.Module):
+class WaveNet(HipPlanned, ARM, nn.Module):
     @dtc.dataclass
     class Config(NetworkConfig):
         io_spec: IOSpec = None
@@ -218,11 +217,6 @@ class WaveNet(ARM, nn.Module):
         self.has_skips = config.skips_dim is not None
         self.output_modules = nn.ModuleList(output_modules)
         self.eval_slice = slice(-1, None) if config.pad_side == 1 else slice(0, 1)
-        self._plan: Optional[native.WaveNetPlan] = None
-        self._plan_batch = 0
-        self._weights = native.WeightsTracker()
-        self.exec_tuning = {}   # execution switches of THIS network's plans ({"MMK_...": "0"}: include/mmk.h `tuning`); merged over native.PLAN_TUNING
-        self._plan_tuning = None            # the tuning text the plan at hand was built with
         self._next_t: Optional[int] = None   # absolute time the queues are ready to produce
         self._state_batch = 0
 
@@ -294,9 +288,7 @@ class WaveNet(ARM, nn.Module):
                                f"for a receptive field of {rf}")
         return self._window_step(tuple(x[:, :rf] for x in inputs), t=rf, **parameters)
 
-    # -- HIP plan ---------------------------------------------------------------------
-    _exec_mode = 0          # 1 while a batch is being redone on the per-layer launch path (mmk_wavenet_config.exec_mode)
-
+    # -- HIP plan (the lifecycle: hip_plan.HipPlanned; _exec_mode 1: the per-layer launch path) -------------------------
     def _describe(self, max_batch: int) -> native.WaveNetConfig:
         cfg, io = self._config, self._config.io_spec
         unsupported = []
@@ -352,44 +344,27 @@ class WaveNet(ARM, nn.Module):
             c.cond_in_dim[j], c.cond_dim[j] = lin.in_features, lin.out_features
         c.bias, c.gated = int(cfg.bias), int(cfg.act_g is not None)
         c.act_f, c.act_g = native.ACT.get(str(cfg.act_f), 0), native.ACT.get(str(cfg.act_g), 0) if cfg.act_g is not None else 0
-        head = self.output_modules[0]
-        if isinstance(head, OutputWrapper) and native.only_mlp(head.estimator):
-            mlp: MLP = head.estimator[0]
-            if native.mlp_head_problem(mlp, self.training):
-                unsupported.append(native.mlp_head_problem(mlp, self.training))
-            else:
-                c.mlp_act = native.mlp_act(mlp)
-            c.head_kind, c.mlp_hidden, c.mlp_n_hidden = 0, mlp.hidden_dim, mlp.n_hidden_layers
-            c.learn_temp = int(mlp.learn_temperature)
-            c.out_dim = mlp.out_dim - c.learn_temp
-            c.min_temp = float(mlp.min_temp) if mlp.learn_temperature else 0.
-            if mlp.n_hidden_layers > 4:
-                unsupported.append("n_mlp_layers > 4")
-        elif isinstance(head, nn.Sequential) and isinstance(head[0], nn.Linear) and head[0].bias is not None:
-            tail = [m for m in list(head)[1:] if not (isinstance(m, Chunk) and m.chunks == 1)]
-            kinds = [type(m).__name__ for m in tail]
-            if kinds == ["Abs"]:
-                c.head_kind = 1
-            elif not kinds:
-                c.head_kind = 2
-            else:
-                unsupported.append(f"linear head followed by {kinds}")
-            c.out_dim = head[0].out_features
+        kind, head, problem = describe_head(self.output_modules[0], self.training)
+        if problem:
+            unsupported.append(problem)
+        elif kind == "mlp":
+            c.head_kind = 0
+            for name, value in head.items():
+                setattr(c, name, value)
         else:
-            unsupported.append(f"output module of type {type(head).__name__}")
+            c.head_kind, c.out_dim = (1 if head["out_abs"] else 2), head["out_dim"]
         # further targets (:293: one output module per target on the same vector): MLP heads whose class goes into input k
         c.n_targets = n_tgt
         for k in range(1, min(n_tgt, native.MAX_STREAMS)):
-            hk = self.output_modules[k]
-            if not (isinstance(hk, OutputWrapper) and native.only_mlp(hk.estimator)) or c.head_kind != 0:
+            kind_k, hk, problem = describe_head(self.output_modules[k], self.training)
+            if kind_k != "mlp" or c.head_kind != 0:
                 unsupported.append(f"target {k}: several targets need MLP heads with samplers")
                 continue
-            mlp = hk.estimator[0]
-            if native.mlp_head_problem(mlp, self.training) or mlp.n_hidden_layers > 4 or native.mlp_act(mlp) != c.mlp_act:
-                unsupported.append(f"target {k}: {native.mlp_head_problem(mlp, self.training) or 'more than 4 hidden layers, or another activation than target 0'}")
-            c.x_mlp_hidden[k], c.x_mlp_n_hidden[k], c.x_learn_temp[k] = mlp.hidden_dim, mlp.n_hidden_layers, int(mlp.learn_temperature)
-            c.x_out_dim[k] = mlp.out_dim - c.x_learn_temp[k]
-            c.x_min_temp[k] = float(mlp.min_temp) if mlp.learn_temperature else 0.
+            if problem or hk["mlp_act"] != c.mlp_act:
+                unsupported.append(f"target {k}: {problem or 'another activation than target 0'}")
+                continue
+            c.x_mlp_hidden[k], c.x_mlp_n_hidden[k], c.x_learn_temp[k] = hk["mlp_hidden"], hk["mlp_n_hidden"], hk["learn_temp"]
+            c.x_out_dim[k], c.x_min_temp[k] = hk["out_dim"], hk["min_temp"]
             if k - 1 < len(cfg.dims_1x1) and c.cond_q_levels[k - 1] < c.x_out_dim[k]:
                 unsupported.append(f"target {k} draws classes that input {k} (not a class stream of as many classes) cannot take")
         c.max_batch = max_batch
@@ -397,42 +372,24 @@ class WaveNet(ARM, nn.Module):
             raise NotImplementedError("the HIP generate path does not cover: " + "; ".join(unsupported))
         return c
 
-    def _ensure_plan(self, batch: int, refresh_weights: bool):
-        device = self.device
-        if device.type != "cuda":
-            raise RuntimeError("WaveNet generates on the MI355X only: move the network to the HIP device ('cuda'); "
-                               "there is no CPU implementation in this package")
-        rebuilt = False
-        tuning = native.tuning_text(native.PLAN_TUNING, self.exec_tuning)
-        stale = self._plan is None or self._plan_tuning != tuning or self._plan_batch < batch or self._plan.device != device
-        # the step kernel is chosen for the batch a plan is made for: one made for more than 128 clips serves groups of 16 clips per visit (~107 us per step
-        # whatever the batch), which a later call of fewer clips must not pay - it gets a plan of its own size (the ring: ~1.1 us per clip, 0.8 from 60 clips on)
-        if not stale and not native.wn_bpipe_by_default(batch) and getattr(self._plan, "batch_pipelined", False) and b"MMK_WN_BPIPE=1" not in tuning:
-            stale = True
-        if stale:
-            self._plan = native.make_wavenet_plan(self._describe, max(batch, 1), device)
-            self._plan_batch = max(batch, 1)
-            self._plan_tuning = tuning
-            rebuilt = True
-        if rebuilt or refresh_weights:
-            # the plan holds a re-packed copy of the weights: redo it only when a parameter changed since (optimiser step,
-            # load_state_dict, .to(device)); the reference's before_generate never touches the weights either.  The queues
-            # need no clearing: every slot a step reads is rewritten by the warm-up that precedes it.
-            if rebuilt or self._weights.changed(self, content=True):
-                self._plan.bind_state_dict(self._plan_tensors())
-                self._plan.commit()
-                self._weights.committed(self)
-            self._next_t = None
+    def _make_plan(self, batch: int, device):
+        """a batch beyond one launch of the stage pipeline runs as slices, each with a plan of its own"""
+        return native.make_wavenet_plan(self._describe, batch, device)
+
+    def _plan_is_stale(self, batch: int, tuning: bytes) -> bool:
+        """the step kernel is chosen for the batch a plan is made for: one made for more than 128 clips serves groups of 16 clips per visit (~107 us per step
+        whatever the batch), which a later call of fewer clips must not pay - it gets a plan of its own size (the ring: ~1.1 us per clip, 0.8 from 60 clips on)"""
+        return not native.wn_bpipe_by_default(batch) and self._plan.batch_pipelined and b"MMK_WN_BPIPE=1" not in tuning
+
+    def _weights_checked(self, repacked: bool):
+        """the queues need no clearing: every slot a step reads is rewritten by the warm-up that precedes it"""
+        self._next_t = None
 
     def _plan_tensors(self):
         """``state_dict`` as the plan binds it.  A grouped dilated convolution (``groups`` > 1, :93 of the reference) is
         handed over as the block-diagonal dense matrix it is: the kernels multiply whole channel tiles, and a zero
         weight adds exactly 0 to a sum, so the result is that of the grouped convolution."""
-        sd = self.state_dict()
-        for k, head in enumerate(self.output_modules):      # (a head with dropout modules between its Linears: the plans know `fc.{2 i}`)
-            est = getattr(head, "estimator", None)
-            if native.only_mlp(est):
-                sd = native.mlp_linear_keys(sd, f"output_modules.{k}.estimator.0.", est[0])
+        sd = super()._plan_tensors()
         groups = self._config.groups
         if groups == 1:
             return sd
@@ -448,16 +405,10 @@ class WaveNet(ARM, nn.Module):
             out[key] = w
         return out
 
-    def _sampling(self, batch: int, n_steps: int, parameters: Dict):
-        temperature = parameters.get("temperature", None)
-        if temperature is None:
+    def _sampling(self, batch: int, n_steps: int, temperature):
+        if self._plan.cfg.head_kind != 0:       # a linear head: no sampling
             return None, None
-        if self._plan.cfg.head_kind != 0:
-            return None, None
-        t = per_row_temperature(temperature, batch, self.device)
-        n_tgt = max(int(self._plan.cfg.n_targets), 1)
-        u = torch.rand((batch, n_steps) if n_tgt == 1 else (n_tgt, batch, n_steps), device=self.device, dtype=torch.float32)
-        return t, u
+        return super()._sampling(batch, n_steps, temperature)
 
     @staticmethod
     def _time_major(x: torch.Tensor) -> torch.Tensor:
@@ -494,7 +445,7 @@ class WaveNet(ARM, nn.Module):
         buf, cond = self._with_blank(in0, cond)
         t_first = t - rf
         self._plan.warmup(buf, cond, t_first, t - 1, t_first=t_first)
-        temp, uni = self._sampling(batch, 1, parameters)
+        temp, uni = self._sampling(batch, 1, parameters.get("temperature"))
         self._plan.generate(buf, cond, t, 1, temp, uni, t_first=t_first)
         self._next_t, self._state_batch = t + 1, batch
         return self._outputs(buf, cond, rf)
@@ -527,7 +478,7 @@ class WaveNet(ARM, nn.Module):
         # queues are in sync: only the newest position (t - 1) is consumed
         in0, cond = self._prepare(tuple(x[:, -1:] for x in inputs))
         buf, cond = self._with_blank(in0, cond)
-        temp, uni = self._sampling(batch, 1, parameters)
+        temp, uni = self._sampling(batch, 1, parameters.get("temperature"))
         self._plan.generate(buf, cond, t, 1, temp, uni, t_first=t - 1)
         self._next_t = t + 1
         return self._outputs(buf, cond, 1)
@@ -548,11 +499,11 @@ class WaveNet(ARM, nn.Module):
         for k in range(1, max(int(self._plan.cfg.n_targets), 1)):
             if cond[k - 1].data_ptr() != tensors[k].data_ptr():
                 raise TypeError(f"generate_block writes in place: tensors[{k}] must be int64 class indices, contiguous along time")
-        temp, uni = self._sampling(batch, n_steps, parameters)
+        temp, uni = self._sampling(batch, n_steps, parameters.get("temperature"))
         self._plan.generate(in0, cond, t0, n_steps, temp, uni, t_first=0)
         self._next_t = t0 + n_steps
         if self._plan.persistent:
-            getattr(self, "_blocks", []).append((tensors, t0, n_steps, dict(parameters)))
+            self._blocks.append((tensors, t0, n_steps, dict(parameters)))
         return True
 
     def after_generate(self, final_outputs: Tuple[torch.Tensor, ...], batch_index) -> None:
@@ -565,24 +516,4 @@ class WaveNet(ARM, nn.Module):
                 self._plan.sync_status()
                 self._blocks = []               # (nothing to redo: drop the references to the loop's tensors)
             except native.NativeError as err:
-                self._redo_on_launch_path(err)
-
-    def _redo_on_launch_path(self, err):
-        import warnings
-        blocks, self._blocks = getattr(self, "_blocks", []), []
-        if not blocks or self._exec_mode == 1:
-            raise err
-        warnings.warn(f"{err}; regenerating this batch on the per-layer launch path")
-        self._exec_mode = 1                     # the next plan is created with exec_mode = 1: one fused kernel per layer half
-        try:
-            self._plan = None
-            first_tensors, first_t0 = blocks[0][0], blocks[0][1]
-            self.before_generate(tuple(x[:, :first_t0] for x in first_tensors), None)
-            for tensors, t0, n_steps, params in blocks:
-                self.generate_block(tensors, t0, n_steps, **params)
-            torch.cuda.synchronize(self.device)
-        finally:
-            self._exec_mode = 0
-            self._blocks = []
-            self._plan = None                   # the next generation gets a persistent plan again
-            self._next_t = None
+                self._redo_blocks(err, "on the per-layer launch path")      # (exec_mode 1: one fused kernel per layer half)
