@@ -115,6 +115,27 @@ int64_t mmk_resample_n_out(int64_t n_in, int32_t orig, int32_t nnew);
 int mmk_resample_f32(const float* x, int64_t x_row_stride, int32_t batch, int64_t n_in, const float* table, int32_t orig,
                      int32_t nnew, int32_t width, float* out, int64_t out_row_stride, mmk_stream_t stream);
 
+/* One first-order filter section per row, torchaudio.functional.lfilter(x, a = [1, a1], b = [b0, b1], clamp=False):
+ *     y[n] = b0 x[n] + b1 x[n-1] - a1 y[n-1],    zero initial state, fp32
+ * - Emphasis (b = [1, -e], a1 = 0), Deemphasis (b = [1 - e, 0], a1 = -e) and RemoveDC (b = [1, -1], a1 = -0.99) of
+ * mimikit/features/functionals.py:211-288.  x, y: (batch, n) rows x_row_stride / y_row_stride elements apart (views of longer tensors),
+ * 4-byte aligned and no more; y may not overlap x.  a1 == 0 is one streaming pass and needs no workspace; otherwise the row is cut into
+ * chunks of MMK_LFILTER1_CHUNK samples (workgroups of MMK_LFILTER1_WG lanes that own MMK_LFILTER1_RUN consecutive samples each) and two
+ * launches scan it, with one float per chunk in `workspace` (mmk_lfilter1_workspace_floats floats; may be NULL where n fits one chunk).
+ * No atomics and one fixed order of every sum: the result is the same from run to run.  |a1| > 1 is MMK_ERR_UNSUPPORTED. */
+#define MMK_LFILTER1_RUN 16
+#define MMK_LFILTER1_WG 256
+#define MMK_LFILTER1_CHUNK 4096   /* = MMK_LFILTER1_RUN * MMK_LFILTER1_WG */
+size_t mmk_lfilter1_workspace_floats(int32_t batch, int64_t n);
+int mmk_lfilter1_f32(const float* x, int64_t x_row_stride, int32_t batch, int64_t n, float b0, float b1, float a1, float* y,
+                     int64_t y_row_stride, float* workspace, mmk_stream_t stream);
+/* torch.nn.functional.normalize(x, p, dim=-1, eps) per row: y = x / max(||x||_p, eps); p: 0 = inf, 1, 2 (MMK_ERR_UNSUPPORTED otherwise).
+ * Rows as above.  Two launches over chunks of MMK_LFILTER1_CHUNK samples: per-chunk partial norms into `workspace`
+ * (mmk_row_normalize_workspace_floats floats, always needed), added up in one fixed order by the scale pass. */
+size_t mmk_row_normalize_workspace_floats(int32_t batch, int64_t n);
+int mmk_row_normalize_f32(const float* x, int64_t x_row_stride, int32_t batch, int64_t n, int32_t p, float eps, float* y,
+                          int64_t y_row_stride, float* workspace, mmk_stream_t stream);
+
 /* STFT.torch_func with coordinate="mag" == MagSpec.torch_func
  * (mimikit/features/functionals.py:507-524, :576-606): periodic-Hann framed
  * real FFT magnitudes.  x: (batch, n_samples) rows `x_row_stride` apart,

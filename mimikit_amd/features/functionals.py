@@ -10,9 +10,12 @@ here:
   (:450-528, :576-606): the torch path runs as HIP kernels on the MI355X
   (``mimikit_amd/csrc/features.hip``); a tensor that is not on the HIP device is
   an error, there is no eager fallback.
-* ``FileToSignal``, ``Normalize``, ``RemoveDC``, ``Compose``, ``Identity``: unit /
-  elem_type carriers needed to build an ``IOSpec`` (dataset extraction itself is
-  out of scope).
+* ``FileToSignal``, ``Compose``, ``Identity``: unit / elem_type carriers needed to build an ``IOSpec`` (decoding
+  audio files is out of scope).
+* ``Emphasis`` / ``Deemphasis`` (:256-288), ``RemoveDC`` (:216-233) and ``Normalize`` (:236-253), the signal
+  conditioning around the mu-law codec: on a device tensor the three filters are one first-order section each
+  (``native.lfilter1``, a chunked scan in ``csrc/filters.hip``) and Normalize a two-stage row reduction
+  (``native.row_normalize``); float32 only.
 * ``ISTFT`` / ``GLA`` (:531-573, :609-646), the ``inv`` of STFT / MagSpec at the loop's tail, run on the HIP
   kernels of ``csrc/istft.hip`` / ``spectral2048.hip``; GLA's parity is unpinned (torchaudio is not installed in the
   build container).
@@ -31,7 +34,7 @@ from ..config import Config
 from .item_spec import Frame, Sample, Unit, convert
 
 __all__ = [
-    "Continuous", "Discrete", "Functional", "Identity", "Compose", "FileToSignal", "RemoveDC", "Normalize",
+    "Continuous", "Discrete", "Functional", "Identity", "Compose", "FileToSignal", "RemoveDC", "Normalize", "Emphasis", "Deemphasis",
     "MuLawCompress", "MuLawExpand", "STFT", "ISTFT", "MagSpec", "GLA", "Resample",
 ]
 
@@ -169,19 +172,59 @@ class FileToSignal(Functional):
 
 @dtc.dataclass
 class RemoveDC(Functional):
-    """DC-blocking one-pole filter of the extraction chain (reference :211-229); carried for its
-    (absent) unit / elem_type only."""
+    """DC-blocking one-pole filter of the extraction chain (reference :216-233): b = [1, -1], a = [1, -0.99].
+    The torch path runs that filter - the one of ``np_func`` - as a HIP kernel.  The reference's own torch path (:226-229) hands
+    ``lfilter`` its arguments in the wrong order (the coefficient vectors where the waveform belongs) and fails for every (B, T)
+    input, so there is no torch behaviour of the reference to differ from."""
 
     def np_func(self, inputs):
         from scipy.signal import lfilter
         return lfilter([1.0, -1.0], [1.0, -0.99], inputs, axis=-1).astype(inputs.dtype)
 
     def torch_func(self, inputs):
-        raise NotImplementedError("RemoveDC is a dataset-extraction step (numpy path only)")
+        from .. import native
+        return native.lfilter1(inputs, 1.0, -1.0, -0.99)
 
     @property
     def inv(self) -> Functional:
         return Identity()
+
+
+@dtc.dataclass
+class Emphasis(Functional):
+    """reference :256-271: y[n] = x[n] - emphasis x[n-1] (torchaudio's lfilter with b = [1, -e], a = [1, 0] on the torch path)"""
+    emphasis: float = 0.
+
+    def np_func(self, inputs):
+        from scipy.signal import lfilter
+        return lfilter([1, -self.emphasis], [1], inputs).astype(inputs.dtype)
+
+    def torch_func(self, inputs):
+        from .. import native
+        return native.lfilter1(inputs, 1.0, -self.emphasis, 0.0)
+
+    @property
+    def inv(self) -> Functional:
+        return Deemphasis(self.emphasis)
+
+
+@dtc.dataclass
+class Deemphasis(Functional):
+    """reference :274-288: y[n] = (1 - emphasis) x[n] + emphasis y[n-1] (b = [1 - e, 0], a = [1, -e]).  With the gain 1 - e this
+    is not the exact inverse of Emphasis: Deemphasis(e)(Emphasis(e)(x)) = (1 - e) x, as in the reference."""
+    emphasis: float = 0.
+
+    def np_func(self, inputs):
+        from scipy.signal import lfilter
+        return lfilter([1 - self.emphasis], [1, -self.emphasis], inputs).astype(inputs.dtype)
+
+    def torch_func(self, inputs):
+        from .. import native
+        return native.lfilter1(inputs, 1 - self.emphasis, 0.0, -self.emphasis)
+
+    @property
+    def inv(self) -> Functional:
+        return Emphasis(self.emphasis)
 
 
 @functools.lru_cache(maxsize=16)
@@ -253,7 +296,13 @@ class Normalize(Functional):
         return (inputs / np.maximum(norm, np.finfo(inputs.dtype).tiny)).astype(inputs.dtype)
 
     def torch_func(self, inputs):
-        raise NotImplementedError("Normalize is a dataset-extraction step (numpy path only)")
+        """reference :248-249: torch.nn.functional.normalize(inputs, p, dim) (eps 1e-12); over the last dimension for p in {inf, 1, 2}"""
+        from .. import native
+        if not isinstance(inputs, torch.Tensor) or inputs.dim() == 0 or self.dim not in (-1, inputs.dim() - 1):
+            raise NotImplementedError(f"Normalize(dim={self.dim}) is not on the HIP path: the last dimension only")
+        if self.p not in native.NORM_ORDERS:
+            raise NotImplementedError(f"Normalize(p={self.p}) is not on the HIP path: p in (inf, 1, 2) only")
+        return native.row_normalize(inputs, self.p)
 
     @property
     def inv(self) -> Functional:

@@ -156,6 +156,10 @@ _SIGNATURES = {
     "mmk_mulaw_expand_i64_f32": (i32, [vp, vp, i64, i32, f32, vp, vp]),
     "mmk_resample_n_out": (i64, [i64, i32, i32]),
     "mmk_resample_f32": (i32, [vp, i64, i32, i64, vp, i32, i32, i32, vp, i64, vp]),
+    "mmk_lfilter1_workspace_floats": (C.c_size_t, [i32, i64]),
+    "mmk_lfilter1_f32": (i32, [vp, i64, i32, i64, f32, f32, f32, vp, i64, vp, vp]),
+    "mmk_row_normalize_workspace_floats": (C.c_size_t, [i32, i64]),
+    "mmk_row_normalize_f32": (i32, [vp, i64, i32, i64, i32, f32, vp, i64, vp, vp]),
     "mmk_stft_n_frames": (i64, [i64, i32, i32, i32]),
     "mmk_stft_mag_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, vp, vp]),
     "mmk_stft_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, i32, i32, vp, vp]),
@@ -336,6 +340,53 @@ def resample(x: torch.Tensor, table: torch.Tensor, orig: int, new: int, width: i
     check(lib().mmk_resample_f32(ptr(x2), x2.stride(0), x2.shape[0], x2.shape[-1], ptr(table), orig, new, width, ptr(out), out.stride(0),
                                  stream_ptr(x.device)), "mmk_resample_f32")
     return out.reshape(*lead, n_out)
+
+
+# include/mmk.h: MMK_LFILTER1_RUN / _WG / _CHUNK - samples per lane, lanes per workgroup and samples per workgroup of the filter and
+# normalisation kernels (csrc/filters.hip); the tests place their lengths on these boundaries
+LFILTER1_RUN = 16
+LFILTER1_WG = 256
+LFILTER1_CHUNK = LFILTER1_RUN * LFILTER1_WG
+NORM_ORDERS = {float("inf"): 0, 1: 1, 2: 2}        # Normalize.p -> the `p` of mmk_row_normalize_f32
+
+
+def _float32_rows(x: torch.Tensor, what: str) -> torch.Tensor:
+    """the argument checks of the row kernels, before the device is asked for: they fail the same way without one"""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{what}: expected a torch.Tensor, got {type(x)}")
+    if x.dtype != torch.float32:
+        raise TypeError(f"{what} runs in float32 on the HIP path, got {x.dtype}")
+    require_device(x)
+    return _rows(x) if x.dim() else x.reshape(1, 1)
+
+
+def lfilter1(x: torch.Tensor, b0: float, b1: float, a1: float) -> torch.Tensor:
+    """x: (..., n) fp32 -> y of the same shape, y[n] = b0 x[n] + b1 x[n-1] - a1 y[n-1] along the last dimension from a zero state:
+    torchaudio.functional.lfilter(x, [1, a1], [b0, b1], clamp=False)"""
+    x2 = _float32_rows(x, "lfilter1")
+    batch, n = x2.shape
+    out = torch.empty((batch, n), dtype=torch.float32, device=x.device)
+    if out.numel() == 0:
+        return out.reshape(x.shape)
+    work = torch.empty((lib().mmk_lfilter1_workspace_floats(batch, n),), dtype=torch.float32, device=x.device) if a1 != 0 else None
+    check(lib().mmk_lfilter1_f32(ptr(x2), x2.stride(0), batch, n, b0, b1, a1, ptr(out), out.stride(0), ptr(work), stream_ptr(x.device)),
+          "mmk_lfilter1_f32")
+    return out.reshape(x.shape)
+
+
+def row_normalize(x: torch.Tensor, p: float, eps: float = 1e-12) -> torch.Tensor:
+    """x: (..., n) fp32 -> x / max(||x||_p, eps) over the last dimension, p in {inf, 1, 2}: torch.nn.functional.normalize"""
+    if p not in NORM_ORDERS:
+        raise NotImplementedError(f"row_normalize: p={p} is not on the HIP path (inf, 1 or 2)")
+    x2 = _float32_rows(x, "row_normalize")
+    batch, n = x2.shape
+    out = torch.empty((batch, n), dtype=torch.float32, device=x.device)
+    if out.numel() == 0:
+        return out.reshape(x.shape)
+    work = torch.empty((lib().mmk_row_normalize_workspace_floats(batch, n),), dtype=torch.float32, device=x.device)
+    check(lib().mmk_row_normalize_f32(ptr(x2), x2.stride(0), batch, n, NORM_ORDERS[p], eps, ptr(out), out.stride(0), ptr(work),
+                                      stream_ptr(x.device)), "mmk_row_normalize_f32")
+    return out.reshape(x.shape)
 
 
 def _rows(x: torch.Tensor) -> torch.Tensor:
