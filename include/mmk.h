@@ -136,6 +136,30 @@ size_t mmk_row_normalize_workspace_floats(int32_t batch, int64_t n);
 int mmk_row_normalize_f32(const float* x, int64_t x_row_stride, int32_t batch, int64_t n, int32_t p, float eps, float* y,
                           int64_t y_row_stride, float* workspace, mmk_stream_t stream);
 
+/* NearestNextNeighbor's alignment (mimikit/models/nnn.py:14-49): cosine distances of `batch` prompts of n frames against a corpus of m frames
+ * over k bins, then the subsequence DTW (steps (1,1), (0,1), (1,0), unit weights) whose last row's FIRST minimum is the end column:
+ *     D[0, j] = C[0, j],   D[i, 0] = D[i-1, 0] + C[i, 0],   D[i, j] = C[i, j] + min(D[i-1, j-1], D[i, j-1], D[i-1, j])
+ * (NearestNextNeighbor.predict_start_frame = end column + 1).  n <= MMK_NNN_MAX_ROWS (one wave per clip; MMK_ERR_UNSUPPORTED beyond),
+ * m < n is legal, n < 1, m < 1, k < 1 and batch < 1 are MMK_ERR_INVALID.  NaN in the inputs is not handled.
+ *
+ * mmk_inv_row_norm_f32: inv_norm[b * rows + r] = 1 / |x[b][r]|_2, and 0 for a row of norm 0 (sklearn's cosine distance leaves such a row as
+ * zeros: distance 1 to everything).  Rows are x_row_stride floats apart, clips x_batch_stride; 4-byte alignment is enough.
+ * mmk_cosine_cost_f32: cost[b][j][i] = clamp(1 - <|x_b,i|, |y_j|> rx[b * n + i] ry[j], 0, 2) - |.| is applied on load - as
+ * (batch, m, n_pad) contiguous floats, 16-byte aligned, n_pad = n rounded up to MMK_NNN_ROW_PAD (the padding holds 1).  k need not be a multiple
+ * of anything and tails are masked here, not padded by the caller.  fp32 MFMA with fp32 accumulation in one fixed order.
+ * mmk_dtw_subseq_f32: over such a cost tensor; end_col[b] (int64), end_val[b] = D[n-1, end_col[b]] and, where last_row is not NULL,
+ * last_row[b][j] = D[n-1, j] ((batch, m) contiguous).  Each D is one rounded add of an exact minimum: bit-identical to the sequential fp32
+ * loop over the same costs.  Costs are fetched MMK_NNN_LOOKAHEAD anti-diagonals ahead of the chain. */
+#define MMK_NNN_MAX_ROWS 64
+#define MMK_NNN_ROW_PAD 16
+#define MMK_NNN_LOOKAHEAD 16
+int mmk_inv_row_norm_f32(const float* x, int64_t x_batch_stride, int64_t x_row_stride, int32_t batch, int64_t rows, int32_t k,
+                         float* inv_norm, mmk_stream_t stream);
+int mmk_cosine_cost_f32(const float* x, int64_t x_batch_stride, int64_t x_row_stride, const float* rx, int32_t batch, int32_t n,
+                        const float* y, int64_t y_row_stride, const float* ry, int64_t m, int32_t k, float* cost, mmk_stream_t stream);
+int mmk_dtw_subseq_f32(const float* cost, int32_t batch, int32_t n, int64_t m, int64_t* end_col, float* end_val, float* last_row,
+                       mmk_stream_t stream);
+
 /* STFT.torch_func with coordinate="mag" == MagSpec.torch_func
  * (mimikit/features/functionals.py:507-524, :576-606): periodic-Hann framed
  * real FFT magnitudes.  x: (batch, n_samples) rows `x_row_stride` apart,

@@ -1,1 +1,2 @@
 from .ensemble_generator import *
+from .nnn import *

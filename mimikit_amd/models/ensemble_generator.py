@@ -9,6 +9,12 @@ ends the clip: what is left stays silent.  An exhausted stream raises ``StopIter
 Here the whole event runs on the device: ``Resample`` is the HIP polyphase kernel (``csrc/features.hip``), the network's
 input transforms and ``GenerateLoopV2`` are the package's own, and an event may name a network or a ``Checkpoint`` of this
 package (``.npz`` weights + the reference's YAML config, see ``mimikit_amd/checkpoint.py``).
+
+An event may also name a ``NearestNextNeighbor`` (``mimikit_amd/models/nnn.py``).  The reference lists the type but cannot run such an
+event (``run_event`` and ``get_n_steps`` read ``net.config``, which the class does not have), so its wiring is this package's: the prompt
+is resampled to ``nnn.sr`` and framed by ``nnn.feature``, ``generate_block`` returns the corpus frames that continue it - as many as
+``GenerateLoopV2.get_n_steps`` counts for a framed target - and ``nnn.feature.inv`` (Griffin-Lim) and ``Resample`` bring them back.  The
+event's temperature is ignored.
 """
 import dataclasses as dtc
 from typing import Dict, Iterator, Optional, Tuple, Union
@@ -21,21 +27,30 @@ from ..features.item_spec import Sample, convert
 from ..loops.generate import GenerateLoopV2
 from ..networks.arm import ARM
 from ..utils import default_device
+from .nnn import NearestNextNeighbor
 
 __all__ = ["Event", "EnsembleGenerator"]
 
 
 @dtc.dataclass
 class Event:
-    generator: Union[ARM, Checkpoint]
+    generator: Union[ARM, Checkpoint, NearestNextNeighbor]
     seconds: float
     temperature: Optional[float] = None
 
-    def network(self) -> ARM:
+    def __post_init__(self):
+        g = self.generator
+        if isinstance(g, NearestNextNeighbor):
+            if g.sr is None:
+                raise ValueError("a NearestNextNeighbor event needs the corpus' sample rate: NearestNextNeighbor(..., sr=...)")
+            if g.feature is None or not hasattr(g.feature, "inv") or getattr(g.feature, "unit", None) is None:
+                raise ValueError("a NearestNextNeighbor event needs the feature that framed the corpus (e.g. MagSpec): its inverse makes the audio")
+
+    def network(self) -> Union[ARM, NearestNextNeighbor]:
         g = self.generator
         if isinstance(g, Checkpoint):
             return g.network
-        if isinstance(g, ARM):
+        if isinstance(g, (ARM, NearestNextNeighbor)):
             return g
         raise TypeError(f"event generator type '{type(g)}' not supported")
 
@@ -88,11 +103,17 @@ class EnsembleGenerator:
     def next_event(self) -> Tuple[Event, ARM, int, Dict]:
         event = Event(**next(self.stream))
         net = event.network()
+        if isinstance(net, NearestNextNeighbor):
+            # GenerateLoopV2.get_n_steps for a framed target: the frames that cover the duration, and one more
+            n_steps = convert(int(net.sr * event.seconds), Sample(1), net.feature.unit, as_length=True) + 1
+            return event, net, n_steps, {}
         n_steps = GenerateLoopV2.get_n_steps(GenerateLoopV2.Config(output_duration_sec=event.seconds), net)
         return event, net, n_steps, event.loop_parameters()
 
     # -- one event ------------------------------------------------------------------------------------
-    def run_event(self, inputs: torch.Tensor, net: ARM, n_steps: int, params: Dict) -> torch.Tensor:
+    def run_event(self, inputs: torch.Tensor, net: Union[ARM, NearestNextNeighbor], n_steps: int, params: Dict) -> torch.Tensor:
+        if isinstance(net, NearestNextNeighbor):
+            return self.run_nnn_event(inputs, net, n_steps)
         spec = net.config.io_spec
         to_net, to_base = Resample(self.base_sr, spec.sr), Resample(spec.sr, self.base_sr)
         at_net_rate = to_net(inputs)
@@ -106,3 +127,9 @@ class EnsembleGenerator:
                               dataloader=[[torch.ones(1), *prompts]])      # (first entry: the prompt's index, unused without a logger)
         outputs = next(iter(loop.run()))
         return to_base(outputs[0][:, kept:])
+
+    def run_nnn_event(self, inputs: torch.Tensor, nnn: NearestNextNeighbor, n_frames: int) -> torch.Tensor:
+        to_nnn, to_base = Resample(self.base_sr, nnn.sr), Resample(nnn.sr, self.base_sr)
+        prompt = nnn.feature(to_nnn(inputs))
+        frames = nnn.generate_block(prompt, n_frames)
+        return to_base(nnn.feature.inv(frames))

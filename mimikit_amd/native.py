@@ -160,6 +160,9 @@ _SIGNATURES = {
     "mmk_lfilter1_f32": (i32, [vp, i64, i32, i64, f32, f32, f32, vp, i64, vp, vp]),
     "mmk_row_normalize_workspace_floats": (C.c_size_t, [i32, i64]),
     "mmk_row_normalize_f32": (i32, [vp, i64, i32, i64, i32, f32, vp, i64, vp, vp]),
+    "mmk_inv_row_norm_f32": (i32, [vp, i64, i64, i32, i64, i32, vp, vp]),
+    "mmk_cosine_cost_f32": (i32, [vp, i64, i64, vp, i32, i32, vp, i64, vp, i64, i32, vp, vp]),
+    "mmk_dtw_subseq_f32": (i32, [vp, i32, i32, i64, vp, vp, vp, vp]),
     "mmk_stft_n_frames": (i64, [i64, i32, i32, i32]),
     "mmk_stft_mag_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, vp, vp]),
     "mmk_stft_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, i32, i32, vp, vp]),
@@ -387,6 +390,87 @@ def row_normalize(x: torch.Tensor, p: float, eps: float = 1e-12) -> torch.Tensor
     check(lib().mmk_row_normalize_f32(ptr(x2), x2.stride(0), batch, n, NORM_ORDERS[p], eps, ptr(out), out.stride(0), ptr(work),
                                       stream_ptr(x.device)), "mmk_row_normalize_f32")
     return out.reshape(x.shape)
+
+
+# include/mmk.h: MMK_NNN_MAX_ROWS / _ROW_PAD / _LOOKAHEAD - prompt frames one wave aligns, the granule the cost rows of one corpus frame are
+# padded to, and the anti-diagonals the DTW kernel loads its costs ahead (csrc/nnn.hip); the tests place their sizes on these
+NNN_MAX_ROWS = 64
+NNN_ROW_PAD = 16
+NNN_LOOKAHEAD = 16
+
+
+def nnn_n_pad(n: int) -> int:
+    """floats between the costs of consecutive corpus frames in the cost tensor of ``cosine_cost``"""
+    return (n + NNN_ROW_PAD - 1) // NNN_ROW_PAD * NNN_ROW_PAD
+
+
+def _nnn_frames(x: torch.Tensor, dims: int, what: str) -> torch.Tensor:
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{what}: expected a torch.Tensor, got {type(x)}")
+    if x.dtype != torch.float32:
+        raise TypeError(f"{what} runs in float32 on the HIP path, got {x.dtype}")
+    if x.dim() != dims:
+        raise ValueError(f"{what}: expected {dims} dimensions, got shape {tuple(x.shape)}")
+    require_device(x)
+    return x if x.stride(-1) == 1 or x.shape[-1] == 1 else x.contiguous()
+
+
+def inv_row_norm(x: torch.Tensor) -> torch.Tensor:
+    """x: (rows, k) or (batch, rows, k) fp32, bins contiguous, rows and clips at any stride -> 1 / |row|_2 per row, 0 for a row of norm 0"""
+    x = _nnn_frames(x, 2 if isinstance(x, torch.Tensor) and x.dim() == 2 else 3, "inv_row_norm")
+    x3 = x.unsqueeze(0) if x.dim() == 2 else x
+    if x3.numel() == 0:
+        raise ValueError(f"inv_row_norm: empty input {tuple(x.shape)}")
+    out = torch.empty(x3.shape[:2], dtype=torch.float32, device=x.device)
+    check(lib().mmk_inv_row_norm_f32(ptr(x3), x3.stride(0), x3.stride(1), x3.shape[0], x3.shape[1], x3.shape[2], ptr(out),
+                                     stream_ptr(x.device)), "mmk_inv_row_norm_f32")
+    return out.reshape(x.shape[:-1])
+
+
+def cosine_cost(prompt_frames: torch.Tensor, corpus: torch.Tensor, corpus_inv_norm: torch.Tensor) -> torch.Tensor:
+    """prompt_frames (B, N, k), corpus (M, k), corpus_inv_norm (M,) = inv_row_norm(corpus) -> cost (B, M, nnn_n_pad(N)):
+    cost[b, j, i] = the cosine distance of |prompt row i of clip b| and |corpus row j|, clipped to [0, 2]; columns i >= N hold 1"""
+    x = _nnn_frames(prompt_frames, 3, "cosine_cost")
+    y = _nnn_frames(corpus, 2, "cosine_cost")
+    require_device(corpus_inv_norm)
+    batch, n, k = x.shape
+    m = y.shape[0]
+    if y.shape[1] != k:
+        raise ValueError(f"cosine_cost: the prompt has {k} bins, the corpus {y.shape[1]}")
+    if corpus_inv_norm.shape != (m,) or corpus_inv_norm.dtype != torch.float32 or not corpus_inv_norm.is_contiguous():
+        raise ValueError(f"cosine_cost: corpus_inv_norm must be {m} contiguous float32 values, got {tuple(corpus_inv_norm.shape)} {corpus_inv_norm.dtype}")
+    if n > NNN_MAX_ROWS:
+        raise NotImplementedError(f"cosine_cost: N = {n} prompt frames, the limit is {NNN_MAX_ROWS}")
+    if min(batch, n, m, k) < 1:
+        raise ValueError(f"cosine_cost: empty input (batch={batch}, N={n}, M={m}, bins={k})")
+    rx = inv_row_norm(x)
+    cost = torch.empty((batch, m, nnn_n_pad(n)), dtype=torch.float32, device=x.device)
+    check(lib().mmk_cosine_cost_f32(ptr(x), x.stride(0), x.stride(1), ptr(rx), batch, n, ptr(y), y.stride(0), ptr(corpus_inv_norm), m, k,
+                                    ptr(cost), stream_ptr(x.device)), "mmk_cosine_cost_f32")
+    return cost
+
+
+def dtw_subseq(cost: torch.Tensor, n: int, last_row: bool = False):
+    """cost: (B, M, nnn_n_pad(n)) as cosine_cost leaves it -> (end (B,) int64, dist (B,) fp32[, D[n-1, :] (B, M) fp32]) of the subsequence DTW"""
+    cost = _nnn_frames(cost, 3, "dtw_subseq")
+    if n > NNN_MAX_ROWS:
+        raise NotImplementedError(f"dtw_subseq: N = {n} prompt frames, the limit is {NNN_MAX_ROWS}")
+    if n < 1 or cost.shape[2] != nnn_n_pad(n) or not cost.is_contiguous():
+        raise ValueError(f"dtw_subseq: a contiguous cost tensor (B, M, {nnn_n_pad(max(n, 1))}) is expected for N = {n}, got {tuple(cost.shape)}")
+    batch, m = cost.shape[:2]
+    end = torch.empty((batch,), dtype=torch.int64, device=cost.device)
+    dist = torch.empty((batch,), dtype=torch.float32, device=cost.device)
+    row = torch.empty((batch, m), dtype=torch.float32, device=cost.device) if last_row else None
+    check(lib().mmk_dtw_subseq_f32(ptr(cost), batch, n, m, ptr(end), ptr(dist), ptr(row), stream_ptr(cost.device)), "mmk_dtw_subseq_f32")
+    return (end, dist, row) if last_row else (end, dist)
+
+
+def nnn_end_columns(prompt_frames: torch.Tensor, corpus: torch.Tensor, corpus_inv_norm: torch.Tensor):
+    """the column where the best subsequence-DTW alignment of each clip's (N, k) prompt frames against the (M, k) corpus ends, and its
+    accumulated cosine distance: (end (B,) int64, dist (B,) fp32), on torch's current stream, without a host round trip
+    (NearestNextNeighbor.predict_start_frame of the reference = end + 1)"""
+    cost = cosine_cost(prompt_frames, corpus, corpus_inv_norm)
+    return dtw_subseq(cost, prompt_frames.shape[1])
 
 
 def _rows(x: torch.Tensor) -> torch.Tensor:
