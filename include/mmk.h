@@ -186,6 +186,40 @@ int mmk_stft_f32(const float* x, int64_t x_row_stride, int32_t batch, int64_t n_
                  int32_t hop, int32_t center, int32_t reflect, int32_t coordinate, float* out,
                  mmk_stream_t stream);
 
+/* Envelop's frame energies (mimikit/features/functionals.py:816-818: MagSpec, then sum over the bins), without the spectrogram:
+ *     out[b][f] = sum_k |STFT_b[f][k]|,   k = 0 .. n_fft/2
+ * Frames, window (periodic Hann), padding (center, reflect as in mmk_stft_f32: reflect needs n_samples > n_fft/2) and the n_fft range
+ * (a power of two in [64, 4096], MMK_ERR_UNSUPPORTED otherwise) are those of mmk_stft_f32; out: (batch, mmk_stft_n_frames()) contiguous.
+ * An epilogue of the same transforms: a frame's magnitudes are added per lane in bin order, then over the wave (a butterfly) and, for
+ * the sizes that take a workgroup per frame pair, over the waves in order.  One float per frame is written: no atomics, no scratch,
+ * the same result from run to run. */
+int mmk_stft_energy_f32(const float* x, int64_t x_row_stride, int32_t batch, int64_t n_samples, int32_t n_fft,
+                        int32_t hop, int32_t center, int32_t reflect, float* out, mmk_stream_t stream);
+
+/* Interpolate (mimikit/features/functionals.py:867-916): each row resampled from n knots at 0 .. n-1 to n_out points, one streaming pass.
+ *   align 1: at np.linspace(0, n-1, n_out) - double(i) * step with step = (n-1) / (n_out-1) in float64 and the last position forced to n-1,
+ *            as numpy does, so a position is the double scipy.interpolate.interp1d sees (Interpolate.np_func)
+ *   align 0: at max(fma(float(n) / float(n_out), i + 0.5, -0.5), 0) in fp32, as the CPU kernel of torch.nn.functional.interpolate(mode="linear",
+ *            align_corners=False) computes it (Interpolate.torch_func; one rounding: its vectorised build fuses the two operations); n_out == n copies
+ *   mode  0: linear;  1: 'previous', y[floor(position)] (align 1 only).
+ * x: (batch, n) rows x_row_stride apart, y: (batch, n_out) rows y_row_stride apart, 4-byte aligned, not overlapping.
+ * n < 2, n_out < 1, another mode / align or 'previous' with align 0: MMK_ERR_INVALID. */
+#define MMK_INTERP_LINEAR 0
+#define MMK_INTERP_PREVIOUS 1
+int mmk_interp1d_f32(const float* x, int64_t x_row_stride, int32_t batch, int64_t n, float* y, int64_t y_row_stride, int64_t n_out,
+                     int32_t mode, int32_t align, mmk_stream_t stream);
+
+/* Derivative (mimikit/features/functionals.py:960-974, derivative_torch) as one pass.  With xp the odd reflection of the row about its ends,
+ * xp[-m] = x[0] + (x[0] - x[m]), xp[n-1+m] = x[n-1] + (x[n-1] - x[n-1-m]), and L = max_lag:
+ *     y[i] = sum_{d=1..L} ((xp[i+d] - x[i]) + (x[i] - xp[i-d])) * (1/d) / 2 / L
+ * added in lag order, each term rounded as the reference rounds it.  A workgroup stages MMK_DERIV_TILE samples and a halo of L on either
+ * side in LDS.  Rows as above.  n <= max_lag or max_lag < 1: MMK_ERR_INVALID; max_lag > MMK_DERIV_MAX_LAG: MMK_ERR_UNSUPPORTED
+ * (the reference's Samplifyer goes to 33). */
+#define MMK_DERIV_MAX_LAG 64
+#define MMK_DERIV_TILE 1024
+int mmk_derivative_f32(const float* x, int64_t x_row_stride, int32_t batch, int64_t n, int32_t max_lag, float* y, int64_t y_row_stride,
+                       mmk_stream_t stream);
+
 /* ISTFT.torch_func (mimikit/features/functionals.py:553-564):
  * torch.istft(spec^T, n_fft, hop, window=hann_window(n_fft)) with torch's defaults (center=True,
  * length=None): inverse real FFT of every frame, periodic-Hann window, overlap-add, division by the

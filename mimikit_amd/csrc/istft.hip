@@ -416,6 +416,9 @@ void istft1024q_kernel(const SpectralTables T, const float* __restrict__ spec, c
 
 // ---- STFT (center or not, constant or reflect padding) with five epilogues --------------------------------------------------
 // OUT 0: (re, im)   OUT 1: (|S|, angle S)   OUT 2: angle S   OUT 4: |S|  (MagSpec)   OUT 3: the Griffin-Lim phase update
+// OUT 5: sum_k |S[k]| of a frame, ONE float per frame in out (batch, n_frames) - the spectrogram is never stored (Envelop): OUT 4's
+//   magnitudes added up per lane in bin order (k = lane, lane + 64, ...), then a butterfly over the wave (the generic kernel: the waves'
+//   sums in wave order through LDS); no atomics, the same result from run to run
 //   angles = S - m tprev ; angles /= |angles| + 1e-16 ; tprev = S          (torchaudio functional.griffinlim, 2.0.1)
 // Two real frames per complex FFT, one pair per wave.
 struct StftRaw { float a[16], b[16]; };
@@ -843,12 +846,19 @@ void stft1024_kernel(const SpectralTables T, const float* __restrict__ x, int64_
       __builtin_amdgcn_wave_barrier();
     } else fft1024_wave_regtw<true>(v, buf, ltw, lane);
     // the two real spectra:  A[k] = (Z[k] + conj(Z[N-k])) / 2 ,  B[k] = (Z[k] - conj(Z[N-k])) / (2i)
+    cf32 esum = cf32{0.f, 0.f};                              // OUT 5: this lane's share of sum |A|, sum |B|
 #pragma unroll
     for (int jj = 0; jj < 9; ++jj) {
       const int k = lane + 64 * jj;
       if (k < bins) {
         const cf32 z = buf[fft_swz(lane) + 64 * jj];
         const cf32 zc = buf[(((N - k) & (N - 1)) & ~63) | fft_swz((64 - lane) & 63)];
+        if (OUT == 5) {                                       // the magnitudes of OUT 4, kept
+          const cf32 pz = z + zc, mz = z - zc;
+          const cf32 pp = pz * pz, mm = mz * mz;
+          esum += cf32{0.5f * __builtin_amdgcn_sqrtf(pp.x + mm.y), 0.5f * __builtin_amdgcn_sqrtf(pp.y + mm.x)};
+          continue;
+        }
         if (OUT == 4) {
           // MagSpec: with p = Z[k] + Z[N-k], m = Z[k] - Z[N-k] (two packed ops), |A| = sqrt(p.x^2 + m.y^2) / 2 and
           // |B| = sqrt(p.y^2 + m.x^2) / 2: packed squares, the hardware square root (1 ulp; the reference's abs() of a complex64 is
@@ -880,6 +890,14 @@ void stft1024_kernel(const SpectralTables T, const float* __restrict__ x, int64_
             *reinterpret_cast<cf32*>(tprev + 2 * e) = s[q];
           }
         }
+      }
+    }
+    if (OUT == 5) {
+      const float ea_sum = spectral_wave_sum(esum.x), eb_sum = spectral_wave_sum(esum.y);
+      if (lane == 0) {
+        float* o = out + b * n_frames + f0;
+        o[0] = ea_sum;
+        if (has_b) o[1] = eb_sum;
       }
     }
     __builtin_amdgcn_wave_barrier();                        // buf is rewritten by the next pair
@@ -983,6 +1001,7 @@ __global__ __launch_bounds__(256) void stft_generic_kernel(const float* __restri
     __syncthreads();
     const float2* src = stockham_fft(buf0, buf1, tw, N, tid, nt);
     const int64_t ea = (b * n_frames + f0) * bins;
+    float esum[2] = {0.f, 0.f};                             // OUT 5: this thread's share of sum |A|, sum |B|
     for (int k = tid; k < bins; k += nt) {
       const float2 z = src[k];
       const float2 zc = src[(N - k) & (N - 1)];
@@ -991,6 +1010,10 @@ __global__ __launch_bounds__(256) void stft_generic_kernel(const float* __restri
       s2[1] = make_float2(0.5f * (z.y + zc.y), -0.5f * (z.x - zc.x));
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
+        if (OUT == 5) {
+          esum[q] += sqrtf(s2[q].x * s2[q].x + s2[q].y * s2[q].y);
+          continue;
+        }
         if (q == 1 && !has_b) break;
         const int64_t e = ea + (int64_t)q * bins + k;
         const float2 v = s2[q];
@@ -1005,6 +1028,19 @@ __global__ __launch_bounds__(256) void stft_generic_kernel(const float* __restri
           *reinterpret_cast<float2*>(out + 2 * e) = make_float2(g.x / d, g.y / d);
           *reinterpret_cast<float2*>(tprev + 2 * e) = v;
         }
+      }
+    }
+    if (OUT == 5) {                                         // lanes -> wave (butterfly) -> the waves in order, through the buffer the transform left free
+      float2* red = (src == buf0) ? buf1 : buf0;
+      const float wa = spectral_wave_sum(esum[0]), wb = spectral_wave_sum(esum[1]);
+      if ((tid & 63) == 0) red[tid >> 6] = make_float2(wa, wb);
+      __syncthreads();
+      if (tid == 0) {
+        float2 t = red[0];
+        for (int w = 1; w < (nt >> 6); ++w) t = make_float2(t.x + red[w].x, t.y + red[w].y);
+        float* o = out + b * n_frames + f0;
+        o[0] = t.x;
+        if (has_b) o[1] = t.y;
       }
     }
     __syncthreads();   // the buffers are rewritten by the next pair
@@ -1211,6 +1247,7 @@ int launch_stft1024(const float* x, int64_t x_row_stride, int batch, int64_t n_s
     case 1: MMK_STFT_LAUNCH(1); break;
     case 2: MMK_STFT_LAUNCH(2); break;
     case 3: MMK_STFT_LAUNCH(3); break;
+    case 5: MMK_STFT_LAUNCH(5); break;
     default: MMK_STFT_LAUNCH(4); break;
   }
 #undef MMK_STFT_LAUNCH
@@ -1232,6 +1269,7 @@ int launch_stft_generic(const float* x, int64_t x_row_stride, int batch, int64_t
     case 1: MMK_STFT_LAUNCH(1); break;
     case 2: MMK_STFT_LAUNCH(2); break;
     case 3: MMK_STFT_LAUNCH(3); break;
+    case 5: MMK_STFT_LAUNCH(5); break;
     default: MMK_STFT_LAUNCH(4); break;
   }
 #undef MMK_STFT_LAUNCH
@@ -1290,6 +1328,19 @@ extern "C" int mmk_stft_f32(const float* x, int64_t x_row_stride, int32_t batch,
   if (reflect && center && n_samples <= n_fft / 2)
     return fail(MMK_ERR_INVALID, "stft: reflect padding of %d needs more than %d samples, got %lld", n_fft / 2, n_fft / 2, (long long)n_samples);
   return stft_any(x, x_row_stride, batch, n_samples, n_fft, hop, center, reflect, coordinate, out, nullptr, 0.f, (hipStream_t)stream);
+}
+
+extern "C" int mmk_stft_energy_f32(const float* x, int64_t x_row_stride, int32_t batch, int64_t n_samples, int32_t n_fft, int32_t hop,
+                                   int32_t center, int32_t reflect, float* out, mmk_stream_t stream) {
+  using namespace mmk;
+  if (!x || !out || batch <= 0) return fail(MMK_ERR_INVALID, "stft_energy: bad arguments");
+  if (int rc = check_fft("stft_energy", n_fft, hop)) return rc;
+  if (mmk_stft_n_frames(n_samples, n_fft, hop, center) <= 0)
+    return fail(MMK_ERR_INVALID, "stft_energy: input of %lld samples is shorter than one frame", (long long)n_samples);
+  if (reflect && center && n_samples <= n_fft / 2)
+    return fail(MMK_ERR_INVALID, "stft_energy: reflect padding of %d needs more than %d samples, got %lld", n_fft / 2, n_fft / 2,
+                (long long)n_samples);
+  return stft_any(x, x_row_stride, batch, n_samples, n_fft, hop, center, reflect, 5, out, nullptr, 0.f, (hipStream_t)stream);
 }
 
 extern "C" int64_t mmk_istft_n_samples(int64_t n_frames, int32_t n_fft, int32_t hop) {

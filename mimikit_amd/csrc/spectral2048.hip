@@ -69,6 +69,7 @@ __device__ __forceinline__ cf32 tangle_conj(cf32 a, cf32 b, cf32 w) {
 
 // ---- STFT -----------------------------------------------------------------------------------------------------------------
 // OUT 0: (re, im)   OUT 1: (|S|, angle S)   OUT 2: angle S   OUT 4: |S|  (MagSpec)
+// OUT 5: sum_k |S[k]|, one float per frame in out (batch, n_frames): lane partials in bin order, then a butterfly over the wave
 template <int OUT>
 __global__ __launch_bounds__(64 * kIstftWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void stft2048_kernel(const SpectralTables T, const float* __restrict__ x, int64_t x_row_stride, int64_t n_samples, int hop, int center, int reflect,
@@ -95,17 +96,23 @@ void stft2048_kernel(const SpectralTables T, const float* __restrict__ x, int64_
     for (int r = 0; r < 16; ++r) v[r] = v[r] * win[r];
     fft1024_wave(v, buf, tw, lane);
     const int64_t e0 = fr * kBins2;
+    float esum = 0.f;                                       // OUT 5: this lane's share of the frame's sum
 #pragma unroll
     for (int j = 0; j < 17; ++j) {
       const int k = lane + 64 * j;
       if (k < kBins2) {
         const cf32 s = untangle(buf, k, wk[j]);
         const int64_t e = e0 + k;
+        if (OUT == 5) esum += sqrtf(s.x * s.x + s.y * s.y);
         if (OUT == 0) *reinterpret_cast<cf32*>(out + 2 * e) = s;
         if (OUT == 1) *reinterpret_cast<cf32*>(out + 2 * e) = cf32{sqrtf(s.x * s.x + s.y * s.y), atan2f(s.y, s.x)};
         if (OUT == 2) out[e] = atan2f(s.y, s.x);
         if (OUT == 4) out[e] = sqrtf(s.x * s.x + s.y * s.y);
       }
+    }
+    if (OUT == 5) {
+      esum = spectral_wave_sum(esum);
+      if (lane == 0) out[fr] = esum;
     }
     __builtin_amdgcn_wave_barrier();                        // buf is rewritten by the next frame
   }
@@ -369,6 +376,7 @@ int launch_stft2048(const float* x, int64_t x_row_stride, int batch, int64_t n_s
     case 0: MMK_STFT_LAUNCH(0); break;
     case 1: MMK_STFT_LAUNCH(1); break;
     case 2: MMK_STFT_LAUNCH(2); break;
+    case 5: MMK_STFT_LAUNCH(5); break;
     default: MMK_STFT_LAUNCH(4); break;
   }
 #undef MMK_STFT_LAUNCH

@@ -18,6 +18,13 @@ struct SpectralTables {
 };
 int spectral_tables(hipStream_t stream, SpectralTables* out);     // (istft.hip)
 
+// sum over the 64 lanes of a wave, the same in every lane: a butterfly, one fixed order (the frame-energy epilogues, OUT 5)
+__device__ __forceinline__ float spectral_wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
 __device__ __forceinline__ void load_twiddles(cf32* tw, const cf32* __restrict__ table, int tid, int nthreads) {
   for (int m = tid; m < 1024; m += nthreads) tw[m] = table[m];
 }

@@ -19,6 +19,9 @@ here:
 * ``ISTFT`` / ``GLA`` (:531-573, :609-646), the ``inv`` of STFT / MagSpec at the loop's tail, run on the HIP
   kernels of ``csrc/istft.hip`` / ``spectral2048.hip``; GLA's parity is unpinned (torchaudio is not installed in the
   build container).
+* ``Envelop`` / ``EnvelopBank`` / ``Interpolate`` / ``Derivative`` (:794-1004), the envelope followers the reference's
+  ``Samplifyer`` is built on: frame energies as an epilogue of the STFT kernels (``native.stft_energy``: the spectrogram
+  is never written), interpolation and the lagged-difference stencil in ``csrc/envelope.hip``.  Results stay on the device.
 * float64 tensors are computed in fp32 on the device (the kernels are fp32; the reference computes in the input's
   dtype, so float64 mu-law codes may differ from it for inputs within one fp32 ulp of a bin edge).
 """
@@ -35,7 +38,7 @@ from .item_spec import Frame, Sample, Unit, convert
 
 __all__ = [
     "Continuous", "Discrete", "Functional", "Identity", "Compose", "FileToSignal", "RemoveDC", "Normalize", "Emphasis", "Deemphasis",
-    "MuLawCompress", "MuLawExpand", "STFT", "ISTFT", "MagSpec", "GLA", "Resample",
+    "MuLawCompress", "MuLawExpand", "STFT", "ISTFT", "MagSpec", "GLA", "Resample", "Envelop", "EnvelopBank", "Interpolate", "Derivative",
 ]
 
 N_FFT = 2048
@@ -592,3 +595,203 @@ class GLA(Functional):
     @property
     def inv(self) -> Functional:
         return MagSpec(self.n_fft, self.hop_length, self.center, self.window, self.pad_mode)
+
+
+# ---------------------------------------------------------------------------
+# envelope followers
+# ---------------------------------------------------------------------------
+def get_metadata(x, key: str, default=None):
+    """reference :143-147: the metadata of a numpy dtype, or an attribute of any other array"""
+    if isinstance(x, np.ndarray):
+        return dict(x.dtype.metadata or {}).get(key, default)
+    return getattr(x, key, default)
+
+
+@dtc.dataclass
+class Interpolate(Functional):
+    """reference :867-916.  On a device tensor the last axis is resampled by ``native.interp1d``: ``mode="linear"`` at the positions of
+    ``torch.nn.functional.interpolate(mode="linear")`` (align_corners=False), with the reference's ``.squeeze()`` of the result;
+    ``mode="previous"`` at scipy's positions ``np.linspace(0, n - 1, N)`` - the reference sends every non-linear mode through scipy on
+    the host and moves the result back, here it stays on the device.  Other modes and other axes raise NotImplementedError."""
+    axis: int = -1
+    mode: str = "linear"
+    length: Optional[int] = None
+    factor: Optional[int] = None
+    metadata_key: str = "n_samples"
+
+    @property
+    def unit(self) -> Optional[Unit]:
+        return None
+
+    @property
+    def elem_type(self) -> Optional[EventType]:
+        return Continuous(-float("inf"), float("inf"), 1)
+
+    @property
+    def inv(self) -> Functional:
+        return Identity()
+
+    def _get_target_length(self, x):
+        if self.length is not None:
+            return self.length
+        if self.factor is not None:
+            return self.factor * x.shape[self.axis]
+        n = get_metadata(x, self.metadata_key)
+        if n is None:
+            raise ValueError("No target length provided. One of length or factor must not be None,"
+                             f" or inputs must have the metadata key {self.metadata_key}")
+        return n
+
+    def np_func(self, inputs):
+        from scipy.interpolate import interp1d
+        n_in = inputs.shape[self.axis]
+        f = interp1d(np.arange(n_in), inputs, kind=self.mode, axis=self.axis, assume_sorted=True, copy=False)
+        return f(np.linspace(0, n_in - 1, self._get_target_length(inputs))).astype(inputs.dtype)
+
+    def torch_func(self, inputs):
+        from .. import native
+        if self.mode not in native.INTERP_MODES:
+            raise NotImplementedError(f"Interpolate(mode='{self.mode}') is not on the HIP path: 'linear' or 'previous'")
+        if not isinstance(inputs, torch.Tensor) or inputs.dim() == 0 or self.axis not in (-1, inputs.dim() - 1):
+            raise NotImplementedError(f"Interpolate(axis={self.axis}) is not on the HIP path: the last axis only")
+        n_out = self._get_target_length(inputs)
+        if self.mode == "linear":
+            return native.interp1d(inputs, n_out, "linear", align=False).squeeze()
+        return native.interp1d(inputs, n_out, "previous", align=True)
+
+
+@dtc.dataclass
+class Derivative(Functional):
+    """reference :931-1004: the mean over lags 1 .. max_lag of the centred differences, over the last axis, for any leading dimensions
+    (``native.derivative``; ``max_lag`` up to ``native.DERIV_MAX_LAG``, rows longer than ``max_lag``).  The reference's
+    ``derivative_torch`` takes 1-D input only (its reflection does not broadcast over a batch); rows are taken one by one here, as
+    ``derivative_np_2d`` takes them.
+
+    ``normalize=True`` divides each row by its largest magnitude (``native.row_normalize(p=inf)``).  That is the meaning of the numpy
+    path: the reference's torch path fails for it (``abs(g).max(dim=-1, keepdims=True)`` is a (values, indices) tuple, and a tensor
+    cannot be divided by one).  A row whose derivative is zero everywhere gives zeros where numpy gives NaN (0 / 0), because
+    ``row_normalize`` clamps the divisor at 1e-12."""
+    max_lag: int = 3
+    normalize: bool = False
+
+    @property
+    def unit(self) -> Optional[Unit]:
+        return None
+
+    @property
+    def elem_type(self) -> Optional[EventType]:
+        return Continuous(-float("inf"), float("inf"), 1)
+
+    def np_func(self, inputs):
+        """derivative_np (:931-957) in plain numpy, without numba: float32 throughout (a Python scalar does not widen a float32 array),
+        the lag terms added in lag order; 1-D or 2-D input"""
+        if inputs.ndim not in (1, 2):
+            raise ValueError(f"Expected input array to have 1 or 2 dimensions. Got {inputs.ndim}")
+        y = np.asarray(inputs, dtype=np.float32)
+        n = y.shape[-1]
+        grads = np.zeros(y.shape, dtype=np.float32)
+        for lag in range(1, self.max_lag + 1):
+            y_p = np.zeros(y.shape[:-1] + (n + 2 * lag,), dtype=np.float32)
+            y_p[..., lag:-lag] = y
+            y_p[..., :lag] = y[..., :1] + (y[..., :1] - y[..., 1:1 + lag])[..., ::-1]
+            y_p[..., -lag:] = y[..., -1:] + (y[..., -1:] - y[..., -lag - 1:-1])[..., ::-1]
+            a, b = y_p[..., :n], y_p[..., 2 * lag:]
+            g = (1 / lag) * ((b - y) + (y - a)) / 2
+            grads += g / self.max_lag
+        if self.normalize:
+            grads /= abs(grads).max(axis=-1, keepdims=True)
+        return grads
+
+    def torch_func(self, inputs):
+        from .. import native
+        g = native.derivative(inputs, self.max_lag)
+        if self.normalize:
+            g = native.row_normalize(g, float("inf"))
+        return g
+
+    @property
+    def inv(self) -> Functional:
+        return Identity()
+
+
+@dtc.dataclass
+class Envelop(Functional):
+    """reference :794-830: the sum over the bins of a reflect-padded magnitude spectrogram, interpolated back to the time domain and
+    divided by its maximum.  On the device: ``STFT._fix_length`` of ``MagSpec(n_fft, hop, center=True, pad_mode="reflect")``
+    (alignment "end"), ``native.stft_energy`` (one float per frame; the spectrogram is never written), ``native.interp1d`` at scipy's
+    positions (the reference's torch path IS its numpy path: ``Interpolate(length=T)`` through scipy, T the length before
+    ``_fix_length``) and ``native.row_normalize(p=inf)``.
+
+    Deviations from the reference: the result is a float32 tensor on the input's device, not a CPU tensor; a ``(B, T)`` input is taken
+    row by row (the reference takes ``(T,)`` only); a silent row gives zeros where the reference gives NaN (0 / 0: ``row_normalize``
+    clamps the divisor at 1e-12); ``n_fft`` is a power of two in [64, 4096]; ``window`` is ignored, the periodic Hann window of the
+    torch STFT is always applied."""
+    n_fft: int = N_FFT
+    hop_length: int = HOP_LENGTH
+    normalize: bool = True
+    window: str = "hann"
+    interp_to_time_domain: bool = True
+
+    @property
+    def fft(self) -> MagSpec:
+        return MagSpec(self.n_fft, self.hop_length, center=True, window=self.window, pad_mode="reflect")
+
+    @property
+    def unit(self) -> Optional[Unit]:
+        return Sample(None) if self.interp_to_time_domain else self.fft.unit
+
+    @property
+    def elem_type(self) -> Optional[EventType]:
+        return Continuous(0., 1. if self.normalize else float("inf"), 1)
+
+    def np_func(self, inputs):
+        return self.fft.np_func(inputs)          # (raises: the numpy MagSpec is librosa's)
+
+    def torch_func(self, inputs):
+        from .. import native
+        native.require_device(inputs)
+        if inputs.dim() not in (1, 2):
+            raise ValueError(f"Envelop takes (T,) or (B, T), got shape {tuple(inputs.shape)}")
+        n_samples = inputs.shape[-1]
+        e = native.stft_energy(self.fft.stft._fix_length(inputs), self.n_fft, self.hop_length, True, "reflect")
+        if self.interp_to_time_domain:
+            e = native.interp1d(e, n_samples, "linear", align=True)
+        if self.normalize:
+            e = native.row_normalize(e, float("inf"))
+        return e
+
+    @property
+    def inv(self) -> Functional:
+        return Identity()
+
+
+@dtc.dataclass
+class EnvelopBank(Functional):
+    """reference :833-864: the envelopes of several (n_fft, hop) pairs, always interpolated to the time domain, joined by
+    ``torch.cat(dim=-1)``.  That follows the reference's ``np.hstack``, which for 1-D envelopes is a concatenation along time - a
+    ``(len(n_fft) * T,)`` result - whatever the ``elem_type.size`` of ``len(n_fft)`` suggests."""
+    n_fft: Tuple[int, ...] = (N_FFT,)
+    hop_length: Tuple[int, ...] = (HOP_LENGTH,)
+    normalize: bool = True
+
+    @property
+    def envelops(self):
+        return tuple(Envelop(n_fft, hop, self.normalize, interp_to_time_domain=True) for n_fft, hop in zip(self.n_fft, self.hop_length))
+
+    @property
+    def unit(self) -> Optional[Unit]:
+        return Sample(None)
+
+    @property
+    def elem_type(self) -> Optional[EventType]:
+        return Continuous(0., 1. if self.normalize else float("inf"), len(self.envelops))
+
+    def np_func(self, inputs):
+        return np.hstack([e(inputs) for e in self.envelops])
+
+    def torch_func(self, inputs):
+        return torch.cat([e(inputs) for e in self.envelops], dim=-1)
+
+    @property
+    def inv(self) -> Functional:
+        return Identity()

@@ -166,6 +166,9 @@ _SIGNATURES = {
     "mmk_stft_n_frames": (i64, [i64, i32, i32, i32]),
     "mmk_stft_mag_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, vp, vp]),
     "mmk_stft_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, i32, i32, vp, vp]),
+    "mmk_stft_energy_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, i32, vp, vp]),
+    "mmk_interp1d_f32": (i32, [vp, i64, i32, i64, vp, i64, i64, i32, i32, vp]),
+    "mmk_derivative_f32": (i32, [vp, i64, i32, i64, i32, vp, i64, vp]),
     "mmk_istft_n_samples": (i64, [i64, i32, i32]),
     "mmk_istft_workspace_floats": (C.c_size_t, [i32, i64, i32]),
     "mmk_istft_f32": (i32, [vp, i32, i32, i64, i32, i32, vp, vp, vp]),
@@ -526,6 +529,74 @@ def stft(x: torch.Tensor, n_fft: int, hop: int, center: bool, pad_mode: str, coo
     check(lib().mmk_stft_f32(ptr(x2), x2.stride(0), x2.shape[0], n, n_fft, hop, int(center), int(pad_mode == "reflect"),
                              STFT_COORDINATES[coordinate], ptr(out), stream_ptr(x.device)), "mmk_stft_f32")
     return out.reshape(*lead, *tail)
+
+
+def stft_energy(x: torch.Tensor, n_fft: int, hop: int, center: bool, pad_mode: str) -> torch.Tensor:
+    """x: (..., n_samples) fp32 -> (..., n_frames): the sum over the bins of each frame's STFT magnitudes (the frames of ``stft``), without
+    the spectrogram ever being written"""
+    require_device(x)
+    if pad_mode not in ("constant", "reflect"):
+        raise NotImplementedError(f"HIP STFT covers pad_mode 'constant' and 'reflect', got '{pad_mode}'")
+    if x.dtype != torch.float32:
+        x = x.float()
+    lead = x.shape[:-1]
+    x2 = _rows(x)
+    n = x2.shape[-1]
+    n_frames = lib().mmk_stft_n_frames(n, n_fft, hop, int(center))
+    if n_frames <= 0:
+        raise RuntimeError(f"stft_energy: input of {n} samples is shorter than one frame of {n_fft}")
+    out = torch.empty((x2.shape[0], n_frames), dtype=torch.float32, device=x.device)
+    check(lib().mmk_stft_energy_f32(ptr(x2), x2.stride(0), x2.shape[0], n, n_fft, hop, int(center), int(pad_mode == "reflect"), ptr(out),
+                                    stream_ptr(x.device)), "mmk_stft_energy_f32")
+    return out.reshape(*lead, n_frames)
+
+
+# include/mmk.h: MMK_INTERP_* / MMK_DERIV_* - the modes of mmk_interp1d_f32, the largest max_lag of mmk_derivative_f32 and the samples one
+# workgroup of it owns (csrc/envelope.hip); the tests place their sizes on these
+INTERP_MODES = {"linear": 0, "previous": 1}
+DERIV_MAX_LAG = 64
+DERIV_TILE = 1024
+
+
+def interp1d(x: torch.Tensor, n_out: int, mode: str = "linear", align: bool = True) -> torch.Tensor:
+    """x: (..., n) fp32 -> (..., n_out) along the last dimension.  ``align``: the positions of np.linspace(0, n - 1, n_out) in float64 (scipy's
+    interp1d as Interpolate.np_func calls it); otherwise those of torch.nn.functional.interpolate(mode="linear", align_corners=False).
+    ``mode``: 'linear', or 'previous' (with ``align`` only)"""
+    if mode not in INTERP_MODES:
+        raise NotImplementedError(f"interp1d: mode '{mode}' is not on the HIP path ('linear' or 'previous')")
+    if mode == "previous" and not align:
+        raise ValueError("interp1d: mode 'previous' exists with align=True only")
+    x2 = _float32_rows(x, "interp1d")
+    batch, n = x2.shape
+    n_out = int(n_out)
+    if n < 2 or n_out < 1:
+        raise ValueError(f"interp1d: needs n >= 2 knots and n_out >= 1 points, got {n} and {n_out}")
+    out = torch.empty((batch, n_out), dtype=torch.float32, device=x.device)
+    if batch == 0:
+        return out.reshape(*x.shape[:-1], n_out)
+    check(lib().mmk_interp1d_f32(ptr(x2), x2.stride(0), batch, n, ptr(out), out.stride(0), n_out, INTERP_MODES[mode], int(bool(align)),
+                                 stream_ptr(x.device)), "mmk_interp1d_f32")
+    return out.reshape(*x.shape[:-1], n_out)
+
+
+def derivative(x: torch.Tensor, max_lag: int) -> torch.Tensor:
+    """x: (..., n) fp32 -> the same shape: the mean over lags 1 .. max_lag of the centred differences (x[i+d] - x[i-d]) / 2d along the last
+    dimension, the row continued by odd reflection about its ends (the reference's derivative_torch)"""
+    max_lag = int(max_lag)
+    if max_lag < 1:
+        raise ValueError(f"derivative: max_lag must be at least 1, got {max_lag}")
+    if max_lag > DERIV_MAX_LAG:
+        raise NotImplementedError(f"derivative: max_lag = {max_lag}, the limit is {DERIV_MAX_LAG}")
+    x2 = _float32_rows(x, "derivative")
+    batch, n = x2.shape
+    if n <= max_lag:
+        raise ValueError(f"derivative: the odd reflection of max_lag = {max_lag} needs more than {max_lag} samples, got {n}")
+    out = torch.empty((batch, n), dtype=torch.float32, device=x.device)
+    if batch == 0:
+        return out.reshape(x.shape)
+    check(lib().mmk_derivative_f32(ptr(x2), x2.stride(0), batch, n, max_lag, ptr(out), out.stride(0), stream_ptr(x.device)),
+          "mmk_derivative_f32")
+    return out.reshape(x.shape)
 
 
 def istft(spec: torch.Tensor, n_fft: int, hop: int, polar: bool) -> torch.Tensor:
