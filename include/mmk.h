@@ -160,6 +160,34 @@ int mmk_cosine_cost_f32(const float* x, int64_t x_batch_stride, int64_t x_row_st
 int mmk_dtw_subseq_f32(const float* cost, int32_t batch, int32_t n, int64_t m, int64_t* end_col, float* end_val, float* last_row,
                        mmk_stream_t stream);
 
+/* Scoring generated clips (mimikit/extract/from_neighbors.py:13-19 nearest_neighbor, :44-55 cum_entropy; demos/checkpoint_k_bests.py:36-46).
+ *
+ * mmk_nn_cosine_f32: for `rows` query frames x (x_row_stride floats apart) and m corpus frames y (y_row_stride apart) over k bins, with
+ * rx / ry their inverse norms from mmk_inv_row_norm_f32,
+ *     c[r, j] = clamp(<x_r, y_j> rx[r] ry[j], -1, 1)       (no |.| on load, unlike mmk_cosine_cost_f32)
+ * index[r] (int64) = the FIRST j that maximises c[r, :], cos_best[r] = that value.  A GEMM on v_mfma_f32_32x32x2_f32 whose epilogue is the row
+ * arg-max: the matrix is never written.  The sum over k has one fixed order that does not depend on where a row or a column sits in a tile, so
+ * two identical corpus frames have bit-identical cosines and ties go to the lower index.  rows, m and k need not be multiples of anything and
+ * 4-byte alignment is enough: tails are masked here, the caller pads nothing.  The corpus is cut into spans of MMK_NN_SPAN frames; a workgroup
+ * keeps its running (value, index) pairs in registers across its span, writes one pair per row and span to `workspace`
+ * (mmk_nn_cosine_workspace_bytes(rows, m) = 8 bytes per row and span, never O(rows * m)), and a second small launch joins the spans by
+ * "greater value, then lower index".  No atomics: repeated calls agree bit for bit.  rows < 1, m < 1, k < 1: MMK_ERR_INVALID; a workspace that
+ * is too small: MMK_ERR_WORKSPACE; m >= 2^31 - MMK_NN_SPAN: MMK_ERR_UNSUPPORTED.  NaN in the inputs is not handled.
+ *
+ * mmk_cum_entropy_i64: `batch` rows of t int64 items, row_stride apart.  With p_i(s) = (occurrences of item i in row[0 .. s]) / (s + 1),
+ *     e[s] = -sum_i p_i(s) log p_i(s)  =  log(s + 1) - S(s) / (s + 1),    S(s) = sum_{u <= s} (f(r_u + 1) - f(r_u)),  f(c) = c log c,
+ * r_u = the number of earlier occurrences of row[u] (counted in the kernel; no items x t table).  total[b] = sum_s e[s]; where e is not NULL,
+ * e[b][s] as well (rows e_row_stride apart).  fp64 throughout, the prefix sum in one fixed order, e clamped at 0, each result rounded to fp32
+ * once.  t > MMK_CUM_ENTROPY_MAX_T: MMK_ERR_UNSUPPORTED (one workgroup ranks a row: t^2 / 2 comparisons); batch < 1, t < 1: MMK_ERR_INVALID. */
+#define MMK_NN_SPAN 2048
+#define MMK_CUM_ENTROPY_MAX_T 32768
+size_t mmk_nn_cosine_workspace_bytes(int64_t rows, int64_t m);
+int mmk_nn_cosine_f32(const float* x, int64_t x_row_stride, const float* rx, int64_t rows, const float* y, int64_t y_row_stride,
+                      const float* ry, int64_t m, int32_t k, int64_t* index, float* cos_best, void* workspace, size_t workspace_bytes,
+                      mmk_stream_t stream);
+int mmk_cum_entropy_i64(const int64_t* items, int64_t row_stride, int32_t batch, int64_t t, float* total, float* e, int64_t e_row_stride,
+                        mmk_stream_t stream);
+
 /* STFT.torch_func with coordinate="mag" == MagSpec.torch_func
  * (mimikit/features/functionals.py:507-524, :576-606): periodic-Hann framed
  * real FFT magnitudes.  x: (batch, n_samples) rows `x_row_stride` apart,

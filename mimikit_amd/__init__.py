@@ -16,4 +16,5 @@ from .io_spec import *
 from .networks import *
 from .loops import *
 from .models import *
+from .extract import *
 from .checkpoint import *

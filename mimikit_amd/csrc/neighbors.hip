@@ -1,0 +1,325 @@
+// Scoring generated clips against the training corpus (mimikit/extract/from_neighbors.py:13-19, :44-55 and demos/checkpoint_k_bests.py:36-46):
+// every generated frame's nearest corpus frame by angular distance, and the cumulative entropy of the series of those neighbours.
+//
+//   nn_cosine_kernel      A GEMM whose epilogue is a row arg-max and which never writes the matrix.  c[r, j] = clamp(<x_r, y_j> rx[r] ry[j], -1, 1)
+//                         for `rows` query frames against m corpus frames over k bins.  A workgroup of four waves owns kNnRows = 128 query
+//                         rows and one SPAN of MMK_NN_SPAN corpus frames, which it walks in tiles of kNnCols = 128 frames; a wave owns a
+//                         64 x 64 corner of the tile as 2 x 2 products of v_mfma_f32_32x32x2_f32 with A = corpus frames and B = query rows, so
+//                         that D has the query row on the lane (l & 31) and 16 corpus frames in the registers (frame (q & 3) + 8 (q >> 2) +
+//                         4 (l >> 5) of the product's 32): the arg-max over a tile is taken inside the lane, in rising frame order, and a lane's
+//                         running (value, index) pair of each of its two query rows stays in registers across the whole span.  Both operands go
+//                         through LDS in chunks of kNnKC = 32 bins: rows are loaded dword by dword with consecutive lanes on consecutive bins
+//                         (coalesced whatever the row stride and the base alignment; every load is unconditional at a clamped, valid address
+//                         and the mask picks zero afterwards - nothing is padded by the caller), the next chunk's loads are in flight while
+//                         this chunk's products run.  Lane (r = l & 31, h = l >> 5) reads bins 8 g + 4 h .. + 3 of its row as one 16-byte LDS
+//                         read and feeds MFMA e of group g with bin 8 g + 4 h + e - the same permutation of the bins on both operands and for
+//                         every row and column, so ONE order of the sum over k wherever a frame sits in a tile: two identical corpus frames
+//                         have bit-identical cosines.  The row pitch of 36 floats keeps the 16-lane groups of that read on 64 different banks.
+//                         At the end of the span the two halves of a wave (one shuffle) and the two waves that share query rows (LDS) are
+//                         joined by "greater value, then lower index" and one pair per query row goes to the workspace, span-major.
+//                         Workgroups are numbered so that those in flight together share few query blocks and few spans (kNnGroup query
+//                         blocks by all spans, query block fastest).
+//   nn_merge_kernel       one thread per query row joins the spans' pairs in rising span order (strictly greater wins: the lower index
+//                         stays) and writes index (int64) and cos_best.
+//   cum_entropy_kernel    one workgroup per row of t items.  e[s] = log(s + 1) - S(s) / (s + 1) with S(s) = sum_{u <= s} (f(r_u + 1) - f(r_u)),
+//                         f(c) = c log c, r_u = the number of earlier occurrences of item u in the row: the entropy of the running histogram
+//                         without an items x t table.  The row is walked in chunks of 256 positions: a thread counts its item's earlier
+//                         occurrences (the row is read through the scalar / L1 path: every lane asks for the same address), a Hillis-Steele
+//                         scan in LDS adds the chunk in one fixed order on top of the carry, all in fp64; e is clamped at 0 (and IS 0 while the row has shown
+//                         one item only: the telescoped sum leaves a rounding residue there) and rounded to
+//                         fp32 once, the total is a fixed-order fp64 sum of the clamped values rounded once.
+// No atomics, no workgroup waits for another, no scratch; every sum has one order, so results are the same from run to run.
+// NaN in the inputs is not handled (> drops it silently).
+#include "mmk_common.h"
+
+namespace mmk {
+
+typedef float nn_f32x4 __attribute__((ext_vector_type(4)));
+typedef float nn_f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kNnSpan = MMK_NN_SPAN;
+constexpr int kNnThreads = 256;
+constexpr int kNnRows = 128;      // query rows of a workgroup, 64 per wave pair
+constexpr int kNnCols = 128;      // corpus frames of a tile, 64 per wave pair
+constexpr int kNnKC = 32;         // bins per LDS chunk
+constexpr int kNnPitch = 36;      // floats between LDS rows: 16-byte aligned, and the 16 lanes of one read group fall into 64 different banks
+constexpr int kNnGroup = 16;      // query blocks that are in flight together
+constexpr int kNnLoads = (kNnRows + kNnCols) / 8;      // dwords a thread loads per chunk
+static_assert(kNnSpan % kNnCols == 0, "a span is a whole number of tiles");
+static_assert(kNnRows == 128 && kNnCols == 128 && kNnThreads == 256, "four waves, each a 64 x 64 corner of 2 x 2 MFMA products");
+
+__device__ __forceinline__ bool nn_better(float v, int j, float bv, int bj) { return v > bv || (v == bv && j < bj); }
+
+__global__ __launch_bounds__(kNnThreads, 2) void nn_cosine_kernel(const float* __restrict__ x, int64_t x_row_stride, const float* __restrict__ rx,
+                                                               int64_t rows, const float* __restrict__ y, int64_t y_row_stride,
+                                                               const float* __restrict__ ry, int64_t M, int32_t K, int32_t n_blocks,
+                                                               int32_t n_spans, float* __restrict__ ws_val, int32_t* __restrict__ ws_idx) {
+  __shared__ __attribute__((aligned(16))) float ys[kNnCols * kNnPitch];
+  __shared__ __attribute__((aligned(16))) float xs[kNnRows * kNnPitch];
+  __shared__ float rys[2][kNnCols];
+  __shared__ float red_val[2][kNnRows];
+  __shared__ int red_idx[2][kNnRows];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = tid & 31, row0 = tid >> 5;       // loads: bin `col` of rows row0, row0 + 8, ...
+  const int fr = lane & 31, fh = lane >> 5;         // MFMA fragments: row / column fr, bin half fh
+  const int wm = wave & 1, wn = wave >> 1;          // this wave's corpus half and query half of the tile
+
+  // workgroup -> (query block, span): groups of kNnGroup query blocks by all spans, the query block fastest
+  const int per_group = kNnGroup * n_spans;
+  const int group = blockIdx.x / per_group, within = blockIdx.x % per_group;
+  const int gsize = min(kNnGroup, n_blocks - group * kNnGroup);
+  const int block = group * kNnGroup + within % gsize, span = within / gsize;
+  if (span >= n_spans) return;                      // (the last group is smaller: its surplus workgroups have nothing to do)
+  const int64_t rbase = (int64_t)block * kNnRows;
+  const int64_t jbeg = (int64_t)span * kNnSpan;
+  const int64_t jend = jbeg + kNnSpan < M ? jbeg + kNnSpan : M;
+
+  float rxq[2];
+#pragma unroll
+  for (int tn = 0; tn < 2; ++tn) {
+    const int64_t r = rbase + wn * 64 + tn * 32 + fr;
+    rxq[tn] = r < rows ? rx[r] : 0.f;
+  }
+  const float ninf = __int_as_float(0xff800000);
+  float best[2] = {ninf, ninf};
+  int bidx[2] = {0x7fffffff, 0x7fffffff};
+
+  int parity = 0;
+  for (int64_t jt = jbeg; jt < jend; jt += kNnCols, parity ^= 1) {
+    if (tid < kNnCols) {
+      const int64_t j = jt + tid;
+      rys[parity][tid] = j < jend ? ry[j] : 0.f;
+    }
+    nn_f32x16 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[a][b][q] = 0.f;
+
+    float rg[kNnLoads];
+    auto gload = [&](int k0) {
+      const int k = k0 + col;
+      const int kc = k < K ? k : K - 1;
+#pragma unroll
+      for (int i = 0; i < kNnCols / 8; ++i) {
+        const int64_t j = jt + i * 8 + row0;
+        rg[i] = y[(j < M ? j : M - 1) * y_row_stride + kc];
+      }
+#pragma unroll
+      for (int i = 0; i < kNnRows / 8; ++i) {
+        const int64_t r = rbase + i * 8 + row0;
+        rg[kNnCols / 8 + i] = x[(r < rows ? r : rows - 1) * x_row_stride + kc];
+      }
+    };
+    gload(0);
+    for (int k0 = 0; k0 < K; k0 += kNnKC) {
+      const bool kin = k0 + col < K;
+#pragma unroll
+      for (int i = 0; i < kNnCols / 8; ++i) ys[(i * 8 + row0) * kNnPitch + col] = (kin && jt + i * 8 + row0 < jend) ? rg[i] : 0.f;
+#pragma unroll
+      for (int i = 0; i < kNnRows / 8; ++i)
+        xs[(i * 8 + row0) * kNnPitch + col] = (kin && rbase + i * 8 + row0 < rows) ? rg[kNnCols / 8 + i] : 0.f;
+      __syncthreads();
+      if (k0 + kNnKC < K) gload(k0 + kNnKC);
+#pragma unroll
+      for (int g = 0; g < kNnKC; g += 8) {
+        nn_f32x4 av[2], bv[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          av[t] = *reinterpret_cast<const nn_f32x4*>(&ys[(wm * 64 + t * 32 + fr) * kNnPitch + g + 4 * fh]);
+          bv[t] = *reinterpret_cast<const nn_f32x4*>(&xs[(wn * 64 + t * 32 + fr) * kNnPitch + g + 4 * fh]);
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[tm][e], bv[tn][e], acc[tm][tn], 0, 0, 0);
+      }
+      __syncthreads();
+    }
+
+    // the tile's arg-max, inside the lane and in rising frame order: strictly greater wins, so the lowest index stays
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int jl = wm * 64 + tm * 32 + (q & 3) + 8 * (q >> 2) + 4 * fh;
+        const int64_t j = jt + jl;
+        const float ryj = rys[parity][jl];
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn) {
+          const float c = fminf(fmaxf(acc[tm][tn][q] * rxq[tn] * ryj, -1.f), 1.f);
+          if (j < jend && c > best[tn]) {
+            best[tn] = c;
+            bidx[tn] = (int)j;
+          }
+        }
+      }
+  }
+
+  // join the two halves of the wave, then the two waves that share these query rows
+#pragma unroll
+  for (int tn = 0; tn < 2; ++tn) {
+    const float ov = __shfl_xor(best[tn], 32);
+    const int oj = __shfl_xor(bidx[tn], 32);
+    if (nn_better(ov, oj, best[tn], bidx[tn])) {
+      best[tn] = ov;
+      bidx[tn] = oj;
+    }
+    if (fh == 0) {
+      red_val[wm][wn * 64 + tn * 32 + fr] = best[tn];
+      red_idx[wm][wn * 64 + tn * 32 + fr] = bidx[tn];
+    }
+  }
+  __syncthreads();
+  if (tid < kNnRows && rbase + tid < rows) {
+    float v = red_val[0][tid];
+    int j = red_idx[0][tid];
+    if (nn_better(red_val[1][tid], red_idx[1][tid], v, j)) {
+      v = red_val[1][tid];
+      j = red_idx[1][tid];
+    }
+    ws_val[(int64_t)span * rows + rbase + tid] = v;
+    ws_idx[(int64_t)span * rows + rbase + tid] = j;
+  }
+}
+
+__global__ __launch_bounds__(256) void nn_merge_kernel(const float* __restrict__ ws_val, const int32_t* __restrict__ ws_idx, int64_t rows,
+                                                       int32_t n_spans, int64_t* __restrict__ index, float* __restrict__ cos_best) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  float v = ws_val[r];
+  int j = ws_idx[r];
+  for (int s = 1; s < n_spans; ++s) {
+    const float sv = ws_val[(int64_t)s * rows + r];
+    if (sv > v) {
+      v = sv;
+      j = ws_idx[(int64_t)s * rows + r];
+    }
+  }
+  index[r] = j;
+  cos_best[r] = v;
+}
+
+// ---- cumulative entropy --------------------------------------------------------------------------------------------------------------
+constexpr int kCeThreads = 256;
+
+__device__ __forceinline__ double ce_f(double c) { return c > 0.0 ? c * log(c) : 0.0; }
+
+__global__ __launch_bounds__(kCeThreads) void cum_entropy_kernel(const int64_t* __restrict__ items, int64_t row_stride, int32_t T,
+                                                                 float* __restrict__ total, float* __restrict__ e, int64_t e_row_stride) {
+  __shared__ double scan[2][kCeThreads];
+  const int tid = threadIdx.x;
+  const int64_t* row = items + (int64_t)blockIdx.x * row_stride;
+  float* er = e ? e + (int64_t)blockIdx.x * e_row_stride : nullptr;
+  double carry = 0.0;       // S at the end of the chunk before this one
+  double mine = 0.0;        // this thread's e values, added in chunk order
+  for (int s0 = 0; s0 < T; s0 += kCeThreads) {
+    const int s = s0 + tid;
+    const bool in = s < T;
+    const int64_t it = row[in ? s : T - 1];
+    // earlier occurrences: u runs over the same positions for every lane (a uniform address), each lane keeps those before its own
+    const int last = min(s0 + kCeThreads, T);
+    int r = 0;
+    for (int u = 0; u < last; ++u) r += (row[u] == it && u < s) ? 1 : 0;
+    double d = in ? ce_f((double)(r + 1)) - ce_f((double)r) : 0.0;
+    // inclusive scan of the chunk, Hillis-Steele: position p adds position p - 2^i at step i - one order for every chunk
+    int cur = 0;
+    scan[0][tid] = d;
+    __syncthreads();
+#pragma unroll
+    for (int off = 1; off < kCeThreads; off <<= 1) {
+      const double v = scan[cur][tid] + (tid >= off ? scan[cur][tid - off] : 0.0);
+      scan[cur ^ 1][tid] = v;
+      cur ^= 1;
+      __syncthreads();
+    }
+    const double S = carry + scan[cur][tid];
+    const double next = carry + scan[cur][kCeThreads - 1];
+    __syncthreads();        // (the next chunk writes scan[0] again)
+    carry = next;
+    if (in) {
+      const double n1 = (double)(s + 1);
+      double h = log(n1) - S / n1;
+      h = (h > 0.0 && r != s) ? h : 0.0;      // r == s: every item so far is this one - a histogram of one bin, exactly 0
+      mine += h;
+      if (er) er[s] = (float)h;
+    }
+  }
+  // the threads' sums, a binary tree in LDS: one fixed order
+  scan[0][tid] = mine;
+  __syncthreads();
+#pragma unroll
+  for (int off = kCeThreads / 2; off >= 1; off >>= 1) {
+    if (tid < off) scan[0][tid] += scan[0][tid + off];
+    __syncthreads();
+  }
+  if (tid == 0) total[blockIdx.x] = (float)scan[0][0];
+}
+
+static int nn_spans(int64_t m) { return (int)((m + kNnSpan - 1) / kNnSpan); }
+
+}  // namespace mmk
+
+extern "C" size_t mmk_nn_cosine_workspace_bytes(int64_t rows, int64_t m) {
+  using namespace mmk;
+  if (rows < 1 || m < 1) return 0;
+  return (size_t)rows * (size_t)nn_spans(m) * (sizeof(float) + sizeof(int32_t));
+}
+
+extern "C" int mmk_nn_cosine_f32(const float* x, int64_t x_row_stride, const float* rx, int64_t rows, const float* y, int64_t y_row_stride,
+                                 const float* ry, int64_t m, int32_t k, int64_t* index, float* cos_best, void* workspace,
+                                 size_t workspace_bytes, mmk_stream_t stream) {
+  using namespace mmk;
+  if (rows < 1) return fail(MMK_ERR_INVALID, "nn_cosine: rows = %lld < 1 (query frames)", (long long)rows);
+  if (m < 1) return fail(MMK_ERR_INVALID, "nn_cosine: m = %lld < 1 (corpus frames)", (long long)m);
+  if (k < 1) return fail(MMK_ERR_INVALID, "nn_cosine: k = %d < 1 (bins)", k);
+  if (m > 0x7fffffffLL - kNnSpan)
+    return fail(MMK_ERR_UNSUPPORTED, "nn_cosine: m = %lld corpus frames: indices are kept in 32 bits across the spans", (long long)m);
+  if (!x || !y || !rx || !ry || !index || !cos_best || !workspace || x_row_stride < 0 || y_row_stride < 0)
+    return fail(MMK_ERR_INVALID, "nn_cosine: bad arguments (null pointer or negative stride %lld / %lld)", (long long)x_row_stride,
+                (long long)y_row_stride);
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(rx) | reinterpret_cast<uintptr_t>(ry) |
+       reinterpret_cast<uintptr_t>(cos_best) | reinterpret_cast<uintptr_t>(workspace)) & 3)
+    return fail(MMK_ERR_INVALID, "nn_cosine: x, y, rx, ry, cos_best and the workspace must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(index) & 7) return fail(MMK_ERR_INVALID, "nn_cosine: index must be 8-byte aligned");
+  if (workspace_bytes < mmk_nn_cosine_workspace_bytes(rows, m))
+    return fail(MMK_ERR_WORKSPACE, "nn_cosine: the workspace has %zu bytes, %zu are needed", workspace_bytes,
+                mmk_nn_cosine_workspace_bytes(rows, m));
+  const int n_spans = nn_spans(m);
+  const int64_t n_blocks = (rows + kNnRows - 1) / kNnRows;
+  const int64_t groups = (n_blocks + kNnGroup - 1) / kNnGroup;
+  const int64_t grid = groups * kNnGroup * n_spans;
+  if (grid > 0x7fffffffLL)
+    return fail(MMK_ERR_UNSUPPORTED, "nn_cosine: %lld rows against %lld frames are more than one launch takes", (long long)rows, (long long)m);
+  float* ws_val = static_cast<float*>(workspace);
+  int32_t* ws_idx = reinterpret_cast<int32_t*>(ws_val + rows * n_spans);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(nn_cosine_kernel, dim3((unsigned)grid), dim3(kNnThreads), 0, st, x, x_row_stride, rx, rows, y, y_row_stride, ry, m, k,
+                     (int32_t)n_blocks, n_spans, ws_val, ws_idx);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, ws_val, ws_idx, rows, n_spans, index, cos_best);
+  MMK_HIP(hipGetLastError());
+  return MMK_OK;
+}
+
+extern "C" int mmk_cum_entropy_i64(const int64_t* items, int64_t row_stride, int32_t batch, int64_t t, float* total, float* e,
+                                   int64_t e_row_stride, mmk_stream_t stream) {
+  using namespace mmk;
+  if (batch < 1) return fail(MMK_ERR_INVALID, "cum_entropy: batch = %d < 1", batch);
+  if (t < 1) return fail(MMK_ERR_INVALID, "cum_entropy: t = %lld < 1 (items per row)", (long long)t);
+  if (t > MMK_CUM_ENTROPY_MAX_T)
+    return fail(MMK_ERR_UNSUPPORTED, "cum_entropy: t = %lld items per row, more than the %d (MMK_CUM_ENTROPY_MAX_T) one workgroup ranks",
+                (long long)t, MMK_CUM_ENTROPY_MAX_T);
+  if (!items || !total || row_stride < 0 || e_row_stride < 0 || (reinterpret_cast<uintptr_t>(items) & 7) ||
+      ((reinterpret_cast<uintptr_t>(total) | reinterpret_cast<uintptr_t>(e)) & 3))
+    return fail(MMK_ERR_INVALID, "cum_entropy: bad arguments (null or misaligned pointer, negative stride %lld / %lld)", (long long)row_stride,
+                (long long)e_row_stride);
+  hipLaunchKernelGGL(cum_entropy_kernel, dim3((unsigned)batch), dim3(kCeThreads), 0, (hipStream_t)stream, items, row_stride, (int32_t)t, total,
+                     e, e_row_stride);
+  MMK_HIP(hipGetLastError());
+  return MMK_OK;
+}

@@ -163,6 +163,9 @@ _SIGNATURES = {
     "mmk_inv_row_norm_f32": (i32, [vp, i64, i64, i32, i64, i32, vp, vp]),
     "mmk_cosine_cost_f32": (i32, [vp, i64, i64, vp, i32, i32, vp, i64, vp, i64, i32, vp, vp]),
     "mmk_dtw_subseq_f32": (i32, [vp, i32, i32, i64, vp, vp, vp, vp]),
+    "mmk_nn_cosine_workspace_bytes": (C.c_size_t, [i64, i64]),
+    "mmk_nn_cosine_f32": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, i32, vp, vp, vp, C.c_size_t, vp]),
+    "mmk_cum_entropy_i64": (i32, [vp, i64, i32, i64, vp, vp, i64, vp]),
     "mmk_stft_n_frames": (i64, [i64, i32, i32, i32]),
     "mmk_stft_mag_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, vp, vp]),
     "mmk_stft_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, i32, i32, vp, vp]),
@@ -474,6 +477,61 @@ def nnn_end_columns(prompt_frames: torch.Tensor, corpus: torch.Tensor, corpus_in
     (NearestNextNeighbor.predict_start_frame of the reference = end + 1)"""
     cost = cosine_cost(prompt_frames, corpus, corpus_inv_norm)
     return dtw_subseq(cost, prompt_frames.shape[1])
+
+
+# include/mmk.h: MMK_NN_SPAN / MMK_CUM_ENTROPY_MAX_T - corpus frames of one workgroup of the arg-max kernel and the longest row the entropy
+# kernel ranks (csrc/neighbors.hip); the tests place their sizes on these
+NN_SPAN = 2048
+CUM_ENTROPY_MAX_T = 32768
+
+
+def nn_cosine(x: torch.Tensor, corpus: torch.Tensor, corpus_inv_norm: torch.Tensor):
+    """x (rows, k), corpus (M, k), corpus_inv_norm (M,) = inv_row_norm(corpus) -> (index (rows,) int64, cos_best (rows,) fp32): per row of x the
+    first corpus frame of the largest cosine similarity and that cosine, clamped to [-1, 1].  The (rows, M) matrix is never formed: the
+    workspace is 8 bytes per row and span of NN_SPAN corpus frames"""
+    x = _nnn_frames(x, 2, "nn_cosine")
+    y = _nnn_frames(corpus, 2, "nn_cosine")
+    require_device(corpus_inv_norm)
+    rows, k = x.shape
+    m = y.shape[0]
+    if y.shape[1] != k:
+        raise ValueError(f"nn_cosine: the queries have {k} bins, the corpus {y.shape[1]}")
+    if corpus_inv_norm.shape != (m,) or corpus_inv_norm.dtype != torch.float32 or not corpus_inv_norm.is_contiguous():
+        raise ValueError(f"nn_cosine: corpus_inv_norm must be {m} contiguous float32 values, got {tuple(corpus_inv_norm.shape)} {corpus_inv_norm.dtype}")
+    if min(rows, m, k) < 1:
+        raise ValueError(f"nn_cosine: empty input (rows={rows}, M={m}, bins={k})")
+    rx = inv_row_norm(x)
+    index = torch.empty((rows,), dtype=torch.int64, device=x.device)
+    best = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    n_work = lib().mmk_nn_cosine_workspace_bytes(rows, m)
+    work = torch.empty((n_work // 4,), dtype=torch.float32, device=x.device)
+    check(lib().mmk_nn_cosine_f32(ptr(x), x.stride(0), ptr(rx), rows, ptr(y), y.stride(0), ptr(corpus_inv_norm), m, k, ptr(index), ptr(best),
+                                  ptr(work), n_work, stream_ptr(x.device)), "mmk_nn_cosine_f32")
+    return index, best
+
+
+def cum_entropy(items: torch.Tensor, per_step: bool = False):
+    """items (B, T) int64 -> total (B,) fp32, the sum over s of the entropy e[s] of the histogram of items[b, :s + 1]; with ``per_step`` also
+    e (B, T) fp32"""
+    if not isinstance(items, torch.Tensor):
+        raise TypeError(f"cum_entropy: expected a torch.Tensor, got {type(items)}")
+    if items.dtype != torch.int64:
+        raise TypeError(f"cum_entropy takes int64 items (indices of neighbours), got {items.dtype}")
+    if items.dim() != 2:
+        raise ValueError(f"cum_entropy: expected (B, T) items, got shape {tuple(items.shape)}")
+    batch, t = items.shape
+    if batch < 1 or t < 1:
+        raise ValueError(f"cum_entropy: empty input {tuple(items.shape)}")
+    if t > CUM_ENTROPY_MAX_T:
+        raise NotImplementedError(f"cum_entropy: T = {t} items per row, the limit is {CUM_ENTROPY_MAX_T}")
+    require_device(items)
+    if items.stride(1) != 1 and t > 1:
+        items = items.contiguous()
+    total = torch.empty((batch,), dtype=torch.float32, device=items.device)
+    e = torch.empty((batch, t), dtype=torch.float32, device=items.device) if per_step else None
+    check(lib().mmk_cum_entropy_i64(ptr(items), items.stride(0), batch, t, ptr(total), ptr(e), t if per_step else 0, stream_ptr(items.device)),
+          "mmk_cum_entropy_i64")
+    return (total, e) if per_step else total
 
 
 def _rows(x: torch.Tensor) -> torch.Tensor:
