@@ -1,5 +1,6 @@
 // Host-side helpers shared by the network plans: state_dict binding, workspace
-// carving, packed-linear descriptors and the hipGraph step cache.
+// carving, packed-linear descriptors, the MLP head, the entry points the plans
+// have in common and the hipGraph step cache.
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -148,6 +149,117 @@ struct PackedLinear {
     a.bias = bias;
   }
 };
+
+// One output module as every network ends in it (networks/mlp.py:42-53, modules/io.py:205): Linear, act, [Linear, act] * n_hidden, Linear
+// with an optional learned-temperature column, then the categorical sampler.  The two hidden-row buffers its layers ping-pong through belong
+// to the plan: a plan's heads share them.
+struct MlpHead {
+  std::vector<PackedLinear> layers;
+  int in_dim = 0, hidden = 0, n_classes = 0, learn_temp = 0;
+  float min_temp = 0.f;
+  float* logits = nullptr;      // (rows, logits_ld): the last Linear's outputs, before the temperature division
+  int logits_ld = 0;
+
+  int n_out() const { return n_classes + (learn_temp ? 1 : 0); }
+
+  // `who` names the head in the message, `bad` is the code a refused geometry returns; logits_ld = n_out() rounded up to `ld_align`
+  int set_geometry(const char* who, int bad, int in_dim_, int hidden_, int n_hidden, int n_classes_, int learn_temp_, float min_temp_, int ld_align) {
+    if (hidden_ < 1 || n_hidden < 0 || n_hidden > MMK_MAX_MLP_HIDDEN)
+      return fail(bad, "%s: bad MLP head geometry (hidden %d, %d extra blocks)", who, hidden_, n_hidden);
+    in_dim = in_dim_; hidden = hidden_; n_classes = n_classes_; learn_temp = learn_temp_; min_temp = min_temp_;
+    layers.assign((size_t)n_hidden + 2, PackedLinear());
+    layers.front().set_geometry(hidden, {in_dim});
+    for (int i = 1; i <= n_hidden; ++i) layers[i].set_geometry(hidden, {hidden});
+    layers.back().set_geometry(n_out(), {hidden});
+    logits_ld = (int)round_up(n_out(), ld_align);
+    return MMK_OK;
+  }
+  void carve(Carver& c, int64_t rows) {
+    for (auto& m : layers) m.carve(c, true);
+    logits = c.take<float>(rows * logits_ld);
+  }
+  // binds <prefix>{0, 2, 4, ..}.weight / .bias; a missing or mis-sized tensor is recorded in the binder
+  int pack(Binder& b, const std::string& prefix, hipStream_t st) {
+    for (size_t i = 0; i < layers.size(); ++i) {
+      PackedLinear& m = layers[i];
+      const std::string kb = prefix + std::to_string(2 * i) + ".";
+      const float* w = b.need(kb + "weight", (int64_t)m.N * m.segK[0]);
+      const float* bb = b.need(kb + "bias", m.N);
+      if (w) MMK_TRY(pack_rect(m.Wp, m.k_chunks, 0, 1, m.N, 0, m.segK[0], w, m.segK[0], 1, st));
+      if (bb) MMK_TRY(pack_bias(m.bias, 0, 1, m.N, bb, 0, st));
+    }
+    return MMK_OK;
+  }
+  // x -> logits through the plan's hid[0] / hid[1]; `linear(w, x, x_ld, out, out_ld, act)` launches one layer the plan's way
+  template <typename Linear>
+  int run(const float* x, int64_t x_ld, float* const* hid, int act, Linear&& linear) const {
+    for (size_t i = 0; i < layers.size(); ++i) {
+      const bool last = i + 1 == layers.size();
+      float* o = last ? logits : hid[i & 1];
+      const int64_t o_ld = last ? logits_ld : hidden;
+      MMK_TRY(linear(layers[i], x, x_ld, o, o_ld, last ? (int)ACT_NONE : act));
+      x = o;
+      x_ld = o_ld;
+    }
+    return MMK_OK;
+  }
+  // the sampler's view of the head; rows, temperature, uniforms, destination and tau are the plan's
+  void fill(SampleArgs& s) const {
+    s.logits = logits; s.ld = logits_ld; s.n_classes = n_classes; s.has_temp_col = learn_temp; s.min_temp = min_temp;
+  }
+  // the n_out() columns of the last step's rows -> out (device memory)
+  int copy_logits(float* out, int64_t out_ld, int64_t rows, hipStream_t st) const {
+    MMK_HIP(hipMemcpy2DAsync(out, (size_t)out_ld * sizeof(float), logits, (size_t)logits_ld * sizeof(float), (size_t)n_out() * sizeof(float),
+                             (size_t)rows, hipMemcpyDeviceToDevice, st));
+    return MMK_OK;
+  }
+};
+
+// ---- the entry points every plan type has in the same words (Plan: cfg, tune, binder, committed, layout(Carver&)) ----------------------
+template <typename Plan, typename Config>
+int plan_create(const char* who, const Config* cfg, Plan** out, int (*derive)(Plan*)) {
+  if (!cfg || !out) return fail(MMK_ERR_INVALID, "%s: null argument", who);
+  Plan* p = new Plan();
+  p->cfg = *cfg;
+  p->tune.parse(cfg->tuning, sizeof(cfg->tuning));
+  const int rc = derive(p);
+  if (rc != MMK_OK) {
+    delete p;
+    return rc;
+  }
+  *out = p;
+  return MMK_OK;
+}
+
+template <typename Plan>
+int plan_bind(const char* who, Plan* p, const char* key, const float* dev_ptr, int64_t numel) {
+  if (!p || !key || !dev_ptr) return fail(MMK_ERR_INVALID, "%s: null argument", who);
+  p->binder.bind(key, dev_ptr, numel);
+  p->committed = false;
+  return MMK_OK;
+}
+
+// layout() only writes pointers: the sizing pass runs it on a copy
+template <typename Plan>
+size_t plan_workspace_bytes(const Plan* p) {
+  if (!p) return 0;
+  Plan tmp = *p;
+  Carver c(nullptr);
+  tmp.layout(c);
+  return c.used();
+}
+
+// a commit's first half: the argument checks, then the plan laid out over the caller's workspace; *used: the bytes it takes
+template <typename Plan>
+int plan_place(const char* who, Plan* p, void* workspace, size_t workspace_bytes, size_t* used) {
+  if (!p || !workspace) return fail(MMK_ERR_INVALID, "%s: null argument", who);
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) return fail(MMK_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
+  Carver carve(workspace);
+  p->layout(carve);
+  *used = carve.used();
+  if (*used > workspace_bytes) return fail(MMK_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, *used);
+  return MMK_OK;
+}
 
 // Cache of one instantiated hipGraph holding `steps` consecutive steps.
 struct GraphCache {

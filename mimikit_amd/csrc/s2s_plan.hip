@@ -165,9 +165,8 @@ struct mmk_s2s_plan {
   float* gemm_partial = nullptr;                 // split-K partial sums of the GEMM launches that would not fill the chip
   int gemm_ksplit = 0;                           // > 0: every GEMM launch splits K this many ways (tuning MMK_GEMM_KSPLIT: a parity-test mode)
   static constexpr int64_t kPartialFloats = 512 * 64 * 64;   // k_split x workgroups <= 512 tiles of 64 x 64
-  std::vector<PackedLinear> mlp;
-  float *hid[2] = {nullptr, nullptr}, *logits = nullptr;
-  int logits_ld = 0;
+  MlpHead head;
+  float* hid[2] = {nullptr, nullptr};
 
   void layout(Carver& cv) {
     for (auto& l : enc) for (int d = 0; d < 2; ++d) { l.ih[d].carve(cv, true); l.hh[d].carve(cv, false); }
@@ -177,10 +176,9 @@ struct mmk_s2s_plan {
     dec_fc.carve(cv, true);
     const int64_t rows = (int64_t)Bmax * hop;
     if (cfg.head_kind == 1) {
-      for (auto& m : mlp) m.carve(cv, true);
+      head.carve(cv, rows);
       hid[0] = cv.take<float>(rows * cfg.mlp_hidden);
       hid[1] = cv.take<float>(rows * cfg.mlp_hidden);
-      logits = cv.take<float>(rows * logits_ld);
     } else {
       out_lin.carve(cv, true);
     }
@@ -212,6 +210,8 @@ struct mmk_s2s_plan {
 
 static int derive(mmk_s2s_plan* p) {
   const mmk_s2s_config& c = p->cfg;
+  if (c.mlp_act < ACT_NONE || c.mlp_act > ACT_COS) return fail(MMK_ERR_INVALID, "s2s_plan_create: mlp_act %d outside MMK_ACT_*", c.mlp_act);
+  if (const char* ks = p->tune.get("MMK_GEMM_KSPLIT")) p->gemm_ksplit = atoi(ks);
   if (c.in_dim < 1 || c.out_dim < 1 || c.model_dim < 1 || c.hop < 1 || c.max_batch < 1) return fail(MMK_ERR_INVALID, "s2s: bad dimensions");
   if (c.enc_n_lstm < 1 || c.enc_n_lstm > 8 || c.dec_n_lstm < 1 || c.dec_n_lstm > 8)
     return fail(MMK_ERR_UNSUPPORTED, "s2s: 1 .. 8 bi-LSTM layers per side, got %d + %d", c.enc_n_lstm, c.dec_n_lstm);
@@ -223,8 +223,8 @@ static int derive(mmk_s2s_plan* p) {
   if (c.in_classes < 0 || (c.in_classes > 0 && c.in_dim != c.model_dim))
     return fail(MMK_ERR_INVALID, "s2s: an embedding input has in_dim == model_dim (got %d, %d)", c.in_dim, c.model_dim);
   if (c.head_kind < 0 || c.head_kind > 1) return fail(MMK_ERR_INVALID, "s2s: head_kind %d unknown", c.head_kind);
-  if (c.head_kind == 1 && (c.mlp_hidden < 1 || c.mlp_n_hidden < 0 || c.mlp_n_hidden > MMK_MAX_MLP_HIDDEN))
-    return fail(MMK_ERR_INVALID, "s2s: bad MLP head geometry (hidden %d, %d extra blocks)", c.mlp_hidden, c.mlp_n_hidden);
+  if (c.head_kind == 1)   // Linear, Mish, [Linear, Mish] * n, Linear   (networks/mlp.py:42-53)
+    MMK_TRY(p->head.set_geometry("s2s", MMK_ERR_INVALID, c.model_dim, c.mlp_hidden, c.mlp_n_hidden, c.out_dim, c.learn_temp, c.min_temp, 4));
   if ((c.head_kind == 1) != (c.in_classes > 0))
     return fail(MMK_ERR_UNSUPPORTED, "s2s: class indices in and out go together (in_classes %d, head_kind %d): the loop feeds outputs back", c.in_classes, c.head_kind);
   p->D = c.model_dim;
@@ -248,20 +248,6 @@ static int derive(mmk_s2s_plan* p) {
   if (c.enc_downsampling == 4) p->enc_fc.set_geometry(p->D / p->hop, {p->D});
   p->dec_fc.set_geometry(p->hop * p->D, {p->D});
   p->out_lin.set_geometry(c.out_dim, {p->D});
-  p->mlp.clear();
-  if (c.head_kind == 1) {   // Linear, Mish, [Linear, Mish] * n, Linear   (networks/mlp.py:42-53)
-    PackedLinear first, last;
-    first.set_geometry(c.mlp_hidden, {p->D});
-    p->mlp.push_back(first);
-    for (int i = 0; i < c.mlp_n_hidden; ++i) {
-      PackedLinear h;
-      h.set_geometry(c.mlp_hidden, {c.mlp_hidden});
-      p->mlp.push_back(h);
-    }
-    last.set_geometry(c.out_dim + (c.learn_temp ? 1 : 0), {c.mlp_hidden});
-    p->mlp.push_back(last);
-    p->logits_ld = (int)round_up(c.out_dim + (c.learn_temp ? 1 : 0), 4);
-  }
   const char* fenv = p->tune.get("MMK_S2S_FUSED");
   p->fused_lstm = !(fenv && fenv[0] == '0') && lstm_step_supported(p->D);
   {
@@ -276,38 +262,15 @@ static int derive(mmk_s2s_plan* p) {
   return MMK_OK;
 }
 
-extern "C" int mmk_s2s_plan_create(const mmk_s2s_config* cfg, mmk_s2s_plan** out) {
-  if (!cfg || !out) return fail(MMK_ERR_INVALID, "s2s_plan_create: null argument");
-  if (cfg->mlp_act < ACT_NONE || cfg->mlp_act > ACT_COS) return fail(MMK_ERR_INVALID, "s2s_plan_create: mlp_act %d outside MMK_ACT_*", cfg->mlp_act);
-  mmk_s2s_plan* p = new mmk_s2s_plan();
-  p->cfg = *cfg;
-  p->tune.parse(cfg->tuning, sizeof(cfg->tuning));
-  if (const char* ks = p->tune.get("MMK_GEMM_KSPLIT")) p->gemm_ksplit = atoi(ks);
-  int rc = derive(p);
-  if (rc != MMK_OK) {
-    delete p;
-    return rc;
-  }
-  *out = p;
-  return MMK_OK;
-}
+extern "C" int mmk_s2s_plan_create(const mmk_s2s_config* cfg, mmk_s2s_plan** out) { return plan_create("s2s_plan_create", cfg, out, derive); }
 
 extern "C" void mmk_s2s_plan_destroy(mmk_s2s_plan* p) { delete p; }
 
 extern "C" int mmk_s2s_plan_bind(mmk_s2s_plan* p, const char* key, const float* dev_ptr, int64_t numel) {
-  if (!p || !key || !dev_ptr) return fail(MMK_ERR_INVALID, "s2s_plan_bind: null argument");
-  p->binder.bind(key, dev_ptr, numel);
-  p->committed = false;
-  return MMK_OK;
+  return plan_bind("s2s_plan_bind", p, key, dev_ptr, numel);
 }
 
-extern "C" size_t mmk_s2s_workspace_bytes(const mmk_s2s_plan* p) {
-  if (!p) return 0;
-  mmk_s2s_plan tmp = *p;
-  Carver c(nullptr);
-  tmp.layout(c);
-  return c.used();
-}
+extern "C" size_t mmk_s2s_workspace_bytes(const mmk_s2s_plan* p) { return plan_workspace_bytes(p); }
 
 static int pack_lstm(mmk_s2s_plan* p, BiLstm& l, const std::string& base, int in_dim, hipStream_t st) {
   Binder& b = p->binder;
@@ -339,15 +302,11 @@ __global__ void s2s_compose_kernel(const float* __restrict__ A, const float* __r
 }
 
 extern "C" int mmk_s2s_commit(mmk_s2s_plan* p, void* workspace, size_t workspace_bytes, mmk_stream_t stream) {
-  if (!p || !workspace) return fail(MMK_ERR_INVALID, "s2s_commit: null argument");
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) return fail(MMK_ERR_WORKSPACE, "s2s_commit: workspace must be 256-byte aligned");
+  size_t used = 0;
+  MMK_TRY(plan_place("s2s_commit", p, workspace, workspace_bytes, &used));
   hipStream_t st = (hipStream_t)stream;
   const mmk_s2s_config& c = p->cfg;
-  Carver carve(workspace);
-  p->layout(carve);
-  if (carve.used() > workspace_bytes)
-    return fail(MMK_ERR_WORKSPACE, "s2s_commit: workspace of %zu bytes, %zu needed", workspace_bytes, carve.used());
-  MMK_HIP(hipMemsetAsync(workspace, 0, carve.used(), st));
+  MMK_HIP(hipMemsetAsync(workspace, 0, used, st));
   if (p->seq_lstm) {
     for (int k = 0; k < 2; ++k) MMK_HIP(hipMemsetAsync(p->xch[k], 0xFF, lstm_seq_xch_floats(p->D, p->Bmax, p->hop) * sizeof(float), st));
     p->xch_cur = 0;
@@ -381,15 +340,7 @@ extern "C" int mmk_s2s_commit(mmk_s2s_plan* p, void* workspace, size_t workspace
     if (const float* bb = b.need("dec.fc.fc.bias", (int64_t)p->hop * D)) MMK_TRY(pack_bias(p->dec_fc.bias, 0, 1, p->hop * D, bb, 0, st));
   }
   if (c.head_kind == 1) {
-    const std::string hb = "output_module.heads.0.estimator.0.fc.";
-    for (size_t i = 0; i < p->mlp.size(); ++i) {
-      PackedLinear& m = p->mlp[i];
-      const std::string kb = hb + std::to_string(2 * i) + ".";
-      const float* w = b.need(kb + "weight", (int64_t)m.N * m.segK[0]);
-      const float* bb = b.need(kb + "bias", m.N);
-      if (w) MMK_TRY(pack_rect(m.Wp, m.k_chunks, 0, 1, m.N, 0, m.segK[0], w, m.segK[0], 1, st));
-      if (bb) MMK_TRY(pack_bias(m.bias, 0, 1, m.N, bb, 0, st));
-    }
+    MMK_TRY(p->head.pack(b, "output_module.heads.0.estimator.0.fc.", st));
   } else {
     if (const float* w = b.need("output_module.heads.0.0.weight", (int64_t)c.out_dim * D))
       MMK_TRY(pack_rect(p->out_lin.Wp, p->out_lin.k_chunks, 0, 1, c.out_dim, 0, D, w, D, 1, st));
@@ -624,19 +575,12 @@ static int s2s_step(mmk_s2s_plan* p, int M, const S2SIo& io, int n_out, hipStrea
   }
   if (c.head_kind == 1) {
     // MLP head over all hop positions of all clips, then one wave per row: learned-temperature division + argmax
-    const float* hx = xl;
-    int64_t hx_ld = D;
-    for (size_t i = 0; i < p->mlp.size(); ++i) {
-      const bool last = i + 1 == p->mlp.size();
-      float* o = last ? p->logits : p->hid[i & 1];
-      const int64_t o_ld = last ? p->logits_ld : c.mlp_hidden;
-      MMK_TRY(plain_linear(p->mlp[i], hx, hx_ld, rows, o, o_ld, last ? (int)ACT_NONE : c.mlp_act, st, p->gemm_partial, p->gemm_ksplit));   // MLPIO.activation (modules/io.py:205: Mish by default)
-      hx = o;
-      hx_ld = o_ld;
-    }
+    MMK_TRY(p->head.run(xl, D, p->hid, c.mlp_act, [&](const PackedLinear& w, const float* hx, int64_t hx_ld, float* o, int64_t o_ld, int act) {
+      return plain_linear(w, hx, hx_ld, rows, o, o_ld, act, st, p->gemm_partial, p->gemm_ksplit);
+    }));
     SampleArgs sa = {};
-    sa.logits = p->logits; sa.ld = p->logits_ld; sa.rows = rows; sa.n_classes = c.out_dim; sa.has_temp_col = c.learn_temp;
-    sa.min_temp = c.min_temp;
+    p->head.fill(sa);
+    sa.rows = rows;
     sa.out = io.yi; sa.out_row_stride = yfs; sa.group = hop; sa.kept = n_out; sa.group_stride = ybs;
     return launch_sample(sa, st);
   }
@@ -684,11 +628,8 @@ extern "C" int mmk_s2s_last_logits(mmk_s2s_plan* p, int32_t batch, float* out, i
   if (!p || !out) return fail(MMK_ERR_INVALID, "s2s_last_logits: null argument");
   if (!p->committed || p->cfg.head_kind != 1) return fail(MMK_ERR_STATE, "s2s_last_logits: only for a committed plan with the MLP head");
   if (batch < 1 || batch > p->Bmax) return fail(MMK_ERR_INVALID, "s2s_last_logits: batch %d outside [1, %d]", batch, p->Bmax);
-  const int n = p->cfg.out_dim + (p->cfg.learn_temp ? 1 : 0);
-  if (out_ld < n) return fail(MMK_ERR_INVALID, "s2s_last_logits: out_ld %lld < %d", (long long)out_ld, n);
-  MMK_HIP(hipMemcpy2DAsync(out, (size_t)out_ld * sizeof(float), p->logits, (size_t)p->logits_ld * sizeof(float), (size_t)n * sizeof(float),
-                           (size_t)batch * p->hop, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return MMK_OK;
+  if (out_ld < p->head.n_out()) return fail(MMK_ERR_INVALID, "s2s_last_logits: out_ld %lld < %d", (long long)out_ld, p->head.n_out());
+  return p->head.copy_logits(out, out_ld, (int64_t)batch * p->hop, (hipStream_t)stream);
 }
 
 extern "C" int mmk_s2s_generate(mmk_s2s_plan* p, int32_t batch, float* frames, int64_t batch_stride, int64_t frame_stride,

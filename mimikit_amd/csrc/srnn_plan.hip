@@ -34,15 +34,6 @@ struct SrnnDeep {
   float *h = nullptr, *c = nullptr;
 };
 
-// an output module beyond the first (one per target, sample_rnn_v2.py:181-182): an MLPIO + sampler of its own geometry on the same hidden vector
-struct SrnnHead {
-  std::vector<PackedLinear> mlp;
-  int q = 0, hidden = 0, learn_temp = 0;
-  float min_temp = 0.f;
-  float* logits = nullptr;
-  int logits_ld = 0;
-};
-
 struct SrnnTier {
   int fs = 0, up = 0;
   std::vector<SrnnDeep> deep;
@@ -70,15 +61,13 @@ struct mmk_srnn_plan {
   int n_rnn_tiers = 0, H = 0, G = 0, Bmax = 0;
   std::vector<SrnnTier> tiers;
   PackedLinear bottom;
-  std::vector<PackedLinear> mlp;
+  std::vector<MlpHead> heads;                   // one output module per target on the same hidden vector (sample_rnn_v2.py:181-182), target 0 first
   // more than one input / target (include/mmk.h): one launch per operation; the ZipReduceVariables weights are folded into the packed
   // input products at commit (zip_w: the weights of tier i at [4 i, 4 i + 4), zip_tmp: a scaled copy on its way into the packed matrix)
   int n_in = 1, n_tgt = 1, in_class[MMK_MAX_STREAMS] = {0, 0, 0, 0};
   bool multi = false;
-  std::vector<SrnnHead> xheads;                 // targets 1 ..
   float *zip_w = nullptr, *zip_tmp = nullptr;
-  float *xbuf = nullptr, *gi = nullptr, *gh = nullptr, *xbot = nullptr, *hid[2] = {nullptr, nullptr}, *logits = nullptr;
-  int logits_ld = 0;
+  float *xbuf = nullptr, *gi = nullptr, *gh = nullptr, *xbot = nullptr, *hid[2] = {nullptr, nullptr};
   int64_t* tau = nullptr;
   hipStream_t cap_stream = nullptr;
   GraphCache gc;
@@ -135,12 +124,9 @@ struct mmk_srnn_plan {
       }
     }
     bottom.carve(c, true);
-    for (auto& m : mlp) m.carve(c, true);
-    int hid_w = cfg.mlp_hidden, fs_max = 1;
-    for (auto& h : xheads) {
-      for (auto& m : h.mlp) m.carve(c, true);
-      h.logits_ld = (int)round_up(h.q + (h.learn_temp ? 1 : 0), 4);
-      h.logits = c.take<float>((int64_t)Bmax * h.logits_ld);
+    int hid_w = 0, fs_max = 1;
+    for (auto& h : heads) {
+      h.carve(c, Bmax);
       hid_w = h.hidden > hid_w ? h.hidden : hid_w;
     }
     for (int i = 0; i < cfg.n_tiers; ++i) fs_max = cfg.frame_size[i] > fs_max ? cfg.frame_size[i] : fs_max;
@@ -152,8 +138,6 @@ struct mmk_srnn_plan {
     xbot = c.take<float>((int64_t)Bmax * H);
     hid[0] = c.take<float>((int64_t)Bmax * hid_w);
     hid[1] = c.take<float>((int64_t)Bmax * hid_w);
-    logits_ld = (int)round_up(cfg.q_levels + (cfg.learn_temp ? 1 : 0), 4);
-    logits = c.take<float>((int64_t)Bmax * logits_ld);
     tau = c.take<int64_t>(32);
     cls_gran = c.take<unsigned long long>((int64_t)Bmax * 256);
     {
@@ -194,10 +178,12 @@ struct mmk_srnn_plan {
 
 static int derive(mmk_srnn_plan* p) {
   const mmk_srnn_config& c = p->cfg;
+  if (c.mlp_act < ACT_NONE || c.mlp_act > ACT_COS) return fail(MMK_ERR_INVALID, "srnn_plan_create: mlp_act %d outside MMK_ACT_*", c.mlp_act);
   if (c.n_tiers < 2 || c.n_tiers > MMK_MAX_TIERS) return fail(MMK_ERR_INVALID, "srnn: n_tiers=%d outside [2, %d]", c.n_tiers, MMK_MAX_TIERS);
   if (c.hidden_dim < 1 || c.max_batch < 1 || c.q_levels < 2) return fail(MMK_ERR_INVALID, "srnn: bad hidden_dim / max_batch / q_levels");
   if (c.rnn_kind < 0 || c.rnn_kind > 2) return fail(MMK_ERR_INVALID, "srnn: rnn_kind %d unknown", c.rnn_kind);
-  if (c.mlp_hidden < 1 || c.mlp_n_hidden < 0 || c.mlp_n_hidden > MMK_MAX_MLP_HIDDEN) return fail(MMK_ERR_INVALID, "srnn: bad MLP head geometry");
+  p->heads.assign(1, MlpHead());
+  MMK_TRY(p->heads[0].set_geometry("srnn", MMK_ERR_INVALID, c.hidden_dim, c.mlp_hidden, c.mlp_n_hidden, c.q_levels, c.learn_temp, c.min_temp, 4));
   p->H = c.hidden_dim;
   p->Bmax = c.max_batch;
   p->G = c.rnn_kind == 0 ? 4 : (c.rnn_kind == 1 ? 3 : 1);
@@ -244,37 +230,14 @@ static int derive(mmk_srnn_plan* p) {
   }
   if (c.frame_size[c.n_tiers - 1] < 1) return fail(MMK_ERR_INVALID, "srnn: bad bottom frame size");
   p->bottom.set_geometry(p->H, std::vector<int>(p->n_in, c.frame_size[c.n_tiers - 1]));
-  p->mlp.clear();
-  PackedLinear first;
-  first.set_geometry(c.mlp_hidden, {p->H});
-  p->mlp.push_back(first);
-  for (int i = 0; i < c.mlp_n_hidden; ++i) {
-    PackedLinear h;
-    h.set_geometry(c.mlp_hidden, {c.mlp_hidden});
-    p->mlp.push_back(h);
-  }
-  PackedLinear last;
-  last.set_geometry(c.q_levels + (c.learn_temp ? 1 : 0), {c.mlp_hidden});
-  p->mlp.push_back(last);
-  p->xheads.clear();
-  for (int k = 1; k < p->n_tgt; ++k) {
-    SrnnHead h;
-    h.q = c.x_q_levels[k]; h.hidden = c.x_mlp_hidden[k]; h.learn_temp = c.x_learn_temp[k]; h.min_temp = c.x_min_temp[k];
-    const int nh = c.x_mlp_n_hidden[k];
-    if (h.q < 2 || h.hidden < 1 || nh < 0 || nh > MMK_MAX_MLP_HIDDEN) return fail(MMK_ERR_INVALID, "srnn: bad MLP head geometry of target %d", k);
-    if (h.q > p->in_class[k]) return fail(MMK_ERR_INVALID, "srnn: target %d draws from %d classes, input %d holds %d", k, h.q, k, p->in_class[k]);
-    PackedLinear f0;
-    f0.set_geometry(h.hidden, {p->H});
-    h.mlp.push_back(f0);
-    for (int i = 0; i < nh; ++i) {
-      PackedLinear m;
-      m.set_geometry(h.hidden, {h.hidden});
-      h.mlp.push_back(m);
-    }
-    PackedLinear out;
-    out.set_geometry(h.q + (h.learn_temp ? 1 : 0), {h.hidden});
-    h.mlp.push_back(out);
-    p->xheads.push_back(h);
+  for (int k = 1; k < p->n_tgt; ++k) {      // target 0 has its geometry in the scalar fields (above), the others in the x_* arrays
+    const std::string who = "srnn target " + std::to_string(k);
+    MlpHead h;
+    if (c.x_q_levels[k] < 2) return fail(MMK_ERR_INVALID, "%s: %d classes", who.c_str(), c.x_q_levels[k]);
+    MMK_TRY(h.set_geometry(who.c_str(), MMK_ERR_INVALID, p->H, c.x_mlp_hidden[k], c.x_mlp_n_hidden[k], c.x_q_levels[k], c.x_learn_temp[k], c.x_min_temp[k], 4));
+    if (h.n_classes > p->in_class[k])
+      return fail(MMK_ERR_INVALID, "srnn: target %d draws from %d classes, input %d holds %d", k, h.n_classes, k, p->in_class[k]);
+    p->heads.push_back(h);
   }
   const char* fenv = p->tune.get("MMK_SRNN_FUSED");
   p->fused_bottom = !(fenv && fenv[0] == '0') && c.mlp_n_hidden == 0 && c.mlp_act == ACT_MISH &&      // (the fused and resident kernels have Mish built in)
@@ -287,20 +250,7 @@ static int derive(mmk_srnn_plan* p) {
   return MMK_OK;
 }
 
-extern "C" int mmk_srnn_plan_create(const mmk_srnn_config* cfg, mmk_srnn_plan** out) {
-  if (!cfg || !out) return fail(MMK_ERR_INVALID, "srnn_plan_create: null argument");
-  if (cfg->mlp_act < ACT_NONE || cfg->mlp_act > ACT_COS) return fail(MMK_ERR_INVALID, "srnn_plan_create: mlp_act %d outside MMK_ACT_*", cfg->mlp_act);
-  mmk_srnn_plan* p = new mmk_srnn_plan();
-  p->cfg = *cfg;
-  p->tune.parse(cfg->tuning, sizeof(cfg->tuning));
-  int rc = derive(p);
-  if (rc != MMK_OK) {
-    delete p;
-    return rc;
-  }
-  *out = p;
-  return MMK_OK;
-}
+extern "C" int mmk_srnn_plan_create(const mmk_srnn_config* cfg, mmk_srnn_plan** out) { return plan_create("srnn_plan_create", cfg, out, derive); }
 
 extern "C" void mmk_srnn_plan_destroy(mmk_srnn_plan* p) {
   if (!p) return;
@@ -310,21 +260,10 @@ extern "C" void mmk_srnn_plan_destroy(mmk_srnn_plan* p) {
 }
 
 extern "C" int mmk_srnn_plan_bind(mmk_srnn_plan* p, const char* key, const float* dev_ptr, int64_t numel) {
-  if (!p || !key || !dev_ptr) return fail(MMK_ERR_INVALID, "srnn_plan_bind: null argument");
-  p->binder.bind(key, dev_ptr, numel);
-  p->committed = false;
-  return MMK_OK;
+  return plan_bind("srnn_plan_bind", p, key, dev_ptr, numel);
 }
 
-extern "C" size_t mmk_srnn_workspace_bytes(const mmk_srnn_plan* p) {
-  if (!p) return 0;
-  mmk_srnn_plan tmp = *p;
-  tmp.gc = GraphCache();
-  tmp.cap_stream = nullptr;
-  Carver c(nullptr);
-  tmp.layout(c);
-  return c.used();
-}
+extern "C" size_t mmk_srnn_workspace_bytes(const mmk_srnn_plan* p) { return plan_workspace_bytes(p); }
 
 // ZipReduceVariables' weights (modules/io.py:296-302, :305-308): sum -> 1, mean -> 1 / M, static_mix -> softmax of the parameter
 __global__ void srnn_zip_weights_kernel(const float* __restrict__ param, int M, int mode, float* __restrict__ out) {
@@ -508,17 +447,13 @@ static int pack_zipped(mmk_srnn_plan* p, int tier, const std::string& mod, const
 }
 
 extern "C" int mmk_srnn_commit(mmk_srnn_plan* p, void* workspace, size_t workspace_bytes, mmk_stream_t stream) {
-  if (!p || !workspace) return fail(MMK_ERR_INVALID, "srnn_commit: null argument");
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) return fail(MMK_ERR_WORKSPACE, "srnn_commit: workspace must be 256-byte aligned");
+  size_t used = 0;
+  MMK_TRY(plan_place("srnn_commit", p, workspace, workspace_bytes, &used));
   hipStream_t st = (hipStream_t)stream;
   const mmk_srnn_config& c = p->cfg;
-  Carver carve(workspace);
-  p->layout(carve);
-  if (carve.used() > workspace_bytes)
-    return fail(MMK_ERR_WORKSPACE, "srnn_commit: workspace of %zu bytes, %zu needed", workspace_bytes, carve.used());
   MMK_HIP(hipStreamSynchronize(st));   // replays of the cached graph may still be queued: wait before destroying it
   p->gc.reset();
-  MMK_HIP(hipMemsetAsync(workspace, 0, carve.used(), st));
+  MMK_HIP(hipMemsetAsync(workspace, 0, used, st));
   Binder& b = p->binder;
   b.clear_missing();
   const int H = p->H, G = p->G;
@@ -617,40 +552,29 @@ extern "C" int mmk_srnn_commit(mmk_srnn_plan* p, void* workspace, size_t workspa
     if (w) MMK_HIP(hipMemcpyAsync(p->wb_raw, w, (size_t)H * fsl * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (bb) MMK_HIP(hipMemcpyAsync(p->bb_raw, bb, (size_t)H * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
-  for (size_t i = 0; i < p->mlp.size(); ++i) {
-    PackedLinear& m = p->mlp[i];
-    const std::string kb = "output_modules.0.estimator.0.fc." + std::to_string(2 * i) + ".";
-    const float* w = b.need(kb + "weight", (int64_t)m.N * m.segK[0]);
-    const float* bb = b.need(kb + "bias", m.N);
-    if (w) MMK_TRY(pack_rect(m.Wp, m.k_chunks, 0, 1, m.N, 0, m.segK[0], w, m.segK[0], 1, st));
-    if (bb) MMK_TRY(pack_bias(m.bias, 0, 1, m.N, bb, 0, st));
-    if (p->mlp.size() == 2) p->mlp_raw[i] = w;
-    if (p->mlp.size() == 2 && i == 0 && w && bb && p->fused_bottom) {   // (wb_raw / bb_raw were copied above, on this stream)
+  for (size_t k = 0; k < p->heads.size(); ++k) MMK_TRY(p->heads[k].pack(b, "output_modules." + std::to_string(k) + ".estimator.0.fc.", st));
+  if (p->heads[0].layers.size() == 2) {
+    // target 0's two-layer head is what the fused and resident kernels know: its matrices as bound, and its first layer composed with the
+    // bottom tier's framed convolution (wb_raw / bb_raw were copied above, on this stream)
+    const int Hm = p->heads[0].hidden;
+    const float* w = p->mlp_raw[0] = b.need("output_modules.0.estimator.0.fc.0.weight", (int64_t)Hm * H);
+    const float* bb = b.need("output_modules.0.estimator.0.fc.0.bias", Hm);
+    p->mlp_raw[1] = b.need("output_modules.0.estimator.0.fc.2.weight", (int64_t)p->heads[0].n_out() * Hm);
+    if (w && bb && p->fused_bottom) {
       const int fsl = c.frame_size[c.n_tiers - 1];
-      hipLaunchKernelGGL(srnn_compose_bottom_kernel, dim3(((fsl + 1) * m.N + 255) / 256), dim3(256), 0, st, w, bb, p->wb_raw, p->bb_raw, m.N,
+      hipLaunchKernelGGL(srnn_compose_bottom_kernel, dim3(((fsl + 1) * Hm + 255) / 256), dim3(256), 0, st, w, bb, p->wb_raw, p->bb_raw, Hm,
                          H, fsl, p->a_comp, p->b_comp);
       MMK_HIP(hipGetLastError());
       p->bottom_composed = true;
       if (p->fused_gru && last_wu && last_bu && links_built == p->n_rnn_tiers) {
         // resident mode: the head's first layer through the last recurrent tier's up-sampler (srnn_resident.hip)
-        const int S = p->tiers.back().up, Hm = m.N;
+        const int S = p->tiers.back().up;
         hipLaunchKernelGGL(srnn_compose_cp_kernel, dim3((unsigned)(((int64_t)S * Hm * H + 255) / 256)), dim3(256), 0, st, w, last_wu, Hm, H, S,
                            p->cp_rpb, p->cp_tiles, p->cp0, p->cp_wp);
         hipLaunchKernelGGL(srnn_compose_bcs_kernel, dim3((S * Hm + 255) / 256), dim3(256), 0, st, w, bb, last_bu, p->bb_raw, Hm, H, S, p->bcs);
         MMK_HIP(hipGetLastError());
         p->resident_ready = true;
       }
-    }
-  }
-  for (size_t k = 0; k < p->xheads.size(); ++k) {
-    SrnnHead& h = p->xheads[k];
-    for (size_t i = 0; i < h.mlp.size(); ++i) {
-      PackedLinear& m = h.mlp[i];
-      const std::string kb = "output_modules." + std::to_string(k + 1) + ".estimator.0.fc." + std::to_string(2 * i) + ".";
-      const float* w = b.need(kb + "weight", (int64_t)m.N * m.segK[0]);
-      const float* bb = b.need(kb + "bias", m.N);
-      if (w) MMK_TRY(pack_rect(m.Wp, m.k_chunks, 0, 1, m.N, 0, m.segK[0], w, m.segK[0], 1, st));
-      if (bb) MMK_TRY(pack_bias(m.bias, 0, 1, m.N, bb, 0, st));
     }
   }
   if (!b.missing().empty()) return fail(MMK_ERR_KEY, "srnn_commit: state_dict tensor %s", b.missing().c_str());
@@ -672,14 +596,15 @@ static SrnnBottomArgs bottom_args(mmk_srnn_plan* p, const SrnnCall& call, int64_
   a.tau_ptr = p->tau; a.tau_off = tau_off;
   a.idx = const_cast<int64_t*>(call.idx); a.idx_rs = call.idx_rs;
   a.wb = p->wb_raw; a.bb = p->bb_raw; a.upper = up.out;
-  a.fc0_wp = p->mlp[0].Wp; a.fc0_bias = p->mlp[0].bias; a.fc2_wp = p->mlp[1].Wp; a.fc2_bias = p->mlp[1].bias;
+  const MlpHead& h0 = p->heads[0];
+  a.fc0_wp = h0.layers[0].Wp; a.fc0_bias = h0.layers[0].bias; a.fc2_wp = h0.layers[1].Wp; a.fc2_bias = h0.layers[1].bias;
   a.fc0_raw = p->mlp_raw[0]; a.fc2_raw = p->mlp_raw[1];
   {
     const char* cenv = p->tune.get("MMK_SRNN_COMPOSED");
     if (p->bottom_composed && !(cenv && cenv[0] == '0')) { a.a_comp = p->a_comp; a.b_comp = p->b_comp; }
   }
   a.temperature = call.temperature; a.uniforms = call.uniforms; a.uni_ld = call.uni_ld; a.uni_off = call.uni_off;
-  a.logits_out = p->logits; a.logits_ld = p->logits_ld;
+  a.logits_out = h0.logits; a.logits_ld = h0.logits_ld;
   {
     const char* senv = diag_only("MMK_SRNN_STAMPS");
     a.stamps = (senv && senv[0] == '1') ? reinterpret_cast<unsigned long long*>(p->tau + 8) : nullptr;
@@ -866,31 +791,20 @@ static int emit_step(mmk_srnn_plan* p, const SrnnCall& call, int64_t tau_off, in
   }
   // one output module per target on the same hidden vector (:259); output k goes into input k (loops/generate.py:213-218)
   for (int k = 0; k < p->n_tgt; ++k) {
-    const std::vector<PackedLinear>& mlp = k == 0 ? p->mlp : p->xheads[k - 1].mlp;
-    float* logits = k == 0 ? p->logits : p->xheads[k - 1].logits;
-    const int logits_ld = k == 0 ? p->logits_ld : p->xheads[k - 1].logits_ld;
-    const int hidden = k == 0 ? c.mlp_hidden : p->xheads[k - 1].hidden;
-    const float* x = p->xbot;
-    int x_ld = H;
-    for (size_t i = 0; i < mlp.size(); ++i) {
-      const bool last = (i + 1 == mlp.size());
+    const MlpHead& h = p->heads[k];
+    MMK_TRY(h.run(p->xbot, H, p->hid, c.mlp_act, [&](const PackedLinear& w, const float* x, int64_t x_ld, float* o, int64_t o_ld, int act) {
       LinearArgs a = {};
-      mlp[i].fill(a);
+      w.fill(a);
       a.seg[0].x = addr_static(x); a.seg[0].ld = x_ld;
       a.M = M; a.tau_ptr = p->tau; a.tau_off = tau_off;
-      a.epilogue = EPI_STORE; a.act = last ? (int)ACT_NONE : c.mlp_act;      // MLPIO.activation (modules/io.py:205)
-      float* o = last ? logits : p->hid[i & 1];
+      a.epilogue = EPI_STORE; a.act = act;
       a.out = addr_static(o);
-      a.out_ld = last ? logits_ld : hidden;
-      MMK_TRY(launch_linear(a, st));
-      x = o;
-      x_ld = (int)a.out_ld;
-    }
+      a.out_ld = o_ld;
+      return launch_linear(a, st);
+    }));
     SampleArgs s = {};
-    s.logits = logits; s.ld = logits_ld; s.rows = M;
-    s.n_classes = k == 0 ? c.q_levels : p->xheads[k - 1].q;
-    s.has_temp_col = k == 0 ? c.learn_temp : p->xheads[k - 1].learn_temp;
-    s.min_temp = k == 0 ? c.min_temp : p->xheads[k - 1].min_temp;
+    h.fill(s);
+    s.rows = M;
     s.temperature = call.temperature;
     s.uniforms = call.uniforms ? call.uniforms + (int64_t)k * M * call.uni_ld : nullptr;       // (n_targets, batch, n_steps)
     s.uniform_ld = call.uni_ld; s.uni_off = call.uni_off;
@@ -1036,9 +950,9 @@ static int run_resident(mmk_srnn_plan* p, const SrnnCall& call, int64_t t_begin,
   a.fsb = c.frame_size[c.n_tiers - 1]; a.S = p->tiers.back().up;
   a.idx = const_cast<int64_t*>(call.idx); a.idx_rs = call.idx_rs;
   a.cp0 = p->cp0; a.a_comp = p->a_comp; a.bcs = p->bcs;
-  a.fc2_raw = p->mlp_raw[1]; a.fc2_bias = p->mlp[1].bias;
+  a.fc2_raw = p->mlp_raw[1]; a.fc2_bias = p->heads[0].layers[1].bias;
   a.temperature = call.temperature; a.uniforms = call.uniforms; a.uni_ld = call.uni_ld; a.uni_off = call.uni_off;
-  a.logits_out = p->logits; a.logits_ld = p->logits_ld;
+  a.logits_out = p->heads[0].logits; a.logits_ld = p->heads[0].logits_ld;
   a.cls_gran = p->cls_gran;
   a.err = reinterpret_cast<int*>(p->tau + 4);
   {
@@ -1212,10 +1126,7 @@ extern "C" int mmk_srnn_last_logits(mmk_srnn_plan* p, int32_t batch, float* out,
     fprintf(stderr, "[mmk stamps] srnn gru kernel, workgroup 0, us per launch over %llu launches: loads=%.2f wait for the bottom kernel=%.2f x=%.2f mfma=%.2f cell=%.2f grid barrier=%.2f up-sampler=%.2f\n",
             st[7], st[0] * 1e-2 / ng, st[4] * 1e-2 / ng, st[1] * 1e-2 / ng, st[2] * 1e-2 / ng, st[3] * 1e-2 / ng, st[5] * 1e-2 / ng, st[6] * 1e-2 / ng);
   }
-  const int n = p->cfg.q_levels + (p->cfg.learn_temp ? 1 : 0);
-  MMK_HIP(hipMemcpy2DAsync(out, ld * sizeof(float), p->logits, p->logits_ld * sizeof(float), n * sizeof(float), batch,
-                           hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return MMK_OK;
+  return p->heads[0].copy_logits(out, ld, batch, (hipStream_t)stream);
 }
 
 extern "C" int mmk_srnn_last_logits_of(mmk_srnn_plan* p, int32_t target, int32_t batch, float* out, int64_t ld, mmk_stream_t stream) {
@@ -1223,9 +1134,5 @@ extern "C" int mmk_srnn_last_logits_of(mmk_srnn_plan* p, int32_t target, int32_t
   if (target == 0) return mmk_srnn_last_logits(p, batch, out, ld, stream);
   if (!p->committed) return fail(MMK_ERR_STATE, "srnn_last_logits_of: plan not committed");
   if (target < 0 || target >= p->n_tgt) return fail(MMK_ERR_INVALID, "srnn_last_logits_of: target %d of %d", target, p->n_tgt);
-  const SrnnHead& h = p->xheads[target - 1];
-  const int n = h.q + (h.learn_temp ? 1 : 0);
-  MMK_HIP(hipMemcpy2DAsync(out, ld * sizeof(float), h.logits, h.logits_ld * sizeof(float), n * sizeof(float), batch,
-                           hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return MMK_OK;
+  return p->heads[target].copy_logits(out, ld, batch, (hipStream_t)stream);
 }

@@ -31,12 +31,12 @@ struct TrLayer {
 struct TrState {
   std::vector<TrLayer> layers;
   PackedLinear kv_ca, in_lin, out_lin;
-  std::vector<PackedLinear> mlp;
+  MlpHead head;
   float *embed = nullptr, *pe = nullptr, *fn_w = nullptr, *fn_b = nullptr;
   float *x0 = nullptr, *x = nullptr, *qkv = nullptr, *att = nullptr, *tmp = nullptr, *qc = nullptr, *hff = nullptr, *kvc = nullptr;
   float* frames = nullptr;
   float *xl = nullptr, *att_l = nullptr, *tmp_l = nullptr, *qc_l = nullptr, *hff_l = nullptr, *xf = nullptr;
-  float *hid[2] = {nullptr, nullptr}, *logits = nullptr;
+  float* hid[2] = {nullptr, nullptr};
   float* partial = nullptr;
   int64_t partial_floats = 0;
   int64_t* tau = nullptr;
@@ -47,7 +47,7 @@ struct mmk_tr_plan {
   mmk_tr_config cfg;
   Binder binder;
   bool committed = false;
-  int D = 0, H = 0, hd = 0, FF = 0, L = 0, rf = 0, Bmax = 0, in_pad = 0, logits_ld = 0;
+  int D = 0, H = 0, hd = 0, FF = 0, L = 0, rf = 0, Bmax = 0, in_pad = 0;
   TrState s;
   hipStream_t cap_stream = nullptr;
   GraphCache gc;
@@ -72,10 +72,9 @@ static void tr_layout(const mmk_tr_plan* p, TrState& s, Carver& cv) {
   s.pe = cv.take<float>((int64_t)p->rf * D);
   if (c.final_norm) { s.fn_w = cv.take<float>(D); s.fn_b = cv.take<float>(D); }
   if (c.head_kind == 0) {
-    for (auto& m : s.mlp) m.carve(cv, true);
+    s.head.carve(cv, B);
     s.hid[0] = cv.take<float>(B * c.mlp_hidden);
     s.hid[1] = cv.take<float>(B * c.mlp_hidden);
-    s.logits = cv.take<float>(B * p->logits_ld);
   } else {
     s.out_lin.carve(cv, true);
   }
@@ -128,8 +127,7 @@ static int derive(mmk_tr_plan* p) {
   }
   if (c.head_kind == 0) {
     if (c.out_dim < 1 || c.out_dim > 1024) return fail(MMK_ERR_UNSUPPORTED, "tr: out_dim %d classes (the sampler takes 1 .. 1024)", c.out_dim);
-    if (c.mlp_hidden < 1 || c.mlp_n_hidden < 0 || c.mlp_n_hidden > MMK_MAX_MLP_HIDDEN)
-      return fail(MMK_ERR_UNSUPPORTED, "tr: MLP head geometry (mlp_hidden %d, mlp_n_hidden %d)", c.mlp_hidden, c.mlp_n_hidden);
+    MMK_TRY(p->s.head.set_geometry("tr", MMK_ERR_UNSUPPORTED, c.model_dim, c.mlp_hidden, c.mlp_n_hidden, c.out_dim, c.learn_temp, c.min_temp, 1));
     if (c.mlp_act < 0 || c.mlp_act > MMK_ACT_COS) return fail(MMK_ERR_INVALID, "tr: mlp_act %d", c.mlp_act);
     if (c.in_kind != 0) return fail(MMK_ERR_UNSUPPORTED, "tr: class indices in and out go together (the loop feeds the outputs back)");
   } else if (c.head_kind == 1) {
@@ -142,7 +140,6 @@ static int derive(mmk_tr_plan* p) {
   p->D = c.model_dim; p->H = c.n_heads; p->hd = hd; p->FF = c.feedforward_dim; p->L = c.num_layers; p->rf = c.rf;
   p->Bmax = c.max_batch;
   p->in_pad = c.in_kind == 1 ? (int)round_up(c.in_dim, 16) : 0;
-  p->logits_ld = c.head_kind == 0 ? c.out_dim + (c.learn_temp ? 1 : 0) : 0;
   const int D = p->D;
   p->s.layers.assign(p->L, TrLayer());
   for (auto& l : p->s.layers) {
@@ -155,38 +152,16 @@ static int derive(mmk_tr_plan* p) {
   }
   p->s.kv_ca.set_geometry(2 * D * p->L, {D});
   if (c.in_kind == 1) p->s.in_lin.set_geometry(D, {c.in_dim});
-  if (c.head_kind == 0) {
-    p->s.mlp.assign(c.mlp_n_hidden + 2, PackedLinear());
-    p->s.mlp[0].set_geometry(c.mlp_hidden, {D});
-    for (int i = 1; i <= c.mlp_n_hidden; ++i) p->s.mlp[i].set_geometry(c.mlp_hidden, {c.mlp_hidden});
-    p->s.mlp.back().set_geometry(p->logits_ld, {c.mlp_hidden});
-  } else {
-    p->s.out_lin.set_geometry(c.out_dim, {D});
-  }
+  if (c.head_kind != 0) p->s.out_lin.set_geometry(c.out_dim, {D});
   return MMK_OK;
 }
 
-extern "C" int mmk_tr_plan_create(const mmk_tr_config* cfg, mmk_tr_plan** out) {
-  if (!cfg || !out) return fail(MMK_ERR_INVALID, "tr_plan_create: null argument");
-  mmk_tr_plan* p = new mmk_tr_plan();
-  p->cfg = *cfg;
-  p->tune.parse(cfg->tuning, sizeof(cfg->tuning));
-  const int rc = derive(p);
-  if (rc != MMK_OK) {
-    delete p;
-    return rc;
-  }
-  *out = p;
-  return MMK_OK;
-}
+extern "C" int mmk_tr_plan_create(const mmk_tr_config* cfg, mmk_tr_plan** out) { return plan_create("tr_plan_create", cfg, out, derive); }
 
 extern "C" void mmk_tr_plan_destroy(mmk_tr_plan* p) { delete p; }
 
 extern "C" int mmk_tr_plan_bind(mmk_tr_plan* p, const char* key, const float* dev_ptr, int64_t numel) {
-  if (!p || !key || !dev_ptr) return fail(MMK_ERR_INVALID, "tr_plan_bind: null argument");
-  p->binder.bind(key, dev_ptr, numel);
-  p->committed = false;
-  return MMK_OK;
+  return plan_bind("tr_plan_bind", p, key, dev_ptr, numel);
 }
 
 extern "C" size_t mmk_tr_workspace_bytes(const mmk_tr_plan* p) {
@@ -262,11 +237,7 @@ extern "C" int mmk_tr_commit(mmk_tr_plan* p, void* workspace, size_t workspace_b
     MMK_TRY(pack_rows(p, p->s.in_lin, "input_module.heads.0.0.", "weight", "bias", D, 0, D, 0, st));
   }
   if (c.head_kind == 0) {
-    const std::string hb = "output_modules.0.estimator.0.fc.";
-    for (size_t i = 0; i < p->s.mlp.size(); ++i) {
-      PackedLinear& m = p->s.mlp[i];
-      MMK_TRY(pack_rows(p, m, hb + std::to_string(2 * i) + ".", "weight", "bias", m.N, 0, m.N, 0, st));
-    }
+    MMK_TRY(p->s.head.pack(b, "output_modules.0.estimator.0.fc.", st));
   } else {
     MMK_TRY(pack_rows(p, p->s.out_lin, "output_modules.0.0.", "weight", "bias", c.out_dim, 0, c.out_dim, 0, st));
   }
@@ -368,18 +339,12 @@ static int emit_step(mmk_tr_plan* p, const TrCall& call, hipStream_t st) {
     hx = s.xf;
   }
   if (c.head_kind == 0) {
-    int64_t hx_ld = D;
-    for (size_t i = 0; i < s.mlp.size(); ++i) {
-      const bool lastm = i + 1 == s.mlp.size();
-      float* o = lastm ? s.logits : s.hid[i & 1];
-      const int64_t o_ld = lastm ? p->logits_ld : c.mlp_hidden;
-      MMK_TRY(tr_linear(p, s.mlp[i], hx, hx_ld, B, o, o_ld, lastm ? (int)ACT_NONE : c.mlp_act, st));
-      hx = o;
-      hx_ld = o_ld;
-    }
+    MMK_TRY(s.head.run(hx, D, s.hid, c.mlp_act, [&](const PackedLinear& w, const float* x, int64_t x_ld, float* o, int64_t o_ld, int act) {
+      return tr_linear(p, w, x, x_ld, B, o, o_ld, act, st);
+    }));
     SampleArgs sa = {};
-    sa.logits = s.logits; sa.ld = p->logits_ld; sa.rows = B; sa.n_classes = c.out_dim; sa.has_temp_col = c.learn_temp;
-    sa.min_temp = c.min_temp;
+    s.head.fill(sa);
+    sa.rows = B;
     sa.temperature = call.temperature; sa.uniforms = call.uniforms; sa.uniform_ld = call.uni_ld; sa.uni_off = 0;
     sa.out = (int64_t*)call.out; sa.out_row_stride = call.out_bs; sa.out_tau_off = 0;   // (class tensors: unit stride along time)
     sa.tau_ptr = s.tau; sa.tau_off = 0;
@@ -481,9 +446,6 @@ extern "C" int mmk_tr_last_logits(mmk_tr_plan* p, int32_t batch, float* out, int
   if (!p || !out) return fail(MMK_ERR_INVALID, "tr_last_logits: null argument");
   if (!p->committed || p->cfg.head_kind != 0) return fail(MMK_ERR_STATE, "tr_last_logits: only for a committed plan with the MLP head");
   if (batch < 1 || batch > p->Bmax) return fail(MMK_ERR_INVALID, "tr_last_logits: batch %d outside [1, %d]", batch, p->Bmax);
-  const int n = p->logits_ld;
-  if (out_ld < n) return fail(MMK_ERR_INVALID, "tr_last_logits: out_ld %lld < %d", (long long)out_ld, n);
-  MMK_HIP(hipMemcpy2DAsync(out, (size_t)out_ld * sizeof(float), p->s.logits, (size_t)n * sizeof(float), (size_t)n * sizeof(float),
-                           (size_t)batch, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return MMK_OK;
+  if (out_ld < p->s.head.n_out()) return fail(MMK_ERR_INVALID, "tr_last_logits: out_ld %lld < %d", (long long)out_ld, p->s.head.n_out());
+  return p->s.head.copy_logits(out, out_ld, batch, (hipStream_t)stream);
 }

@@ -42,15 +42,6 @@ struct WnCall {
   int64_t uni_off = 0;
 };
 
-// an output module beyond the first (one per target, wavenet_v2.py:240-243, :293): an MLPIO + sampler of its own geometry on the same hidden vector
-struct WnHead {
-  std::vector<PackedLinear> mlp;
-  int q = 0, hidden = 0, learn_temp = 0;
-  float min_temp = 0.f;
-  float* logits = nullptr;
-  int logits_ld = 0;
-};
-
 struct mmk_wavenet_plan {
   Tuning tune;                  // the config's execution switches (plan_util.h): never the environment in the product library
   mmk_wavenet_config cfg;
@@ -67,17 +58,17 @@ struct mmk_wavenet_plan {
   const float* emb = nullptr;
   const float* cond_emb[MMK_MAX_COND] = {nullptr, nullptr, nullptr, nullptr};   // class conditioning inputs: their EmbeddingIO tables as bound
   int n_tgt = 1;
-  std::vector<WnHead> xheads;                    // targets 1 .. (written to cond[k - 1]); launch path
-  PackedLinear in0_lin;
-  std::vector<PackedLinear> cond_lin, A, Bm, mlp;
+  // one output module per target on the same hidden vector (wavenet_v2.py:240-243, :293), target 0 first: its class goes into in0, target k's
+  // into cond[k - 1] (launch path).  Under a linear head (head_kind != 0) heads[0] stays empty and out_lin is the output module
+  std::vector<MlpHead> heads;
+  PackedLinear in0_lin, out_lin;
+  std::vector<PackedLinear> cond_lin, A, Bm;
 
   std::vector<float*> hist;
   std::vector<float*> cbuf;
   float* ybuf = nullptr;
   float* skipbuf = nullptr;
   float* hid[2] = {nullptr, nullptr};
-  float* logits = nullptr;
-  int logits_ld = 0;
   int64_t* tau = nullptr;
 
   hipStream_t cap_stream = nullptr;
@@ -226,12 +217,10 @@ struct mmk_wavenet_plan {
     affbuf = Aff.empty() ? nullptr : c.take<float>((int64_t)Bmax * 3 * C);
     for (auto& p : Bm)
       if (p.n_tiles > 0) p.carve(c, bias);
-    for (auto& p : mlp) p.carve(c, true);
+    if (cfg.head_kind != 0) out_lin.carve(c, true);
     int hmax = cfg.mlp_hidden > 0 ? cfg.mlp_hidden : 1;
-    for (auto& h : xheads) {
-      for (auto& m : h.mlp) m.carve(c, true);
-      h.logits_ld = (int)round_up(h.q + (h.learn_temp ? 1 : 0), 4);
-      h.logits = c.take<float>((int64_t)Bmax * h.logits_ld);
+    for (auto& h : heads) {
+      h.carve(c, Bmax);
       hmax = h.hidden > hmax ? h.hidden : hmax;
     }
     hist.resize(L + 1);
@@ -243,8 +232,6 @@ struct mmk_wavenet_plan {
     skipbuf = c.take<float>((int64_t)Bmax * (S > 0 ? S : 1));
     hid[0] = c.take<float>((int64_t)Bmax * hmax);
     hid[1] = c.take<float>((int64_t)Bmax * hmax);
-    logits_ld = (int)round_up(cfg.out_dim + (cfg.learn_temp ? 1 : 0), 4);
-    logits = c.take<float>((int64_t)Bmax * logits_ld);
     tau = c.take<int64_t>(8 + 256 + 2048 + 256 + 8);   // [0]: the launch path's position; [8 ..]: stamps of the diagnostic builds
     if (persistent) layout_persistent(c);
   }
@@ -287,12 +274,16 @@ __global__ __launch_bounds__(256) void compose_kernel(const float* __restrict__ 
 
 static int derive(mmk_wavenet_plan* p) {
   const mmk_wavenet_config& c = p->cfg;
+  if (c.act_f < 0 || c.act_f > ACT_COS || c.act_g < 0 || c.act_g > ACT_COS || c.mlp_act < 0 || c.mlp_act > ACT_COS)
+    return fail(MMK_ERR_INVALID, "wavenet_plan_create: act_f / act_g / mlp_act outside MMK_ACT_*");
   if (c.n_layers < 1 || c.n_layers > MMK_MAX_LAYERS) return fail(MMK_ERR_INVALID, "wavenet: n_layers=%d out of range", c.n_layers);
   if (c.dim_dilated < 1 || c.max_batch < 1) return fail(MMK_ERR_INVALID, "wavenet: dim_dilated / max_batch must be positive");
   if (c.n_cond < 0 || c.n_cond > MMK_MAX_COND) return fail(MMK_ERR_INVALID, "wavenet: n_cond=%d out of range", c.n_cond);
   if (c.q_levels == 0 && c.in_dim < 1) return fail(MMK_ERR_INVALID, "wavenet: in_dim required when q_levels == 0");
-  if (c.head_kind == 0 && (c.mlp_hidden < 1 || c.mlp_n_hidden < 0 || c.mlp_n_hidden > MMK_MAX_MLP_HIDDEN))
-    return fail(MMK_ERR_INVALID, "wavenet: bad MLP head geometry");
+  p->heads.assign(1, MlpHead());
+  if (c.head_kind == 0)
+    MMK_TRY(p->heads[0].set_geometry("wavenet", MMK_ERR_INVALID, c.skips_dim > 0 ? c.skips_dim : c.dim_dilated, c.mlp_hidden, c.mlp_n_hidden, c.out_dim,
+                                     c.learn_temp, c.min_temp, 4));
   if (c.head_kind < 0 || c.head_kind > 2) return fail(MMK_ERR_INVALID, "wavenet: head_kind %d unknown", c.head_kind);
   if (c.exec_mode < 0 || c.exec_mode > 1) return fail(MMK_ERR_INVALID, "wavenet: exec_mode %d unknown", c.exec_mode);
   if (c.head_kind != 0 && c.q_levels != 0) return fail(MMK_ERR_UNSUPPORTED, "wavenet: linear head needs a continuous input 0");
@@ -330,27 +321,15 @@ static int derive(mmk_wavenet_plan* p) {
     return fail(MMK_ERR_UNSUPPORTED, "wavenet: %d targets for %d inputs (the loop writes output k into input k)", p->n_tgt, 1 + p->n_cond);
   bool multi = p->n_tgt > 1;
   for (int j = 0; j < p->n_cond; ++j) multi = multi || c.cond_q_levels[j] > 0;
-  p->xheads.clear();
-  for (int k = 1; k < p->n_tgt; ++k) {
-    WnHead h;
-    h.q = c.x_out_dim[k]; h.hidden = c.x_mlp_hidden[k]; h.learn_temp = c.x_learn_temp[k]; h.min_temp = c.x_min_temp[k];
-    const int nh = c.x_mlp_n_hidden[k];
-    if (h.q < 2 || h.hidden < 1 || nh < 0 || nh > MMK_MAX_MLP_HIDDEN) return fail(MMK_ERR_INVALID, "wavenet: bad MLP head geometry of target %d", k);
-    if (c.cond_q_levels[k - 1] < h.q)
-      return fail(MMK_ERR_INVALID, "wavenet: target %d draws from %d classes, but input %d is %s", k, h.q, k,
+  for (int k = 1; k < p->n_tgt; ++k) {      // target 0 has its geometry in the scalar fields (above), the others in the x_* arrays
+    const std::string who = "wavenet target " + std::to_string(k);
+    MlpHead h;
+    if (c.x_out_dim[k] < 2) return fail(MMK_ERR_INVALID, "%s: %d classes", who.c_str(), c.x_out_dim[k]);
+    MMK_TRY(h.set_geometry(who.c_str(), MMK_ERR_INVALID, p->head_in, c.x_mlp_hidden[k], c.x_mlp_n_hidden[k], c.x_out_dim[k], c.x_learn_temp[k], c.x_min_temp[k], 4));
+    if (c.cond_q_levels[k - 1] < h.n_classes)
+      return fail(MMK_ERR_INVALID, "wavenet: target %d draws from %d classes, but input %d is %s", k, h.n_classes, k,
                   c.cond_q_levels[k - 1] > 0 ? "a stream of fewer classes" : "not a class stream");
-    PackedLinear f0;
-    f0.set_geometry(h.hidden, {p->S > 0 ? p->S : p->C});
-    h.mlp.push_back(f0);
-    for (int i = 0; i < nh; ++i) {
-      PackedLinear m;
-      m.set_geometry(h.hidden, {h.hidden});
-      h.mlp.push_back(m);
-    }
-    PackedLinear out;
-    out.set_geometry(h.q + (h.learn_temp ? 1 : 0), {h.hidden});
-    h.mlp.push_back(out);
-    p->xheads.push_back(h);
+    p->heads.push_back(h);
   }
   p->A.resize(p->L);
   p->Bm.resize(p->L);
@@ -370,24 +349,7 @@ static int derive(mmk_wavenet_plan* p) {
     else
       p->Bm[l] = PackedLinear();
   }
-  p->mlp.clear();
-  if (c.head_kind == 0) {
-    PackedLinear first;
-    first.set_geometry(c.mlp_hidden, {p->head_in});
-    p->mlp.push_back(first);
-    for (int i = 0; i < c.mlp_n_hidden; ++i) {
-      PackedLinear h;
-      h.set_geometry(c.mlp_hidden, {c.mlp_hidden});
-      p->mlp.push_back(h);
-    }
-    PackedLinear last;
-    last.set_geometry(c.out_dim + (c.learn_temp ? 1 : 0), {c.mlp_hidden});
-    p->mlp.push_back(last);
-  } else {
-    PackedLinear only;
-    only.set_geometry(c.out_dim, {p->head_in});
-    p->mlp.push_back(only);
-  }
+  if (c.head_kind != 0) p->out_lin.set_geometry(c.out_dim, {p->head_in});
 
   // ---- persistent-kernel mode: one launch for all steps (wavenet_persist.hip) -------------------
   // Geometry it covers: gated k=2 layers, embedding input, MLP head without extra hidden layers,
@@ -556,19 +518,7 @@ static int derive(mmk_wavenet_plan* p) {
 }
 
 extern "C" int mmk_wavenet_plan_create(const mmk_wavenet_config* cfg, mmk_wavenet_plan** out) {
-  if (!cfg || !out) return fail(MMK_ERR_INVALID, "wavenet_plan_create: null argument");
-  if (cfg->act_f < 0 || cfg->act_f > ACT_COS || cfg->act_g < 0 || cfg->act_g > ACT_COS || cfg->mlp_act < 0 || cfg->mlp_act > ACT_COS)
-    return fail(MMK_ERR_INVALID, "wavenet_plan_create: act_f / act_g / mlp_act outside MMK_ACT_*");
-  mmk_wavenet_plan* p = new mmk_wavenet_plan();
-  p->cfg = *cfg;
-  p->tune.parse(cfg->tuning, sizeof(cfg->tuning));
-  int rc = derive(p);
-  if (rc != MMK_OK) {
-    delete p;
-    return rc;
-  }
-  *out = p;
-  return MMK_OK;
+  return plan_create("wavenet_plan_create", cfg, out, derive);
 }
 
 extern "C" void mmk_wavenet_plan_destroy(mmk_wavenet_plan* p) {
@@ -579,23 +529,12 @@ extern "C" void mmk_wavenet_plan_destroy(mmk_wavenet_plan* p) {
 }
 
 extern "C" int mmk_wavenet_plan_bind(mmk_wavenet_plan* p, const char* key, const float* dev_ptr, int64_t numel) {
-  if (!p || !key || !dev_ptr) return fail(MMK_ERR_INVALID, "wavenet_plan_bind: null argument");
-  p->binder.bind(key, dev_ptr, numel);
-  p->committed = false;
-  return MMK_OK;
+  return plan_bind("wavenet_plan_bind", p, key, dev_ptr, numel);
 }
 
 extern "C" int64_t mmk_wavenet_receptive_field(const mmk_wavenet_plan* p) { return p ? p->rf : 0; }
 
-extern "C" size_t mmk_wavenet_workspace_bytes(const mmk_wavenet_plan* p) {
-  if (!p) return 0;
-  mmk_wavenet_plan tmp = *p;  // layout() only writes pointers; run it on a copy
-  tmp.gc = GraphCache();
-  tmp.cap_stream = nullptr;
-  Carver c(nullptr);
-  tmp.layout(c);
-  return c.used();
-}
+extern "C" size_t mmk_wavenet_workspace_bytes(const mmk_wavenet_plan* p) { return plan_workspace_bytes(p); }
 
 __global__ void vec_add_kernel(const float* __restrict__ a, const float* __restrict__ b, int n, float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -603,17 +542,13 @@ __global__ void vec_add_kernel(const float* __restrict__ a, const float* __restr
 }
 
 extern "C" int mmk_wavenet_commit(mmk_wavenet_plan* p, void* workspace, size_t workspace_bytes, mmk_stream_t stream) {
-  if (!p || !workspace) return fail(MMK_ERR_INVALID, "wavenet_commit: null argument");
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) return fail(MMK_ERR_WORKSPACE, "wavenet_commit: workspace must be 256-byte aligned");
+  size_t used = 0;
+  MMK_TRY(plan_place("wavenet_commit", p, workspace, workspace_bytes, &used));
   hipStream_t st = (hipStream_t)stream;
   const mmk_wavenet_config& c = p->cfg;
-  Carver carve(workspace);
-  p->layout(carve);
-  if (carve.used() > workspace_bytes)
-    return fail(MMK_ERR_WORKSPACE, "wavenet_commit: workspace of %zu bytes, %zu needed", workspace_bytes, carve.used());
   MMK_HIP(hipStreamSynchronize(st));   // replays of the cached graph may still be queued: wait before destroying it
   p->gc.reset();  // pointers inside a cached graph are stale now
-  MMK_HIP(hipMemsetAsync(workspace, 0, carve.used(), st));
+  MMK_HIP(hipMemsetAsync(workspace, 0, used, st));
 
   Binder& b = p->binder;
   b.clear_missing();
@@ -832,19 +767,10 @@ extern "C" int mmk_wavenet_commit(mmk_wavenet_plan* p, void* workspace, size_t w
       MMK_HIP(hipStreamSynchronize(st));   // `raw` is host-local
     }
   }
-  // head
-  if (c.head_kind == 0) {
-    const std::string hb = "output_modules.0.estimator.0.fc.";
-    for (size_t i = 0; i < p->mlp.size(); ++i) {
-      PackedLinear& m = p->mlp[i];
-      const std::string kb = hb + std::to_string(2 * i) + ".";
-      const float* w = b.need(kb + "weight", (int64_t)m.N * m.segK[0]);
-      const float* bb = b.need(kb + "bias", m.N);
-      if (w) MMK_TRY(pack_rect(m.Wp, m.k_chunks, 0, 1, m.N, 0, m.segK[0], w, m.segK[0], 1, st));
-      if (bb) MMK_TRY(pack_bias(m.bias, 0, 1, m.N, bb, 0, st));
-    }
-  } else {
-    PackedLinear& m = p->mlp[0];
+  // output modules (heads[0] is empty under the linear head)
+  for (size_t k = 0; k < p->heads.size(); ++k) MMK_TRY(p->heads[k].pack(b, "output_modules." + std::to_string(k) + ".estimator.0.fc.", st));
+  if (c.head_kind != 0) {
+    PackedLinear& m = p->out_lin;
     const float* w = b.need("output_modules.0.0.weight", (int64_t)m.N * m.segK[0]);
     const float* bb = b.need("output_modules.0.0.bias", m.N);
     if (w) MMK_TRY(pack_rect(m.Wp, m.k_chunks, 0, 1, m.N, 0, m.segK[0], w, m.segK[0], 1, st));
@@ -873,17 +799,6 @@ extern "C" int mmk_wavenet_commit(mmk_wavenet_plan* p, void* workspace, size_t w
       MMK_TRY(pack_bias(p->lp_mlp0.bias, 0, 1, PH, p->sp_fb0p, 0, st));
       MMK_TRY(pack_rect(p->lp_mlp1.Wp, p->lp_mlp1.k_chunks, 0, 1, PQ + 1, 0, PH, p->sp_fc2p, PH, 1, st));
       MMK_TRY(pack_bias(p->lp_mlp1.bias, 0, 1, PQ + 1, p->sp_fc2bp, 0, st));
-    }
-  }
-  for (size_t k = 0; k < p->xheads.size(); ++k) {
-    WnHead& h = p->xheads[k];
-    for (size_t i = 0; i < h.mlp.size(); ++i) {
-      PackedLinear& m = h.mlp[i];
-      const std::string kb = "output_modules." + std::to_string(k + 1) + ".estimator.0.fc." + std::to_string(2 * i) + ".";
-      const float* w = b.need(kb + "weight", (int64_t)m.N * m.segK[0]);
-      const float* bb = b.need(kb + "bias", m.N);
-      if (w) MMK_TRY(pack_rect(m.Wp, m.k_chunks, 0, 1, m.N, 0, m.segK[0], w, m.segK[0], 1, st));
-      if (bb) MMK_TRY(pack_bias(m.bias, 0, 1, m.N, bb, 0, st));
     }
   }
   if (!b.missing().empty()) return fail(MMK_ERR_KEY, "wavenet_commit: state_dict tensor %s", b.missing().c_str());
@@ -1024,66 +939,37 @@ static int emit_step(mmk_wavenet_plan* p, const WnCall& call, int64_t tau_off, b
   if (!with_head) return MMK_OK;
   // without skips the head reads the last layer's output: its gated units, or (reverse_layer_order) the residual sum
   const float* x = S > 0 ? p->skipbuf : (p->has_res[L - 1] ? p->hist[L] : p->ybuf);
-  int x_ld = p->head_in;
   if (c.head_kind == 0) {
-    for (size_t i = 0; i < p->mlp.size(); ++i) {
-      const bool last = (i + 1 == p->mlp.size());
-      LinearArgs a = {};
-      p->mlp[i].fill(a);
-      a.seg[0].x = addr_static(x);
-      a.seg[0].ld = x_ld;
-      a.M = M; a.tau_ptr = p->tau; a.tau_off = tau_off;
-      a.epilogue = EPI_STORE;
-      a.act = last ? (int)ACT_NONE : c.mlp_act;  // MLPIO.activation (modules/io.py:205: Mish unless the spec says otherwise)
-      float* o = last ? p->logits : p->hid[i & 1];
-      a.out = addr_static(o);
-      a.out_ld = last ? p->logits_ld : c.mlp_hidden;
-      MMK_TRY(launch_linear(a, st));
-      x = o;
-      x_ld = (int)a.out_ld;
-    }
-    SampleArgs s = {};
-    s.logits = p->logits; s.ld = p->logits_ld; s.rows = M; s.n_classes = c.out_dim; s.has_temp_col = c.learn_temp;
-    s.min_temp = c.min_temp; s.temperature = call.temperature; s.uniforms = call.uniforms;
-    s.uniform_ld = call.uni_ld; s.uni_off = call.uni_off;
-    s.out = (int64_t*)call.in0; s.out_row_stride = call.in0_rs; s.out_tau_off = 1;
-    s.tau_ptr = p->tau; s.tau_off = tau_off;
-    MMK_TRY(launch_sample(s, st));
-    const float* x_head = S > 0 ? p->skipbuf : (p->has_res[L - 1] ? p->hist[L] : p->ybuf);
-    for (size_t k = 0; k < p->xheads.size(); ++k) {     // one output module per target on the same vector (:293); output k + 1 goes into input k + 1
-      const WnHead& h = p->xheads[k];
-      const float* xk = x_head;
-      int xk_ld = p->head_in;
-      for (size_t i = 0; i < h.mlp.size(); ++i) {
-        const bool last = (i + 1 == h.mlp.size());
+    for (size_t k = 0; k < p->heads.size(); ++k) {     // one output module per target on the same vector (:293); output k goes into input k
+      const MlpHead& h = p->heads[k];
+      MMK_TRY(h.run(x, p->head_in, p->hid, c.mlp_act, [&](const PackedLinear& w, const float* hx, int64_t hx_ld, float* o, int64_t o_ld, int act) {
         LinearArgs a = {};
-        h.mlp[i].fill(a);
-        a.seg[0].x = addr_static(xk);
-        a.seg[0].ld = xk_ld;
+        w.fill(a);
+        a.seg[0].x = addr_static(hx);
+        a.seg[0].ld = hx_ld;
         a.M = M; a.tau_ptr = p->tau; a.tau_off = tau_off;
         a.epilogue = EPI_STORE;
-        a.act = last ? (int)ACT_NONE : c.mlp_act;
-        float* o = last ? h.logits : p->hid[i & 1];
+        a.act = act;
         a.out = addr_static(o);
-        a.out_ld = last ? h.logits_ld : h.hidden;
-        MMK_TRY(launch_linear(a, st));
-        xk = o;
-        xk_ld = (int)a.out_ld;
-      }
-      SampleArgs sk = {};
-      sk.logits = h.logits; sk.ld = h.logits_ld; sk.rows = M; sk.n_classes = h.q; sk.has_temp_col = h.learn_temp;
-      sk.min_temp = h.min_temp; sk.temperature = call.temperature;
-      sk.uniforms = call.uniforms ? call.uniforms + (int64_t)(k + 1) * M * call.uni_ld : nullptr;     // (n_targets, batch, n_steps)
-      sk.uniform_ld = call.uni_ld; sk.uni_off = call.uni_off;
-      sk.out = reinterpret_cast<int64_t*>(const_cast<float*>(call.cond[k])); sk.out_row_stride = call.cond_rs[k]; sk.out_tau_off = 1;
-      sk.tau_ptr = p->tau; sk.tau_off = tau_off;
-      MMK_TRY(launch_sample(sk, st));
+        a.out_ld = o_ld;
+        return launch_linear(a, st);
+      }));
+      SampleArgs s = {};
+      h.fill(s);
+      s.rows = M; s.temperature = call.temperature;
+      s.uniforms = call.uniforms ? call.uniforms + (int64_t)k * M * call.uni_ld : nullptr;     // (n_targets, batch, n_steps)
+      s.uniform_ld = call.uni_ld; s.uni_off = call.uni_off;
+      if (k == 0) { s.out = (int64_t*)call.in0; s.out_row_stride = call.in0_rs; }
+      else { s.out = reinterpret_cast<int64_t*>(const_cast<float*>(call.cond[k - 1])); s.out_row_stride = call.cond_rs[k - 1]; }
+      s.out_tau_off = 1;
+      s.tau_ptr = p->tau; s.tau_off = tau_off;
+      MMK_TRY(launch_sample(s, st));
     }
   } else {
     LinearArgs a = {};
-    p->mlp[0].fill(a);
+    p->out_lin.fill(a);
     a.seg[0].x = addr_static(x);
-    a.seg[0].ld = x_ld;
+    a.seg[0].ld = p->head_in;
     a.M = M; a.tau_ptr = p->tau; a.tau_off = tau_off;
     a.epilogue = EPI_STORE; a.act = c.head_kind == 1 ? ACT_ABS : ACT_NONE;
     a.out = addr_time(call.in0, c.in_dim, 1, 1, 0);
@@ -1138,6 +1024,7 @@ static int project_cond(mmk_wavenet_plan* p, const WnCall& call, int j, int col,
 // (clear of the hand-off words) + ONE kernel that runs every step of the block
 static int run_persistent(mmk_wavenet_plan* p, const WnCall& call, int64_t tau0, int64_t n, bool with_head, hipStream_t st) {
   const mmk_wavenet_config& c = p->cfg;
+  const MlpHead& h0 = p->heads[0];      // (persistent mode: one target, a two-layer MLP head)
   for (int64_t done = 0; done < n;) {
     // (the layer pipeline without conditioning has no block to prepare: one launch reads its weights once for up to 2^20 steps)
     const int64_t block = (p->lpipe && p->C1 == 0) ? ((int64_t)1 << 20) : (int64_t)p->kCondBlock;
@@ -1247,11 +1134,11 @@ static int run_persistent(mmk_wavenet_plan* p, const WnCall& call, int64_t tau0,
       k.iters = p->iter_tab; k.ring_floats_per_wg = p->ring_floats_per_wg;
       k.emb = p->emb; k.idx = (int64_t*)call.in0; k.idx_rs = call.in0_rs;
       k.condall = p->condall; k.cond_steps = p->kCondBlock; k.zeros = p->zero_pad;
-      k.fc0_wp = p->mlp[0].Wp; k.fc0_bias = p->mlp[0].bias; k.fc2_wp = p->mlp[1].Wp; k.fc2_bias = p->mlp[1].bias;
+      k.fc0_wp = h0.layers[0].Wp; k.fc0_bias = h0.layers[0].bias; k.fc2_wp = h0.layers[1].Wp; k.fc2_bias = h0.layers[1].bias;
       k.temperature = call.temperature;
       k.uniforms = call.uniforms ? call.uniforms + done : nullptr;
       k.uni_ld = call.uni_ld;
-      k.logits_out = p->logits; k.logits_ld = p->logits_ld;
+      k.logits_out = h0.logits; k.logits_ld = h0.logits_ld;
       k.gran_h = p->gran_h; k.gran_y = p->gran_y; k.gran_skip = p->gran_skip; k.gran_hid = p->gran_hid;
       k.gran_logit = p->gran_logit; k.gran_idx = p->gran_idx;
       k.h_rings = p->h_rings; k.err_flag = p->err_flag; k.xcd_count = p->xcd_count;
@@ -1275,11 +1162,11 @@ static int run_persistent(mmk_wavenet_plan* p, const WnCall& call, int64_t tau0,
     a.layers = p->layer_tab; a.ring_floats_per_wg = p->ring_floats_per_wg;
     a.emb = p->emb; a.idx = (int64_t*)call.in0; a.idx_rs = call.in0_rs;
     a.condall = p->condall; a.cond_steps = p->kCondBlock; a.zeros = p->zero_pad;
-    a.fc0_wp = p->mlp[0].Wp; a.fc0_bias = p->mlp[0].bias; a.fc2_wp = p->mlp[1].Wp; a.fc2_bias = p->mlp[1].bias;
+    a.fc0_wp = h0.layers[0].Wp; a.fc0_bias = h0.layers[0].bias; a.fc2_wp = h0.layers[1].Wp; a.fc2_bias = h0.layers[1].bias;
     a.temperature = call.temperature;
     a.uniforms = call.uniforms ? call.uniforms + done : nullptr;   // column s of this block = done + s
     a.uni_ld = call.uni_ld;
-    a.logits_out = p->logits; a.logits_ld = p->logits_ld;
+    a.logits_out = h0.logits; a.logits_ld = h0.logits_ld;
     a.gran_h = p->gran_h; a.gran_y = p->gran_y; a.gran_skip = p->gran_skip; a.gran_hid = p->gran_hid;
     a.gran_logit = p->gran_logit; a.gran_idx = p->gran_idx;
     a.h_rings = p->h_rings; a.err_flag = p->err_flag;
@@ -1451,7 +1338,6 @@ extern "C" int mmk_wavenet_last_logits(mmk_wavenet_plan* p, int32_t batch, float
   if (!p || !out) return fail(MMK_ERR_INVALID, "wavenet_last_logits: null argument");
   if (!p->committed) return fail(MMK_ERR_STATE, "wavenet_last_logits: plan not committed");
   if (p->cfg.head_kind != 0) return fail(MMK_ERR_UNSUPPORTED, "wavenet_last_logits: only for the MLP head");
-  const int n = p->cfg.out_dim + (p->cfg.learn_temp ? 1 : 0);
   if (p->spipe || p->lpipe) {      // these kernels' head writes 256 classes + the temperature at column 256: the network's classes, then its temperature
     constexpr int PQ = mmk_wavenet_plan::kSpQ, PLD = mmk_wavenet_plan::kSpLogitsLd;
     MMK_HIP(hipMemcpy2DAsync(out, ld * sizeof(float), p->sp_logits, PLD * sizeof(float), p->cfg.out_dim * sizeof(float), batch, hipMemcpyDeviceToDevice,
@@ -1461,9 +1347,7 @@ extern "C" int mmk_wavenet_last_logits(mmk_wavenet_plan* p, int32_t batch, float
                                hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return MMK_OK;
   }
-  MMK_HIP(hipMemcpy2DAsync(out, ld * sizeof(float), p->logits, p->logits_ld * sizeof(float), n * sizeof(float), batch,
-                           hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return MMK_OK;
+  return p->heads[0].copy_logits(out, ld, batch, (hipStream_t)stream);
 }
 
 extern "C" int mmk_wavenet_last_logits_of(mmk_wavenet_plan* p, int32_t target, int32_t batch, float* out, int64_t ld, mmk_stream_t stream) {
@@ -1471,11 +1355,7 @@ extern "C" int mmk_wavenet_last_logits_of(mmk_wavenet_plan* p, int32_t target, i
   if (!p || !out) return fail(MMK_ERR_INVALID, "wavenet_last_logits_of: null argument");
   if (!p->committed) return fail(MMK_ERR_STATE, "wavenet_last_logits_of: plan not committed");
   if (target < 0 || target >= p->n_tgt) return fail(MMK_ERR_INVALID, "wavenet_last_logits_of: target %d of %d", target, p->n_tgt);
-  const WnHead& h = p->xheads[target - 1];
-  const int n = h.q + (h.learn_temp ? 1 : 0);
-  MMK_HIP(hipMemcpy2DAsync(out, ld * sizeof(float), h.logits, h.logits_ld * sizeof(float), n * sizeof(float), batch,
-                           hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return MMK_OK;
+  return p->heads[target].copy_logits(out, ld, batch, (hipStream_t)stream);
 }
 
 extern "C" int mmk_wavenet_profile_steps(mmk_wavenet_plan* p, int32_t batch, void* in0, int64_t in0_row_stride,
