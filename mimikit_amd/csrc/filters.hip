@@ -24,6 +24,7 @@
 // sum has one fixed order, so a result does not depend on the run.  Powers of p come from repeated squaring (and p^(i+1), i < 16, from
 // a product chain), never from powf.
 #include "mmk_common.h"
+#include "wave_ops.h"
 
 namespace mmk {
 
@@ -220,11 +221,7 @@ template <int P>
 __device__ __forceinline__ float nrm_join(float a, float b) { return P == 0 ? fmaxf(a, b) : a + b; }
 
 template <int P>
-__device__ __forceinline__ float nrm_wave(float a) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) a = nrm_join<P>(a, __shfl_xor(a, d));
-  return a;
-}
+__device__ __forceinline__ float nrm_wave(float a) { return P == 0 ? wave_max(a) : wave_sum(a); }
 
 template <int P>
 __global__ __launch_bounds__(kLfWg) void row_norm_partial_kernel(const float* __restrict__ x, int64_t x_row_stride, int64_t n, int64_t n_chunks,

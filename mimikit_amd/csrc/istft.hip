@@ -893,7 +893,7 @@ void stft1024_kernel(const SpectralTables T, const float* __restrict__ x, int64_
       }
     }
     if (OUT == 5) {
-      const float ea_sum = spectral_wave_sum(esum.x), eb_sum = spectral_wave_sum(esum.y);
+      const float ea_sum = wave_sum(esum.x), eb_sum = wave_sum(esum.y);
       if (lane == 0) {
         float* o = out + b * n_frames + f0;
         o[0] = ea_sum;
@@ -1032,7 +1032,7 @@ __global__ __launch_bounds__(256) void stft_generic_kernel(const float* __restri
     }
     if (OUT == 5) {                                         // lanes -> wave (butterfly) -> the waves in order, through the buffer the transform left free
       float2* red = (src == buf0) ? buf1 : buf0;
-      const float wa = spectral_wave_sum(esum[0]), wb = spectral_wave_sum(esum[1]);
+      const float wa = wave_sum(esum[0]), wb = wave_sum(esum[1]);
       if ((tid & 63) == 0) red[tid >> 6] = make_float2(wa, wb);
       __syncthreads();
       if (tid == 0) {

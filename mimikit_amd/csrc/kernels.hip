@@ -4,6 +4,7 @@
 #include <stdarg.h>
 
 #include "mmk_common.h"
+#include "wave_ops.h"
 
 namespace mmk {
 
@@ -134,17 +135,6 @@ int launch_copy_rows(Addr src, int64_t src_ld, Addr dst, int64_t dst_ld, int M, 
 // ---- categorical head -----------------------------------------------------------
 // One wavefront per row.  Lane i owns the contiguous classes [i*per, (i+1)*per),
 // so the inclusive CDF is a lane-local running sum plus a wave exclusive scan.
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 constexpr int kMaxPerLane = 16;  // classes <= 1024
 
 __global__ __launch_bounds__(64) void sample_kernel(const SampleArgs a) {
@@ -202,12 +192,7 @@ __global__ __launch_bounds__(64) void sample_kernel(const SampleArgs a) {
       if (j < per) { v[j] = expf(v[j] - mx); local += v[j]; }
     }
     // inclusive scan across lanes
-    float incl = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const float up = __shfl_up(incl, o);
-      if (lane >= o) incl += up;
-    }
+    const float incl = wave_incl_scan(local, lane);
     const float total = __shfl(incl, 63);
     const float u = a.uniforms[(int64_t)row * a.uniform_ld + tau + a.uni_off];
     const float target = u * total;

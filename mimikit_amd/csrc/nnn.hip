@@ -26,6 +26,7 @@
 // No atomics, no workgroup waits for another, no scratch; every sum has one order, so results are the same from run to run.
 // NaN in the inputs is not handled (min and < drop it silently).
 #include "mmk_common.h"
+#include "wave_ops.h"
 
 namespace mmk {
 
@@ -49,8 +50,7 @@ __global__ __launch_bounds__(256) void inv_row_norm_kernel(const float* __restri
     const float v = p[k];
     a = fmaf(v, v, a);
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) a += __shfl_xor(a, d);
+  a = wave_sum(a);
   if (lane == 0) out[g] = a > 0.f ? 1.0f / sqrtf(a) : 0.f;
 }
 
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(kCcThreads) void cosine_cost_kernel(const float* __
 // ---- subsequence DTW ---------------------------------------------------------------------------------------------------------------
 // lane l receives lane l - 1's v, lane 0 +inf (DPP wave_shr:1; a lane without a source keeps `old`)
 __device__ __forceinline__ float nnn_from_lane_below(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0x7f800000, __float_as_int(v), 0x138, 0xf, 0xf, false));
+  return dpp_move<kDppWaveShr1>(v, INFINITY);
 }
 
 template <int NPAD, bool kRow>

@@ -9,52 +9,45 @@
 // loop spends 24 LDS round trips (ds_bpermute).  On the chain of every sampled step: 2.7 us -> ~0.7 us per clip.
 #pragma once
 #include "mmk_common.h"
+#include "wave_ops.h"
 
 namespace mmk {
 
-
-#define MMK_DPP_F(old_, v_, CTRL, ROWMASK) \
-  __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old_), __float_as_int(v_), CTRL, ROWMASK, 0xf, false))
-#define MMK_DPP_I(old_, v_, CTRL, ROWMASK) __builtin_amdgcn_update_dpp(old_, v_, CTRL, ROWMASK, 0xf, false)
-
-// (the readlane builtin is an integer one: a float argument would be CONVERTED, not reinterpreted)
-__device__ __forceinline__ float readlane_f(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
-
 // maximum over the wave, in every lane
 __device__ __forceinline__ float wave_max_dpp(float v) {
-  v = fmaxf(v, MMK_DPP_F(v, v, 0xB1, 0xf));     // quad_perm [1,0,3,2]
-  v = fmaxf(v, MMK_DPP_F(v, v, 0x4E, 0xf));     // quad_perm [2,3,0,1]
-  v = fmaxf(v, MMK_DPP_F(v, v, 0x141, 0xf));    // row_half_mirror
-  v = fmaxf(v, MMK_DPP_F(v, v, 0x140, 0xf));    // row_mirror: every lane holds its row's maximum
+  v = fmaxf(v, dpp_xor1(v, v));     // quad_perm [1,0,3,2]
+  v = fmaxf(v, dpp_xor2(v, v));     // quad_perm [2,3,0,1]
+  v = fmaxf(v, dpp_half_mirror(v, v));    // row_half_mirror
+  v = fmaxf(v, dpp_mirror(v, v));    // row_mirror: every lane holds its row's maximum
   const float r0 = readlane_f(v, 0), r1 = readlane_f(v, 16), r2 = readlane_f(v, 32), r3 = readlane_f(v, 48);
   return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
 }
 
 // inclusive prefix sum over the lanes of the wave (fixed order: Kogge-Stone inside a row, then the rows' totals)
 __device__ __forceinline__ float wave_scan_dpp(float x) {
-  x += MMK_DPP_F(0.f, x, 0x111, 0xf);           // row_shr:1 (lanes without a source add 0)
-  x += MMK_DPP_F(0.f, x, 0x112, 0xf);           // row_shr:2
-  x += MMK_DPP_F(0.f, x, 0x114, 0xf);           // row_shr:4
-  x += MMK_DPP_F(0.f, x, 0x118, 0xf);           // row_shr:8
-  x += MMK_DPP_F(0.f, x, 0x142, 0xa);           // row_bcast:15 into rows 1 and 3
-  x += MMK_DPP_F(0.f, x, 0x143, 0xc);           // row_bcast:31 into rows 2 and 3
+  x += dpp_move<dpp_row_shr(1)>(x);          // row_shr:1 (lanes without a source add 0)
+  x += dpp_move<dpp_row_shr(2)>(x);          // row_shr:2
+  x += dpp_move<dpp_row_shr(4)>(x);          // row_shr:4
+  x += dpp_move<dpp_row_shr(8)>(x);          // row_shr:8
+  x += dpp_move<kDppRowBcast15, 0xa>(x);       // row_bcast:15 into rows 1 and 3
+  x += dpp_move<kDppRowBcast31, 0xc>(x);       // row_bcast:31 into rows 2 and 3
   return x;
 }
 
 __device__ __forceinline__ int wave_min_dpp(int v) {
-  v = min(v, MMK_DPP_I(v, v, 0xB1, 0xf));
-  v = min(v, MMK_DPP_I(v, v, 0x4E, 0xf));
-  v = min(v, MMK_DPP_I(v, v, 0x141, 0xf));
-  v = min(v, MMK_DPP_I(v, v, 0x140, 0xf));
+  v = min(v, dpp_xor1(v, v));
+  v = min(v, dpp_xor2(v, v));
+  v = min(v, dpp_half_mirror(v, v));
+  v = min(v, dpp_mirror(v, v));
   return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
              min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
 }
 
 __device__ __forceinline__ int wave_max_dpp_i(int v) {
-  v = max(v, MMK_DPP_I(v, v, 0xB1, 0xf));
-  v = max(v, MMK_DPP_I(v, v, 0x4E, 0xf));
-  v = max(v, MMK_DPP_I(v, v, 0x141, 0xf));
-  v = max(v, MMK_DPP_I(v, v, 0x140, 0xf));
+  v = max(v, dpp_xor1(v, v));
+  v = max(v, dpp_xor2(v, v));
+  v = max(v, dpp_half_mirror(v, v));
+  v = max(v, dpp_mirror(v, v));
   return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
              max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
 }
@@ -65,12 +58,10 @@ __device__ __forceinline__ int wave_argmax_first(float best, int bi) {
   auto take = [&](float ob, int oi) {
     if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
   };
-#define MMK_ARGMAX_STEP(CTRL) take(MMK_DPP_F(best, best, CTRL, 0xf), MMK_DPP_I(bi, bi, CTRL, 0xf))
-  MMK_ARGMAX_STEP(0xB1);
-  MMK_ARGMAX_STEP(0x4E);
-  MMK_ARGMAX_STEP(0x141);
-  MMK_ARGMAX_STEP(0x140);
-#undef MMK_ARGMAX_STEP
+  take(dpp_xor1(best, best), dpp_xor1(bi, bi));
+  take(dpp_xor2(best, best), dpp_xor2(bi, bi));
+  take(dpp_half_mirror(best, best), dpp_half_mirror(bi, bi));
+  take(dpp_mirror(best, best), dpp_mirror(bi, bi));
   float rb = readlane_f(best, 0);
   int ri = __builtin_amdgcn_readlane(bi, 0);
 #pragma unroll

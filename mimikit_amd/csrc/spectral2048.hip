@@ -111,7 +111,7 @@ void stft2048_kernel(const SpectralTables T, const float* __restrict__ x, int64_
       }
     }
     if (OUT == 5) {
-      esum = spectral_wave_sum(esum);
+      esum = wave_sum(esum);
       if (lane == 0) out[fr] = esum;
     }
     __builtin_amdgcn_wave_barrier();                        // buf is rewritten by the next frame

@@ -1,6 +1,7 @@
 // Small device helpers shared by the n_fft = 1024 kernels (istft.hip) and the n_fft = 2048 kernels (spectral2048.hip).
 #pragma once
 #include "fft1024.h"
+#include "wave_ops.h"
 
 namespace mmk {
 
@@ -17,13 +18,6 @@ struct SpectralTables {
   const cf32* w2048;         // [1088]: exp(-pi i k / 1024), k <= 1087 (the bins lane + 64 j of a lane, j <= 16)
 };
 int spectral_tables(hipStream_t stream, SpectralTables* out);     // (istft.hip)
-
-// sum over the 64 lanes of a wave, the same in every lane: a butterfly, one fixed order (the frame-energy epilogues, OUT 5)
-__device__ __forceinline__ float spectral_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 __device__ __forceinline__ void load_twiddles(cf32* tw, const cf32* __restrict__ table, int tid, int nthreads) {
   for (int m = tid; m < 1024; m += nthreads) tw[m] = table[m];

@@ -21,23 +21,6 @@
 
 namespace mmk {
 
-// eight partial sums per lane, 16 lanes (one DPP row) that each hold a different K slice: lanes 2 c, 2 c + 1 of the row end with column c's
-// total (own + mirror partner, + half-mirror partner, + the lane two further, + the neighbour: a fixed order) - as in wavenet_spipe.hip's head
-__device__ __forceinline__ float bot_reduce_scatter8(const float (&v)[8], int ks) {
-  auto mirror = [](float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x140, 0xf, 0xf, false)); };
-  auto half_mirror = [](float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x141, 0xf, 0xf, false)); };
-  const bool b3 = (ks & 8) != 0, b2 = (ks & 4) != 0, b1 = (ks & 2) != 0;
-  float k4[4], k2[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) k4[i] = (b3 ? v[4 + i] : v[i]) + mirror(b3 ? v[i] : v[4 + i]);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) k2[i] = (b2 ? k4[2 + i] : k4[i]) + half_mirror(b2 ? k4[i] : k4[2 + i]);
-  float r = (b1 ? k2[1] : k2[0]) + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(b1 ? k2[0] : k2[1]), 0x4E, 0xf, 0xf, false));   // quad_perm [2,3,0,1]
-  r += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r), 0xB1, 0xf, 0xf, false));                                             // quad_perm [1,0,3,2]
-  return r;
-}
-
-
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) f32x4* gf32x4_ptr;
 
@@ -47,10 +30,7 @@ constexpr int kBotClips = 4;
 // sum over the 4 K sub-slices (lanes n, n+16, n+32, n+48), fixed order ((0+1)+(2+3))
 __device__ __forceinline__ f32x4 reduce_ks(f32x4 v) {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[i] += __shfl_xor(v[i], 16);
-    v[i] += __shfl_xor(v[i], 32);
-  }
+  for (int i = 0; i < 4; ++i) v[i] = subslice_sum(v[i]);
   return v;
 }
 
@@ -272,14 +252,10 @@ __global__ __launch_bounds__(kBotThreads) void srnn_bottom_kernel(const SrnnBott
         auto take = [&](float ob, int oi) {
           if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
         };
-#define MMK_DPP_STEP(CTRL)                                                                                         \
-        take(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(best), CTRL, 0xf, 0xf, false)),            \
-             __builtin_amdgcn_update_dpp(0, bi, CTRL, 0xf, 0xf, false))
-        MMK_DPP_STEP(0xB1);    // quad_perm [1,0,3,2]
-        MMK_DPP_STEP(0x4E);    // quad_perm [2,3,0,1]
-        MMK_DPP_STEP(0x141);   // row_half_mirror
-        MMK_DPP_STEP(0x140);   // row_mirror
-#undef MMK_DPP_STEP
+        take(dpp_xor1(best), dpp_xor1(bi));
+        take(dpp_xor2(best), dpp_xor2(bi));
+        take(dpp_half_mirror(best), dpp_half_mirror(bi));
+        take(dpp_mirror(best), dpp_mirror(bi));
 #pragma unroll
         for (int o = 16; o <= 32; o <<= 1) {
           const float ob = __shfl_xor(best, o);
@@ -294,8 +270,7 @@ __global__ __launch_bounds__(kBotThreads) void srnn_bottom_kernel(const SrnnBott
           const int c = lane * per + q;
           if (c < nc) mx = fmaxf(mx, (a.learn_temp ? lg[c] / denom : lg[c]) / T);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        mx = wave_max(mx);
         float local = 0.f;
         for (int q = 0; q < per; ++q) {
           const int c = lane * per + q;
@@ -452,14 +427,6 @@ __global__ __launch_bounds__(kBotThreads) void srnn_bottom1_kernel(const SrnnBot
   const int u0 = (int)(t0 % a.up_slots);                      // outputs[-1][:, (t % fs[-2]) - fs[-2]]   (:257)
   auto upper_at = [&](int step) -> float { return a.upper[((int64_t)clip * a.up_slots + (u0 + step) % a.up_slots) * H + xc]; };
   float up_next = upper_at(0);
-  // sum over the 16 lanes of a DPP row, every lane ends with the total (fixed order)
-  auto row_sum = [](float v) -> float {
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, false));    // quad_perm [1,0,3,2]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, false));    // quad_perm [2,3,0,1]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, false));   // row_half_mirror
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, false));   // row_mirror
-    return v;
-  };
   __syncthreads();
   stamp(0);
   int first_cls = s_win[0];
@@ -496,14 +463,13 @@ __global__ __launch_bounds__(kBotThreads) void srnn_bottom1_kernel(const SrnnBot
       acc += h1 * w2[j][1];
       part[j] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
     }
-    const float mine = bot_reduce_scatter8(part, ks);            // (class cg 8 + ks / 2, in two lanes)
+    const float mine = row_reduce_scatter8(part, ks);            // (class cg 8 + ks / 2, in two lanes)
     const int c = cg * 8 + (ks >> 1);
     if ((ks & 1) == 0 && c < n_out) lbuf[c] = mine + fc2_b;
     for (int r = wave; r < n_extra; r += kBotThreads / 64) {      // rows past 256: one wave each, lanes over k
       float p = 0.f;
       for (int k = lane; k < Hm; k += 64) p = fmaf(hid[(k / KS2) * kPad2 + k % KS2], wx[r * Hm + k], p);
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o);
+      p = wave_sum(p);
       if (lane == 0) lbuf[256 + r] = p + a.fc2_bias[256 + r];
     }
   };
@@ -560,8 +526,7 @@ __global__ __launch_bounds__(kBotThreads) void srnn_bottom1_kernel(const SrnnBot
         const int c = lane * per + q;
         if (c < nc) mx = fmaxf(mx, (a.learn_temp ? lg[c] / denom : lg[c]) / T);
       }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+      mx = wave_max(mx);
       float local = 0.f;
       for (int q = 0; q < per; ++q) {
         const int c = lane * per + q;

@@ -549,22 +549,6 @@ __device__ __forceinline__ void res_tier_role(const SrnnResArgs& a, const SrnnRe
 }
 
 // ---- bottom role -----------------------------------------------------------------------------------------------------------
-// eight partial sums per lane, 16 lanes (one DPP row) that each hold a different K slice: lanes 2 c, 2 c + 1 of the row end with column c's
-// total (own + mirror partner, + half-mirror partner, + the lane two further, + the neighbour: a fixed order) - as srnn_bottom.hip's
-__device__ __forceinline__ float res_reduce_scatter8(const float (&v)[8], int ks) {
-  auto mirror = [](float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x140, 0xf, 0xf, false)); };
-  auto half_mirror = [](float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x141, 0xf, 0xf, false)); };
-  const bool b3 = (ks & 8) != 0, b2 = (ks & 4) != 0, b1 = (ks & 2) != 0;
-  float k4[4], k2[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) k4[i] = (b3 ? v[4 + i] : v[i]) + mirror(b3 ? v[i] : v[4 + i]);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) k2[i] = (b2 ? k4[2 + i] : k4[i]) + half_mirror(b2 ? k4[i] : k4[2 + i]);
-  float r = (b1 ? k2[1] : k2[0]) + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(b1 ? k2[0] : k2[1]), 0x4E, 0xf, 0xf, false));   // quad_perm [2,3,0,1]
-  r += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r), 0xB1, 0xf, 0xf, false));                                             // quad_perm [1,0,3,2]
-  return r;
-}
-
 // One clip per workgroup, every step of the block (srnn_bottom.hip's one-clip kernel with the hidden layer's product composed
 // through the up-sampler: see the top of this file).  Thread layout of both products: lane = 16 cgl + ks - the 16 lanes of a DPP row
 // split K in 16 slices, the 4 rows of a wave and the 8 waves give 32 column groups.
@@ -640,14 +624,6 @@ __device__ __forceinline__ void res_bottom_role(const SrnnResArgs& a, char* smem
   if (tid < 16) s_win[tid] = tid < fsb ? (int)a.idx[(int64_t)clip * a.idx_rs + t0 - fsb + tid] : 0;
   const int xc = tid < H ? tid : 0;
   const int xs_at = (xc / KS0) * kPad0 + xc % KS0;
-  // sum over the 16 lanes of a DPP row, every lane ends with the total (fixed order)
-  auto row_sum = [](float v) -> float {
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, false));    // quad_perm [1,0,3,2]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, false));    // quad_perm [2,3,0,1]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, false));   // row_half_mirror
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, false));   // row_mirror
-    return v;
-  };
   __syncthreads();
   const float a_c0 = (ks < 4 && cg * 4 + ks < Hm) ? acs[cg * 4 + ks] : 0.f;     // frames of one sample (the common case): the weight itself
 
@@ -681,14 +657,13 @@ __device__ __forceinline__ void res_bottom_role(const SrnnResArgs& a, char* smem
       acc += h1 * w2[j][1];
       part[j] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
     }
-    const float mine = res_reduce_scatter8(part, ks);            // (class cg 8 + ks / 2, in two lanes)
+    const float mine = row_reduce_scatter8(part, ks);            // (class cg 8 + ks / 2, in two lanes)
     const int c = cg * 8 + (ks >> 1);
     if ((ks & 1) == 0 && c < n_out) lbuf[c] = mine + fc2_b;
     for (int r = wave; r < n_extra; r += kResWaves) {            // rows past 256: one wave each, lanes over k
       float p = 0.f;
       for (int k = lane; k < Hm; k += 64) p = fmaf(hid[(k / KS2) * kPad2 + k % KS2], wx[r * Hm + k], p);
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o);
+      p = wave_sum(p);
       if (lane == 0) lbuf[256 + r] = p + a.fc2_bias[256 + r];
     }
   };

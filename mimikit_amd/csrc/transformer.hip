@@ -13,6 +13,7 @@
 //   rows of LDS whatever the window.
 // Residual add + LayerNorm: one wave per row, the row in registers, mean then centred second moment in fp32.
 #include "transformer.h"
+#include "wave_ops.h"
 
 namespace mmk {
 
@@ -101,8 +102,7 @@ __global__ __launch_bounds__(256) void tr_attention_kernel(const TrAttnArgs a) {
         p[r] = expf(p[r] - m_new);
         rs += p[r];
       }
-      rs += __shfl_xor(rs, 16);
-      rs += __shfl_xor(rs, 32);
+      rs = subslice_sum(rs);
       l_i = l_i * alpha + rs;
       m_i = m_new;
 #pragma unroll
@@ -157,12 +157,6 @@ int launch_tr_attention(const TrAttnArgs& a, int batch, hipStream_t stream) {
   return MMK_OK;
 }
 
-__device__ __forceinline__ float tr_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 constexpr int kLnPer = 16;   // columns per lane: D <= 1024
 
 // (no __restrict__: out may be res - a wave holds its whole row in registers before it writes)
@@ -187,7 +181,7 @@ __global__ __launch_bounds__(256) void tr_add_ln_kernel(const float* y, int64_t 
     v[k] = x;
     s += x;
   }
-  const float mean = tr_wave_sum(s) / (float)D;
+  const float mean = wave_sum(s) / (float)D;
   float q = 0.f;
 #pragma unroll
   for (int k = 0; k < kLnPer; ++k) {
@@ -197,7 +191,7 @@ __global__ __launch_bounds__(256) void tr_add_ln_kernel(const float* y, int64_t 
       q = fmaf(d, d, q);
     }
   }
-  const float var = tr_wave_sum(q) / (float)D;
+  const float var = wave_sum(q) / (float)D;
   const float rstd = 1.f / sqrtf(var + 1e-5f);
   float* orow = out + (int64_t)row * out_ld;
 #pragma unroll

@@ -2,6 +2,7 @@
 // 8-byte hand-off granules, the polling sweep, MFMA tile steps and fixed-order reductions.
 #pragma once
 #include "mmk_common.h"
+#include "wave_ops.h"
 
 namespace mmk {
 
@@ -134,8 +135,8 @@ __device__ __forceinline__ f32x4 mma_step(float x, float w, f32x4 acc) {
 __device__ __forceinline__ f32x4 reduce_subslices(f32x4 v) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    v[i] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[i]), 0x114, 0xf, 0xf, true));   // row_shr:4
-    v[i] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[i]), 0x118, 0xf, 0xf, true));   // row_shr:8
+    v[i] += dpp_move<dpp_row_shr(4), 0xf, true>(v[i]);   // row_shr:4
+    v[i] += dpp_move<dpp_row_shr(8), 0xf, true>(v[i]);   // row_shr:8
   }
   return v;
 }

@@ -38,12 +38,6 @@ __device__ __forceinline__ float packed_at(const float* wp, int k_chunks, int n,
   return wp[((((int64_t)(n >> 4) * k_chunks + (k >> 4)) * 64) + ((k & 15) >> 2) * 16 + (n & 15)) * 4 + (k & 3)];
 }
 
-__device__ __forceinline__ float quad_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, false));   // quad_perm [2,3,0,1]
-  return v;
-}
-
 __device__ __forceinline__ u64 poll(const u64* p, unsigned epoch, int32_t* err) {
   u64 g = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   unsigned spins = 0;
@@ -232,7 +226,7 @@ __device__ __forceinline__ void run_stage(const WnLpipeArgs& a, int clip, int st
       // tanh(f) sigmoid(g) (wavenet_v2.py:151), both halves at once on their own quads with the hardware exp2 / rcp, as in the other
       // step kernels: sigmoid(x) = 1 / (1 + 2^(-x log2 e)), tanh(x) = 2 sigmoid(2 x) - 1; the g quad sits four lanes up (row_shl:4)
       const float act = fmaf(mmk_rcp(1.0f + __builtin_amdgcn_exp2f(acc * gate_scale)), gate_k, gate_shift);
-      const float other = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(act), 0x104, 0xf, 0xf, false));
+      const float other = dpp_move<dpp_row_shl(4)>(act);
       if ((tid & 7) == 0) zs[tid >> 3] = act * other;
       __syncthreads();
       float a4[4] = {0.f, 0.f, 0.f, 0.f};
@@ -272,12 +266,11 @@ __device__ __forceinline__ void run_stage(const WnLpipeArgs& a, int clip, int st
 #pragma unroll
       for (int k = 0; k < 64; ++k) q4[k & 3] = fmaf(w2[k], hs[k], q4[k & 3]);
       float q = (q4[0] + q4[1]) + (q4[2] + q4[3]);
-      q += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(q), 0xB1, 0xf, 0xf, false));
+      q += dpp_xor1(q);
       if ((tid & 1) == 0) lg[tid >> 1] = q + b2;
       if (wave == 0 && a.learn_temp) {
         float tv = fmaf(wt[0], hid[lane], wt[1] * hid[64 + lane]);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) tv += __shfl_xor(tv, off);
+        tv = wave_sum(tv);
         if (lane == 0) lg[kQ] = tv + bt;
       }
       __syncthreads();

@@ -411,7 +411,7 @@ __global__ __launch_bounds__(wn_threads(KC)) void wavenet_persist_kernel(const W
           const float f = sum_partials(redA) + cndbuf[tid] + biasA[l * 16 + e_n];
           const float act = fmaf(__frcp_rn(1.0f + __builtin_amdgcn_exp2f(f * gate_scale)), gate_k, gate_shift);
           // lane i takes lane i+1's value (row_shl:1): the even lane multiplies tanh(f) by its neighbour's sigmoid(g)
-          const float other = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(act), 0x101, 0xf, 0xf, false));
+          const float other = dpp_move<dpp_row_shl(1)>(act);
           if (!(e_n & 1)) gran_store<XCD>(gran_y + y_slot, epoch, act * other);
         }
         __syncthreads();                                   // B1b: y is on its way - the matrix waves may use the memory pipe
@@ -604,14 +604,10 @@ __global__ __launch_bounds__(wn_threads(KC)) void wavenet_persist_kernel(const W
           auto take = [&](float ob, int oi) {
             if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
           };
-#define MMK_DPP_STEP(CTRL)                                                                                           \
-          take(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(best), CTRL, 0xf, 0xf, false)),            \
-               __builtin_amdgcn_update_dpp(0, bi, CTRL, 0xf, 0xf, false))
-          MMK_DPP_STEP(0xB1);    // quad_perm [1,0,3,2]
-          MMK_DPP_STEP(0x4E);    // quad_perm [2,3,0,1]
-          MMK_DPP_STEP(0x141);   // row_half_mirror
-          MMK_DPP_STEP(0x140);   // row_mirror
-#undef MMK_DPP_STEP
+          take(dpp_xor1(best), dpp_xor1(bi));
+          take(dpp_xor2(best), dpp_xor2(bi));
+          take(dpp_half_mirror(best), dpp_half_mirror(bi));
+          take(dpp_mirror(best), dpp_mirror(bi));
 #pragma unroll
           for (int o = 16; o <= 32; o <<= 1) {
             const float ob = __shfl_xor(best, o);
@@ -626,8 +622,7 @@ __global__ __launch_bounds__(wn_threads(KC)) void wavenet_persist_kernel(const W
             const int c = lane * per + q;
             if (c < nc) mx = fmaxf(mx, (a.learn_temp ? lg[c] / denom : lg[c]) / T);
           }
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+          mx = wave_max(mx);
           float local = 0.f;
           for (int q = 0; q < per; ++q) {
             const int c = lane * per + q;

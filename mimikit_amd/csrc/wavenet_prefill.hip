@@ -13,6 +13,7 @@
 // up-to-three K segments are staged once in LDS, wave w owns column tile w and two 16-row accumulators, weight
 // fragments are streamed (next chunk's load in flight while the current one is multiplied).
 #include "wavenet_prefill.h"
+#include "wave_ops.h"
 
 namespace mmk {
 
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(kPfThreads) void wn_prefill_kernel(const WnPrefillA
       if (EPI == 0) {
         // even packed columns hold f, odd columns g of the same channel (wavenet_v2.py:151): tanh(f) * sigmoid(g)
         const float act = (n & 1) ? sigmoidf_(v) : tanhf(v);
-        const float other = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(act), 0x101, 0xf, 0xf, false));   // lane + 1
+        const float other = dpp_move<dpp_row_shl(1)>(act);   // lane + 1
         if (!(n & 1) && m < a.M && col < a.N)
           a.out[(int64_t)b * a.out_batch + (int64_t)m * a.out_ld + tile * 8 + (n >> 1)] = act * other;
       } else {

@@ -72,59 +72,6 @@ constexpr int kChainPrio = 3;
 #define SP_ABL(bit) ((STAMPS && (a.dbg & (bit))) || (MMK_SP_ABL & (bit)))
 __device__ __forceinline__ int pad_of(int ch) { return (ch >> 4) * kXSlice + (ch & 15); }
 
-__device__ __forceinline__ float dpp_quad_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, false));   // quad_perm [2,3,0,1]
-  return v;
-}
-__device__ __forceinline__ float dpp_half_mirror_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float dpp_mirror_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, false));
-}
-
-__device__ __forceinline__ float dpp_mirror(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, false)); }
-__device__ __forceinline__ float dpp_half_mirror(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, false)); }
-
-// Four partial sums per lane, 16 lanes (one DPP row) that each hold a different K slice: add them up across the row and leave column c's
-// total in lanes 4 c .. 4 c + 3 of the row (lane l of the wave ends with column l / 4 of the wave's 16).  Fixed order: own + mirror
-// partner, + half-mirror partner, then the quad.  A lane reads 1/4 of the inputs it would need with one column per lane: the LDS, which
-// all four SIMDs share, is what bounds a visit otherwise.
-__device__ __forceinline__ float row_reduce_scatter4(float v0, float v1, float v2, float v3, int ks) {
-  const bool hi = (ks & 8) != 0, q4 = (ks & 4) != 0;
-  float t0 = hi ? v2 : v0, t1 = hi ? v3 : v1;
-  const float u0 = hi ? v0 : v2, u1 = hi ? v1 : v3;
-  t0 += dpp_mirror(u0);
-  t1 += dpp_mirror(u1);
-  float w = q4 ? t1 : t0;
-  const float sd = q4 ? t0 : t1;
-  w += dpp_half_mirror(sd);
-  return dpp_quad_sum(w);
-}
-// two partial sums per lane: lanes 0-7 of the row end with column 0's total, lanes 8-15 with column 1's
-__device__ __forceinline__ float row_reduce_scatter2(float v0, float v1, int ks) {
-  const bool hi = (ks & 8) != 0;
-  float t = hi ? v1 : v0;
-  const float u = hi ? v0 : v1;
-  t += dpp_mirror(u);
-  return dpp_quad_sum(dpp_half_mirror_add(t));
-}
-
-// eight partial sums per lane: lanes 2 c, 2 c + 1 of the row end with column c's total (own + mirror partner, + half-mirror partner, + the lane
-// two further, + the neighbour)
-__device__ __forceinline__ float row_reduce_scatter8(const float (&v)[8], int ks) {
-  const bool b3 = (ks & 8) != 0, b2 = (ks & 4) != 0, b1 = (ks & 2) != 0;
-  float k4[4], k2[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) k4[i] = (b3 ? v[4 + i] : v[i]) + dpp_mirror(b3 ? v[i] : v[4 + i]);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) k2[i] = (b2 ? k4[2 + i] : k4[i]) + dpp_half_mirror(b2 ? k4[i] : k4[2 + i]);
-  float r = (b1 ? k2[1] : k2[0]) + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(b1 ? k2[0] : k2[1]), 0x4E, 0xf, 0xf, false));   // quad_perm [2,3,0,1]
-  r += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r), 0xB1, 0xf, 0xf, false));                                             // quad_perm [1,0,3,2]
-  return r;
-}
-
 __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 
 // LDS counters: written by one lane of one wave, read by all; LDS serves a wave's operations in issue order, so data written before
@@ -403,7 +350,7 @@ __device__ void chain_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int q
       z += bzv;
       // tanh(f) sigmoid(g) (wavenet_v2.py:151) with the hardware exp2 / rcp as in the other step kernels; the g row sits four lanes up
       const float act = fmaf(mmk_rcp(1.0f + __builtin_amdgcn_exp2f(z * gate_scale)), gate_k, gate_shift);
-      const float other = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(act), 0x104, 0xf, 0xf, false));   // row_shl:4
+      const float other = dpp_move<dpp_row_shl(4)>(act);   // row_shl:4
       const float y = act * other;
       // ---- publish 8 x | 8 y, re-poison the same words two steps ahead, keep x_s for the delayed taps -------------------------------------
       if (pub_lane) {
@@ -430,7 +377,7 @@ __device__ void chain_role(const WnSpipeArgs& a, Lds& S, int stage, int p, int q
           hc[0] = fma2(f32x2{wh[i][0], wh[i][1]}, f32x2{yv[0], yv[1]}, hc[0]);
           hc[1] = fma2(f32x2{wh[i][2], wh[i][3]}, f32x2{yv[2], yv[3]}, hc[1]);
         }
-        const float hs = dpp_mirror_add(dpp_half_mirror_add(dpp_quad_sum((hc[0][0] + hc[0][1]) + (hc[1][0] + hc[1][1]))));
+        const float hs = row_sum((hc[0][0] + hc[0][1]) + (hc[1][0] + hc[1][1]));
         // the sum so far (the stage below handed it on behind its own publish) was fetched by the helper that staged this visit's message:
         // the chain waves load NOTHING from memory - a load's data is waited for with a count that also covers the stores before it,
         // i.e. every visit would wait for its own publish to be acknowledged (a written-through one: ~1 us)
@@ -1027,7 +974,7 @@ __device__ void head_role(const WnSpipeArgs& a, int p) {
         float zc[4];
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc) zc[cc] = (acc[cc][0][0] + acc[cc][0][1]) + (acc[cc][1][0] + acc[cc][1][1]);
-        hsum = row_reduce_scatter4(zc[0], zc[1], zc[2], zc[3], ks) + dpp_quad_sum(hacc);      // (unit 4 rg + ks / 4 = o, in its four lanes)
+        hsum = row_reduce_scatter4(zc[0], zc[1], zc[2], zc[3], ks) + quad_sum(hacc);      // (unit 4 rg + ks / 4 = o, in its four lanes)
       }
       if (kq == 0) hid[(o >> 3) * kHidSlice + (o & 7)] = mish_fast(hsum + b0);
       __syncthreads();
@@ -1050,7 +997,7 @@ __device__ void head_role(const WnSpipeArgs& a, int p) {
       }
       if (wave == 0 && a.learn_temp) {
         float tv = fmaf(wt[0], hid[(lane >> 3) * kHidSlice + (lane & 7)], wt[1] * hid[(8 + (lane >> 3)) * kHidSlice + (lane & 7)]);
-        tv = dpp_mirror_add(dpp_half_mirror_add(dpp_quad_sum(tv)));        // every lane: its row's sum (DPP; six ds_bpermute round trips before)
+        tv = row_sum(tv);        // every lane: its row's sum (DPP; six ds_bpermute round trips before)
         tv = (readlane_f(tv, 0) + readlane_f(tv, 16)) + (readlane_f(tv, 32) + readlane_f(tv, 48));
         if (lane == 0) lg[kQ] = tv + bt;
       }

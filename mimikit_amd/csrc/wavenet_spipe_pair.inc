@@ -39,8 +39,6 @@ struct Lds2 {
 // acc{clip 0, clip 1} += w.lo * x{clip 0, clip 1} / += w.hi * ..: the weight pair is a 64-bit register pair as it lies in the image
 __device__ __forceinline__ void pk_lo(f32x2& acc, f32x2 w, f32x2 x) { asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(acc) : "v"(w), "v"(x)); }
 __device__ __forceinline__ void pk_hi(f32x2& acc, f32x2 w, f32x2 x) { asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(w), "v"(x)); }
-__device__ __forceinline__ float dpp_xor1(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, false)); }
-__device__ __forceinline__ float dpp_xor2(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, false)); }
 
 // row_reduce_scatter4 for two clips: the same additions in the same order, the last level (the lane two further) keeps clip (ks >> 1) & 1
 // instead of both: lanes 4 c, 4 c + 1 of the row end with column c's total of clip 0, lanes 4 c + 2, 4 c + 3 with clip 1's
@@ -63,8 +61,8 @@ __device__ __forceinline__ float row_reduce_scatter2_pair(float a0, float a1, fl
   const bool hi = (ks & 8) != 0, b1 = (ks & 2) != 0;
   float ta = (hi ? a1 : a0) + dpp_mirror(hi ? a0 : a1);
   float tb = (hi ? b1v : b0) + dpp_mirror(hi ? b0 : b1v);
-  ta = dpp_half_mirror_add(ta);
-  tb = dpp_half_mirror_add(tb);
+  ta += dpp_half_mirror(ta);
+  tb += dpp_half_mirror(tb);
   ta += dpp_xor1(ta);
   tb += dpp_xor1(tb);
   return (b1 ? tb : ta) + dpp_xor2(b1 ? ta : tb);
@@ -258,7 +256,7 @@ __device__ void chain_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, int
       z += bzv;
       // tanh(f) sigmoid(g) (wavenet_v2.py:151); the g row sits four lanes up (same clip)
       const float act = fmaf(mmk_rcp(1.0f + __builtin_amdgcn_exp2f(z * gate_scale)), gate_k, gate_shift);
-      const float other = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(act), 0x104, 0xf, 0xf, false));   // row_shl:4
+      const float other = dpp_move<dpp_row_shl(4)>(act);   // row_shl:4
       const float y = act * other;
       // ---- publish 8 x | 8 y per clip, re-poison the same words two steps ahead, keep x_s for the delayed taps --------------------------------
       unsigned* dst = msg_out + ((int64_t)cm * kSpSlots + slot) * kMsgFloats + pub_off;
@@ -284,8 +282,8 @@ __device__ void chain_role2(const WnSpipeArgs& a, Lds2& S, int stage, int p, int
           pk_hi(hc[1], f32x2{wh[i][2], wh[i][3]}, f32x2{yc[2], yc[3]});
         }
         const f32x2 hsum = hc[0] + hc[1];
-        const float hs0 = dpp_mirror_add(dpp_half_mirror_add(dpp_quad_sum(hsum[0])));
-        const float hs1 = dpp_mirror_add(dpp_half_mirror_add(dpp_quad_sum(hsum[1])));
+        const float hs0 = row_sum(hsum[0]);
+        const float hs1 = row_sum(hsum[1]);
         float hin = 0.f;
         if (hid_chain_in && !(MMK_SP_ABL & 256)) {
           if (!lds_wait1(&S.hidin_ready[v & 3], v + 1, a.err_flag)) return;
