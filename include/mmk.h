@@ -514,6 +514,10 @@ int64_t mmk_srnn_resident_blocks(const mmk_srnn_plan* plan);
 /* diagnostic: warm-ups (mmk_srnn_warmup: SampleRNN.before_generate, sample_rnn_v2.py:226-234) this plan has run as ONE teacher-forced resident launch - the
  * tiers with their matrices in registers, windows from the prompt, no bottom tier - instead of one launch per tier update */
 int64_t mmk_srnn_resident_warmups(const mmk_srnn_plan* plan);
+/* diagnostic: what the bottom tier and the head of the most recent steps outside resident mode were emitted as - 0 nothing yet,
+ * 1 the fused kernel with one clip per workgroup, 2 the fused kernel with four clips per workgroup (MFMA), 3 one launch per op
+ * (the draw is the stand-alone sampler); tests assert that the class picker they mean to cover is the one that ran */
+int32_t mmk_srnn_bottom_kernel(const mmk_srnn_plan* plan);
 
 /* ------------------------------------------------------------------------
  * Seq2SeqLSTMNetwork (mimikit/networks/s2s_lstm_v2.py)

@@ -22,6 +22,8 @@ struct SrnnBottomArgs {
 };
 
 bool srnn_bottom_supported(int H, int Hm, int n_out, int fs);
+// which of the file's two kernels launch_srnn_bottom starts for `a`: 1 = one clip per workgroup, 2 = four clips per workgroup (MFMA)
+int srnn_bottom_kernel_of(const SrnnBottomArgs& a);
 int launch_srnn_bottom(const SrnnBottomArgs& a, hipStream_t stream);
 
 }  // namespace mmk

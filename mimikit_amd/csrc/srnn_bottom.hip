@@ -676,6 +676,8 @@ bool srnn_bottom_supported(int H, int Hm, int n_out, int fs) {
   return srnn_bottom_lds_bytes(a) <= 160 * 1024;
 }
 
+int srnn_bottom_kernel_of(const SrnnBottomArgs& a) { return srnn_bottom1_applies(a) ? 1 : 2; }
+
 int launch_srnn_bottom(const SrnnBottomArgs& a, hipStream_t stream) {
   if (!srnn_bottom_supported(a.H, a.Hm, a.n_out, a.fs)) return fail(MMK_ERR_UNSUPPORTED, "srnn bottom kernel: geometry H=%d Hm=%d", a.H, a.Hm);
   if (srnn_bottom1_applies(a)) {

@@ -86,6 +86,7 @@ struct mmk_srnn_plan {
   bool resident_ready = false;                  // every composed operand of the mode was built at commit
   // fused bottom tier (srnn_bottom.hip): chosen at create time when the geometry allows it
   bool fused_bottom = false;
+  int bottom_kernel = 0;                        // what the last bottom-tier steps outside resident mode were emitted as (mmk_srnn_bottom_kernel)
   bool fused_gru = false;                       // srnn_gru.hip: input linear + both gate products + cell in one launch
   float *wb_raw = nullptr, *bb_raw = nullptr;   // framed conv weight / bias in their state_dict layout
   const float* mlp_raw[2] = {nullptr, nullptr}; // fc0 / fc2 weights as bound (row-major; the caller keeps them alive with the plan)
@@ -768,8 +769,10 @@ static int emit_step(mmk_srnn_plan* p, const SrnnCall& call, int64_t tau_off, in
   if (bottom_steps <= 0) return MMK_OK;
   if (p->fused_bottom) {
     SrnnBottomArgs a = bottom_args(p, call, tau_off, bottom_steps);
+    p->bottom_kernel = srnn_bottom_kernel_of(a);
     return launch_srnn_bottom(a, st);
   }
+  p->bottom_kernel = 3;
   {
     const int fsl = c.frame_size[c.n_tiers - 1];
     SrnnTier& up = p->tiers[p->n_rnn_tiers - 1];
@@ -1091,6 +1094,7 @@ extern "C" int mmk_srnn_sync_status(mmk_srnn_plan* p, mmk_stream_t stream) {
 
 extern "C" int64_t mmk_srnn_resident_blocks(const mmk_srnn_plan* p) { return p ? p->resident_blocks : 0; }
 extern "C" int64_t mmk_srnn_resident_warmups(const mmk_srnn_plan* p) { return p ? p->resident_warmups : 0; }
+extern "C" int32_t mmk_srnn_bottom_kernel(const mmk_srnn_plan* p) { return p ? p->bottom_kernel : 0; }
 
 extern "C" int mmk_srnn_last_logits(mmk_srnn_plan* p, int32_t batch, float* out, int64_t ld, mmk_stream_t stream) {
   if (!p || !out) return fail(MMK_ERR_INVALID, "srnn_last_logits: null argument");

@@ -217,6 +217,7 @@ _SIGNATURES = {
     "mmk_srnn_last_logits_of": (i32, [vp, i32, i32, vp, i64, vp]),
     "mmk_srnn_resident_blocks": (i64, [vp]),
     "mmk_srnn_resident_warmups": (i64, [vp]),
+    "mmk_srnn_bottom_kernel": (i32, [vp]),
     "mmk_srnn_sync_status": (i32, [vp, vp]),
     "mmk_srnn_inject_sync_error": (i32, [vp, vp]),
     "mmk_s2s_plan_create": (i32, [C.POINTER(S2SConfig), C.POINTER(vp)]),
@@ -1177,6 +1178,11 @@ class SrnnPlan(_Plan):
     def resident_warmups(self) -> int:
         """warm-ups run as one teacher-forced resident launch so far (diagnostic, see include/mmk.h)"""
         return int(self._lib.mmk_srnn_resident_warmups(self.handle))
+
+    def bottom_kernel(self) -> int:
+        """what the most recent bottom-tier steps outside resident mode were emitted as: 0 nothing yet, 1 the fused kernel with one clip per
+        workgroup, 2 the fused kernel with four clips per workgroup, 3 one launch per op (diagnostic, see include/mmk.h)"""
+        return int(self._lib.mmk_srnn_bottom_kernel(self.handle))
 
     def last_logits(self, batch: int, target: int = 0) -> torch.Tensor:
         out = torch.empty((batch, self._logit_columns("q_levels", target)), dtype=torch.float32, device=self.device)

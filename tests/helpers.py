@@ -310,7 +310,10 @@ def sampled_picks_ok(raw, temperature, uniforms, picks, min_temp=1e-4, tol=2e-5)
     softmax(logits / T) at `uniforms` (B, n).  A pick k is right iff  cdf[k-1] <= u * total < cdf[k]; device and oracle
     logits differ by fp32 re-association (~1e-6 relative, 2e-4 is the stated logit tolerance), which moves every CDF
     step by about that fraction of the total, so a draw within `tol` * total of a step may fall on either side of it
-    and nowhere else.  Returns (ok (B, n) bool, exact (B, n) bool = inside the interval with no tolerance)."""
+    and nowhere else.  Returns (ok (B, n) bool, exact (B, n) bool = inside the interval with no tolerance).
+    (The pickers alone are held to tests/picker_refs.py: check_picks, on EXACT logits - a zero-weight last layer and a crafted bias: there the
+    only slack is the picker's own fp32 arithmetic and the tolerance, derived per row, is a few 1e-6; here the oracle's logits differ from the
+    device's by re-association, hence 2e-5.)"""
     from oracle import torch_ref as O
     raw = T(raw).double()
     logits = O.mlp_logits(raw.float(), min_temp).double()
