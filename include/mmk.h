@@ -188,6 +188,36 @@ int mmk_nn_cosine_f32(const float* x, int64_t x_row_stride, const float* rx, int
 int mmk_cum_entropy_i64(const int64_t* items, int64_t row_stride, int32_t batch, int64_t t, float* total, float* e, int64_t e_row_stride,
                         mmk_stream_t stream);
 
+/* Labelling corpus frames (mimikit/extract/clusters.py:157-205 HCluster): one level is mmk_inv_row_norm_f32, then the three below.
+ *
+ * mmk_nn_cosine_self_f32: mmk_nn_cosine_f32 with the corpus = the queries and frame r left out of row r: index[r] = the FIRST j != r that
+ * maximises clamp(<x_r, x_j> rx[r] rx[j], -1, 1), cos_best[r] = that value.  The same kernel (a compile-time switch that tests j != r only
+ * in the tiles the diagonal crosses), the same order of the sum, tie rule and span / merge workspace (mmk_nn_cosine_workspace_bytes(rows,
+ * rows)), no atomics.  An all-zero x gives index 0 for every row but row 0, which gets 1.  rows < 2, k < 1: MMK_ERR_INVALID.
+ *
+ * mmk_nn_components_i64: labels[i] (int64) = the number of the weakly connected component of node i in the functional graph i -> nearest[i],
+ * components numbered by rising smallest member; *n_components (one int64 on the device) = their count.  Right for any functional graph -
+ * cycles of any length, self-loops, one chain of n nodes: ceil(log2 n) + 1 rounds of pointer doubling with a carried minimum find the
+ * smallest node of every component's cycle, an integer atomicMin (order-free) the component's smallest member, and a prefix count over the
+ * nodes that are their component's smallest member the number (a kernel of this call).  An entry of `nearest` outside [0, n) is the caller's
+ * error: it is not reported (it is clamped, never used as an address).  Workspace: mmk_nn_components_workspace_bytes(n) = 20 bytes per node
+ * and 4 per 256 nodes.  n < 1: MMK_ERR_INVALID; n >= 2^31: MMK_ERR_UNSUPPORTED.
+ *
+ * mmk_segment_mean_f32: out[s][0 .. k) = the mean of the rows x[order[u]], offsets[s] <= u < offsets[s + 1], for s < n_segments: `order`
+ * holds n row numbers (int64), `offsets` n_segments + 1 rising positions in it.  Members are added in the order given in fp64, divided once
+ * and rounded to fp32 once.  n_segments < 1 or > n (some segment would be empty), n < 1, k < 1: MMK_ERR_INVALID; an empty segment among
+ * n_segments <= n is not looked for on the device (its row is NaN).
+ *
+ * All three: raw pointers and strides, 4-byte alignment of the float data (8 of the int64 data) is enough, tails are masked here, nothing but
+ * the stated outputs and workspace is written, two calls give the same bits.  NaN in the inputs is not handled. */
+int mmk_nn_cosine_self_f32(const float* x, int64_t x_row_stride, const float* rx, int64_t rows, int32_t k, int64_t* index, float* cos_best,
+                           void* workspace, size_t workspace_bytes, mmk_stream_t stream);
+size_t mmk_nn_components_workspace_bytes(int64_t n);
+int mmk_nn_components_i64(const int64_t* nearest, int64_t n, int64_t* labels, int64_t* n_components, void* workspace, size_t workspace_bytes,
+                          mmk_stream_t stream);
+int mmk_segment_mean_f32(const float* x, int64_t x_row_stride, int64_t n, int32_t k, const int64_t* order, const int64_t* offsets,
+                         int64_t n_segments, float* out, int64_t out_row_stride, mmk_stream_t stream);
+
 /* STFT.torch_func with coordinate="mag" == MagSpec.torch_func
  * (mimikit/features/functionals.py:507-524, :576-606): periodic-Hann framed
  * real FFT magnitudes.  x: (batch, n_samples) rows `x_row_stride` apart,

@@ -1,0 +1,209 @@
+// Labelling the frames of a corpus (mimikit/extract/clusters.py:157-205 HCluster): the pieces of one level besides the nearest-other-frame
+// arg-max, which is nn_cosine_kernel<true> of neighbors.hip.
+//
+//   components   the weakly connected components of the functional graph i -> f(i) = nearest[i], numbered by rising smallest member.  Every
+//                component of such a graph holds exactly one cycle, so the smallest node ON the cycle names the component:
+//                  cc_init_kernel     p[i] = f(i) (clamped into [0, n): an entry outside is the caller's error and must not become an
+//                                     address), m[i] = i, cmin[i] = int max
+//                  cc_double_kernel   (p, m) <- (p[p], min(m, m[p])) on ping-pong buffers, R = ceil(log2 n) + 1 rounds, one launch each.  After t
+//                                     rounds p[i] = f^(2^t)(i) and m[i] = min f^j(i) over 0 <= j < 2^t.  2^R >= 2 n: p[i] lies on the cycle (a
+//                                     tail has fewer than n nodes) and m[p[i]] is the minimum over at least n steps from a node of the
+//                                     cycle, that is over the whole cycle - whatever its length, self-loops and one chain of n nodes included.
+//                  cc_rep_kernel      rep[i] = m[p[i]];  atomicMin(cmin[rep[i]], i): the component's smallest member, which need not lie
+//                                     on the cycle.  An integer minimum is the same in any order - the one atomic here, and no float goes
+//                                     through it.
+//                  cc_count_kernel    node i is a root if cmin[rep[i]] == i; roots per block of 256 nodes
+//                  cc_scan_kernel     ONE workgroup: the exclusive prefix sum of the block counts (Hillis-Steele in LDS, chunk by chunk with
+//                                     a carry) and the total = the number of components (int64 on the device).  The prefix count is this
+//                                     kernel, not a torch.cumsum in the wrapper: the entry point returns finished labels.
+//                  cc_rank_kernel     rank[root] = the block's offset + the roots before it in the block (ballot / popcount per wave)
+//                  cc_label_kernel    labels[i] = rank[cmin[rep[i]]]
+//                Indices are kept in 32 bits: five int32 arrays of n and one of the blocks as workspace.
+//   segment_mean out[s] = the mean of the rows x[order[offsets[s] .. offsets[s + 1])]: one workgroup per segment, a lane per bin (consecutive
+//                lanes on consecutive bins: every member row is read coalesced), members added in the order given in fp64, one division and
+//                ONE rounding to fp32.
+// No workgroup waits for another, no scratch, and two calls give the same bits.  NaN in the inputs is not handled.
+#include "mmk_common.h"
+
+namespace mmk {
+
+constexpr int kCcThreads = 256;
+
+__global__ __launch_bounds__(kCcThreads) void cc_init_kernel(const int64_t* __restrict__ nearest, int32_t n, int32_t* __restrict__ p,
+                                                            int32_t* __restrict__ m, int32_t* __restrict__ cmin) {
+  const int64_t i = (int64_t)blockIdx.x * kCcThreads + threadIdx.x;
+  if (i >= n) return;
+  const int64_t f = nearest[i];
+  p[i] = (int32_t)(f < 0 ? 0 : (f >= n ? n - 1 : f));
+  m[i] = (int32_t)i;
+  cmin[i] = 0x7fffffff;
+}
+
+__global__ __launch_bounds__(kCcThreads) void cc_double_kernel(const int32_t* __restrict__ p_in, const int32_t* __restrict__ m_in, int32_t n,
+                                                              int32_t* __restrict__ p_out, int32_t* __restrict__ m_out) {
+  const int64_t i = (int64_t)blockIdx.x * kCcThreads + threadIdx.x;
+  if (i >= n) return;
+  const int32_t q = p_in[i];
+  p_out[i] = p_in[q];
+  m_out[i] = min(m_in[i], m_in[q]);
+}
+
+__global__ __launch_bounds__(kCcThreads) void cc_rep_kernel(const int32_t* __restrict__ p, const int32_t* __restrict__ m, int32_t n,
+                                                           int32_t* __restrict__ rep, int32_t* __restrict__ cmin) {
+  const int64_t i = (int64_t)blockIdx.x * kCcThreads + threadIdx.x;
+  if (i >= n) return;
+  const int32_t r = m[p[i]];
+  rep[i] = r;
+  atomicMin(&cmin[r], (int32_t)i);
+}
+
+__global__ __launch_bounds__(kCcThreads) void cc_count_kernel(const int32_t* __restrict__ rep, const int32_t* __restrict__ cmin, int32_t n,
+                                                             int32_t* __restrict__ counts) {
+  const int64_t i = (int64_t)blockIdx.x * kCcThreads + threadIdx.x;
+  const int root = (i < n && cmin[rep[i < n ? i : 0]] == (int32_t)i) ? 1 : 0;
+  const int total = __syncthreads_count(root);
+  if (threadIdx.x == 0) counts[blockIdx.x] = total;
+}
+
+// in place: counts[b] becomes the number of roots in the blocks before b
+__global__ __launch_bounds__(kCcThreads) void cc_scan_kernel(int32_t* __restrict__ counts, int32_t n_blocks, int64_t* __restrict__ n_components) {
+  __shared__ int32_t scan[2][kCcThreads];
+  const int tid = threadIdx.x;
+  int32_t carry = 0;
+  for (int32_t b0 = 0; b0 < n_blocks; b0 += kCcThreads) {
+    const int32_t b = b0 + tid;
+    const int32_t v = b < n_blocks ? counts[b] : 0;
+    int cur = 0;
+    scan[0][tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (int off = 1; off < kCcThreads; off <<= 1) {
+      scan[cur ^ 1][tid] = scan[cur][tid] + (tid >= off ? scan[cur][tid - off] : 0);
+      cur ^= 1;
+      __syncthreads();
+    }
+    if (b < n_blocks) counts[b] = carry + scan[cur][tid] - v;
+    const int32_t next = carry + scan[cur][kCcThreads - 1];
+    __syncthreads();        // (the next chunk writes scan[0] again)
+    carry = next;
+  }
+  if (tid == 0) *n_components = carry;
+}
+
+__global__ __launch_bounds__(kCcThreads) void cc_rank_kernel(const int32_t* __restrict__ rep, const int32_t* __restrict__ cmin,
+                                                            const int32_t* __restrict__ offsets, int32_t n, int32_t* __restrict__ rank) {
+  __shared__ int32_t wave_roots[kCcThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t i = (int64_t)blockIdx.x * kCcThreads + tid;
+  const bool root = i < n && cmin[rep[i < n ? i : 0]] == (int32_t)i;
+  const unsigned long long mask = __ballot(root);
+  if (lane == 0) wave_roots[wave] = __popcll(mask);
+  __syncthreads();
+  if (!root) return;
+  int32_t before = offsets[blockIdx.x] + __popcll(mask & ((1ull << lane) - 1ull));
+  for (int w = 0; w < wave; ++w) before += wave_roots[w];
+  rank[i] = before;
+}
+
+__global__ __launch_bounds__(kCcThreads) void cc_label_kernel(const int32_t* __restrict__ rep, const int32_t* __restrict__ cmin,
+                                                             const int32_t* __restrict__ rank, int32_t n, int64_t* __restrict__ labels) {
+  const int64_t i = (int64_t)blockIdx.x * kCcThreads + threadIdx.x;
+  if (i >= n) return;
+  labels[i] = rank[cmin[rep[i]]];
+}
+
+__global__ __launch_bounds__(256) void segment_mean_kernel(const float* __restrict__ x, int64_t x_row_stride, int64_t n, int32_t K,
+                                                          const int64_t* __restrict__ order, const int64_t* __restrict__ offsets,
+                                                          float* __restrict__ out, int64_t out_row_stride) {
+  const int64_t s = blockIdx.x;
+  // (clamped: a wrong offset or member is the caller's error and gives a wrong mean, never an address outside x or order)
+  const int64_t beg = min(max(offsets[s], (int64_t)0), n), end = min(max(offsets[s + 1], beg), n);
+  const double count = (double)(end - beg);
+  for (int k = threadIdx.x; k < K; k += blockDim.x) {
+    double acc = 0.0;
+    for (int64_t u = beg; u < end; ++u) {
+      const int64_t r = min(max(order[u], (int64_t)0), n - 1);      // (one address for the whole wave)
+      acc += (double)x[r * x_row_stride + k];
+    }
+    out[s * out_row_stride + k] = (float)(acc / count);
+  }
+}
+
+static int cc_blocks(int64_t n) { return (int)((n + kCcThreads - 1) / kCcThreads); }
+
+}  // namespace mmk
+
+extern "C" size_t mmk_nn_components_workspace_bytes(int64_t n) {
+  using namespace mmk;
+  if (n < 1 || n > 0x7fffffffLL) return 0;
+  return ((size_t)5 * (size_t)n + (size_t)cc_blocks(n)) * sizeof(int32_t);
+}
+
+extern "C" int mmk_nn_components_i64(const int64_t* nearest, int64_t n, int64_t* labels, int64_t* n_components, void* workspace,
+                                     size_t workspace_bytes, mmk_stream_t stream) {
+  using namespace mmk;
+  if (n < 1) return fail(MMK_ERR_INVALID, "nn_components: n = %lld < 1 (nodes)", (long long)n);
+  if (n > 0x7fffffffLL) return fail(MMK_ERR_UNSUPPORTED, "nn_components: n = %lld nodes: indices are kept in 32 bits", (long long)n);
+  if (!nearest || !labels || !n_components || !workspace)
+    return fail(MMK_ERR_INVALID, "nn_components: bad arguments (null pointer)");
+  if ((reinterpret_cast<uintptr_t>(nearest) | reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(n_components)) & 7)
+    return fail(MMK_ERR_INVALID, "nn_components: nearest, labels and n_components must be 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(workspace) & 3) return fail(MMK_ERR_INVALID, "nn_components: the workspace must be 4-byte aligned");
+  if (workspace_bytes < mmk_nn_components_workspace_bytes(n))
+    return fail(MMK_ERR_WORKSPACE, "nn_components: the workspace has %zu bytes, %zu are needed", workspace_bytes,
+                mmk_nn_components_workspace_bytes(n));
+  hipStream_t st = (hipStream_t)stream;
+  const int32_t nn = (int32_t)n;
+  const int blocks = cc_blocks(n);
+  int32_t* w = static_cast<int32_t*>(workspace);
+  int32_t* p[2] = {w, w + n};
+  int32_t* m[2] = {w + 2 * n, w + 3 * n};
+  int32_t* cmin = w + 4 * n;
+  int32_t* counts = w + 5 * n;
+  const dim3 grid((unsigned)blocks), wg(kCcThreads);
+  hipLaunchKernelGGL(cc_init_kernel, grid, wg, 0, st, nearest, nn, p[0], m[0], cmin);
+  MMK_HIP(hipGetLastError());
+  int rounds = 1;                                   // ceil(log2 n) + 1
+  while (((int64_t)1 << (rounds - 1)) < n) ++rounds;
+  int cur = 0;
+  for (int r = 0; r < rounds; ++r, cur ^= 1) {
+    hipLaunchKernelGGL(cc_double_kernel, grid, wg, 0, st, p[cur], m[cur], nn, p[cur ^ 1], m[cur ^ 1]);
+    MMK_HIP(hipGetLastError());
+  }
+  int32_t* rep = p[cur ^ 1];                        // the buffers of the round before the last are free again
+  int32_t* rank = m[cur ^ 1];
+  hipLaunchKernelGGL(cc_rep_kernel, grid, wg, 0, st, p[cur], m[cur], nn, rep, cmin);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(cc_count_kernel, grid, wg, 0, st, rep, cmin, nn, counts);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(cc_scan_kernel, dim3(1), wg, 0, st, counts, (int32_t)blocks, n_components);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(cc_rank_kernel, grid, wg, 0, st, rep, cmin, counts, nn, rank);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(cc_label_kernel, grid, wg, 0, st, rep, cmin, rank, nn, labels);
+  MMK_HIP(hipGetLastError());
+  return MMK_OK;
+}
+
+extern "C" int mmk_segment_mean_f32(const float* x, int64_t x_row_stride, int64_t n, int32_t k, const int64_t* order, const int64_t* offsets,
+                                    int64_t n_segments, float* out, int64_t out_row_stride, mmk_stream_t stream) {
+  using namespace mmk;
+  if (n < 1) return fail(MMK_ERR_INVALID, "segment_mean: n = %lld < 1 (rows)", (long long)n);
+  if (k < 1) return fail(MMK_ERR_INVALID, "segment_mean: k = %d < 1 (bins)", k);
+  if (n_segments < 1 || n_segments > n)
+    return fail(MMK_ERR_INVALID, "segment_mean: %lld segments of %lld rows (every segment has a member)", (long long)n_segments, (long long)n);
+  if (n_segments > 0x7fffffffLL)
+    return fail(MMK_ERR_UNSUPPORTED, "segment_mean: %lld segments are more than one launch takes", (long long)n_segments);
+  if (!x || !order || !offsets || !out || x_row_stride < 0 || out_row_stride < 0)
+    return fail(MMK_ERR_INVALID, "segment_mean: bad arguments (null pointer or negative stride %lld / %lld)", (long long)x_row_stride,
+                (long long)out_row_stride);
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 3)
+    return fail(MMK_ERR_INVALID, "segment_mean: x and out must be 4-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(order) | reinterpret_cast<uintptr_t>(offsets)) & 7)
+    return fail(MMK_ERR_INVALID, "segment_mean: order and offsets must be 8-byte aligned");
+  const int threads = k <= 64 ? 64 : (k <= 128 ? 128 : 256);
+  hipLaunchKernelGGL(segment_mean_kernel, dim3((unsigned)n_segments), dim3(threads), 0, (hipStream_t)stream, x, x_row_stride, n, k, order, offsets,
+                     out, out_row_stride);
+  MMK_HIP(hipGetLastError());
+  return MMK_OK;
+}

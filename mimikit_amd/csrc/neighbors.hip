@@ -19,6 +19,9 @@
 //                         joined by "greater value, then lower index" and one pair per query row goes to the workspace, span-major.
 //                         Workgroups are numbered so that those in flight together share few query blocks and few spans (kNnGroup query
 //                         blocks by all spans, query block fastest).
+//                         nn_cosine_kernel<true> (mmk_nn_cosine_self_f32) is the same kernel with the corpus = the queries and frame r left
+//                         out of row r: the nearest OTHER frame, every level of HCluster (hcluster.hip holds the rest of a level).  Its
+//                         instance keeps four registers in scratch, read once per tile outside the loop over the bins; <false> has none.
 //   nn_merge_kernel       one thread per query row joins the spans' pairs in rising span order (strictly greater wins: the lower index
 //                         stays) and writes index (int64) and cos_best.
 //   cum_entropy_kernel    one workgroup per row of t items.  e[s] = log(s + 1) - S(s) / (s + 1) with S(s) = sum_{u <= s} (f(r_u + 1) - f(r_u)),
@@ -28,7 +31,7 @@
 //                         scan in LDS adds the chunk in one fixed order on top of the carry, all in fp64; e is clamped at 0 (and IS 0 while the row has shown
 //                         one item only: the telescoped sum leaves a rounding residue there) and rounded to
 //                         fp32 once, the total is a fixed-order fp64 sum of the clamped values rounded once.
-// No atomics, no workgroup waits for another, no scratch; every sum has one order, so results are the same from run to run.
+// No atomics, no workgroup waits for another; every sum has one order, so results are the same from run to run.
 // NaN in the inputs is not handled (> drops it silently).
 #include "mmk_common.h"
 
@@ -50,6 +53,9 @@ static_assert(kNnRows == 128 && kNnCols == 128 && kNnThreads == 256, "four waves
 
 __device__ __forceinline__ bool nn_better(float v, int j, float bv, int bj) { return v > bv || (v == bv && j < bj); }
 
+// kSelf: the corpus IS the queries (the host passes y = x, ry = rx, M = rows) and frame j == r is left out of row r's arg-max - every level
+// of HCluster (extract/clusters.py).  The <false> instance is the kernel as it was before the switch, statement for statement.
+template <bool kSelf>
 __global__ __launch_bounds__(kNnThreads, 2) void nn_cosine_kernel(const float* __restrict__ x, int64_t x_row_stride, const float* __restrict__ rx,
                                                                int64_t rows, const float* __restrict__ y, int64_t y_row_stride,
                                                                const float* __restrict__ ry, int64_t M, int32_t K, int32_t n_blocks,
@@ -141,7 +147,13 @@ __global__ __launch_bounds__(kNnThreads, 2) void nn_cosine_kernel(const float* _
       __syncthreads();
     }
 
-    // the tile's arg-max, inside the lane and in rising frame order: strictly greater wins, so the lowest index stays
+    // the tile's arg-max, inside the lane and in rising frame order: strictly greater wins, so the lowest index stays.  kSelf: self_jl is
+    // the tile's frame that IS this lane's first query row (the second one's lies 32 further on) where the diagonal crosses the tile, and
+    // no frame of the tile anywhere else - one epilogue, since a second copy of it for the diagonal's tiles does not fit the registers
+    int self_jl = -64;
+    if constexpr (kSelf) {
+      if (jt < rbase + kNnRows && jt + kNnCols > rbase) self_jl = wn * 64 + fr - (int)(jt - rbase);
+    }
 #pragma unroll
     for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
@@ -152,7 +164,9 @@ __global__ __launch_bounds__(kNnThreads, 2) void nn_cosine_kernel(const float* _
 #pragma unroll
         for (int tn = 0; tn < 2; ++tn) {
           const float c = fminf(fmaxf(acc[tm][tn][q] * rxq[tn] * ryj, -1.f), 1.f);
-          if (j < jend && c > best[tn]) {
+          bool take = j < jend && c > best[tn];
+          if constexpr (kSelf) take = take && jl != self_jl + tn * 32;
+          if (take) {
             best[tn] = c;
             bidx[tn] = (int)j;
           }
@@ -262,6 +276,26 @@ __global__ __launch_bounds__(kCeThreads) void cum_entropy_kernel(const int64_t* 
 
 static int nn_spans(int64_t m) { return (int)((m + kNnSpan - 1) / kNnSpan); }
 
+// the two launches of one call, shared by the two entry points (kSelf: y = x, ry = rx, m = rows)
+template <bool kSelf>
+static int nn_launch(const char* who, const float* x, int64_t x_row_stride, const float* rx, int64_t rows, const float* y, int64_t y_row_stride,
+                     const float* ry, int64_t m, int32_t k, int64_t* index, float* cos_best, void* workspace, hipStream_t st) {
+  const int n_spans = nn_spans(m);
+  const int64_t n_blocks = (rows + kNnRows - 1) / kNnRows;
+  const int64_t groups = (n_blocks + kNnGroup - 1) / kNnGroup;
+  const int64_t grid = groups * kNnGroup * n_spans;
+  if (grid > 0x7fffffffLL)
+    return fail(MMK_ERR_UNSUPPORTED, "%s: %lld rows against %lld frames are more than one launch takes", who, (long long)rows, (long long)m);
+  float* ws_val = static_cast<float*>(workspace);
+  int32_t* ws_idx = reinterpret_cast<int32_t*>(ws_val + rows * n_spans);
+  hipLaunchKernelGGL(nn_cosine_kernel<kSelf>, dim3((unsigned)grid), dim3(kNnThreads), 0, st, x, x_row_stride, rx, rows, y, y_row_stride, ry, m, k,
+                     (int32_t)n_blocks, n_spans, ws_val, ws_idx);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, ws_val, ws_idx, rows, n_spans, index, cos_best);
+  MMK_HIP(hipGetLastError());
+  return MMK_OK;
+}
+
 }  // namespace mmk
 
 extern "C" size_t mmk_nn_cosine_workspace_bytes(int64_t rows, int64_t m) {
@@ -289,21 +323,27 @@ extern "C" int mmk_nn_cosine_f32(const float* x, int64_t x_row_stride, const flo
   if (workspace_bytes < mmk_nn_cosine_workspace_bytes(rows, m))
     return fail(MMK_ERR_WORKSPACE, "nn_cosine: the workspace has %zu bytes, %zu are needed", workspace_bytes,
                 mmk_nn_cosine_workspace_bytes(rows, m));
-  const int n_spans = nn_spans(m);
-  const int64_t n_blocks = (rows + kNnRows - 1) / kNnRows;
-  const int64_t groups = (n_blocks + kNnGroup - 1) / kNnGroup;
-  const int64_t grid = groups * kNnGroup * n_spans;
-  if (grid > 0x7fffffffLL)
-    return fail(MMK_ERR_UNSUPPORTED, "nn_cosine: %lld rows against %lld frames are more than one launch takes", (long long)rows, (long long)m);
-  float* ws_val = static_cast<float*>(workspace);
-  int32_t* ws_idx = reinterpret_cast<int32_t*>(ws_val + rows * n_spans);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(nn_cosine_kernel, dim3((unsigned)grid), dim3(kNnThreads), 0, st, x, x_row_stride, rx, rows, y, y_row_stride, ry, m, k,
-                     (int32_t)n_blocks, n_spans, ws_val, ws_idx);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, ws_val, ws_idx, rows, n_spans, index, cos_best);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return nn_launch<false>("nn_cosine", x, x_row_stride, rx, rows, y, y_row_stride, ry, m, k, index, cos_best, workspace, (hipStream_t)stream);
+}
+
+extern "C" int mmk_nn_cosine_self_f32(const float* x, int64_t x_row_stride, const float* rx, int64_t rows, int32_t k, int64_t* index,
+                                      float* cos_best, void* workspace, size_t workspace_bytes, mmk_stream_t stream) {
+  using namespace mmk;
+  if (rows < 2) return fail(MMK_ERR_INVALID, "nn_cosine_self: rows = %lld < 2 (a frame needs another one)", (long long)rows);
+  if (k < 1) return fail(MMK_ERR_INVALID, "nn_cosine_self: k = %d < 1 (bins)", k);
+  if (rows > 0x7fffffffLL - kNnSpan)
+    return fail(MMK_ERR_UNSUPPORTED, "nn_cosine_self: %lld frames: indices are kept in 32 bits across the spans", (long long)rows);
+  if (!x || !rx || !index || !cos_best || !workspace || x_row_stride < 0)
+    return fail(MMK_ERR_INVALID, "nn_cosine_self: bad arguments (null pointer or negative stride %lld)", (long long)x_row_stride);
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(rx) | reinterpret_cast<uintptr_t>(cos_best) |
+       reinterpret_cast<uintptr_t>(workspace)) & 3)
+    return fail(MMK_ERR_INVALID, "nn_cosine_self: x, rx, cos_best and the workspace must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(index) & 7) return fail(MMK_ERR_INVALID, "nn_cosine_self: index must be 8-byte aligned");
+  if (workspace_bytes < mmk_nn_cosine_workspace_bytes(rows, rows))
+    return fail(MMK_ERR_WORKSPACE, "nn_cosine_self: the workspace has %zu bytes, %zu are needed", workspace_bytes,
+                mmk_nn_cosine_workspace_bytes(rows, rows));
+  return nn_launch<true>("nn_cosine_self", x, x_row_stride, rx, rows, x, x_row_stride, rx, rows, k, index, cos_best, workspace,
+                         (hipStream_t)stream);
 }
 
 extern "C" int mmk_cum_entropy_i64(const int64_t* items, int64_t row_stride, int32_t batch, int64_t t, float* total, float* e,

@@ -1,1 +1,2 @@
 from .from_neighbors import *
+from .clusters import *

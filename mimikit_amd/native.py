@@ -166,6 +166,10 @@ _SIGNATURES = {
     "mmk_nn_cosine_workspace_bytes": (C.c_size_t, [i64, i64]),
     "mmk_nn_cosine_f32": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, i32, vp, vp, vp, C.c_size_t, vp]),
     "mmk_cum_entropy_i64": (i32, [vp, i64, i32, i64, vp, vp, i64, vp]),
+    "mmk_nn_cosine_self_f32": (i32, [vp, i64, vp, i64, i32, vp, vp, vp, C.c_size_t, vp]),
+    "mmk_nn_components_workspace_bytes": (C.c_size_t, [i64]),
+    "mmk_nn_components_i64": (i32, [vp, i64, vp, vp, vp, C.c_size_t, vp]),
+    "mmk_segment_mean_f32": (i32, [vp, i64, i64, i32, vp, vp, i64, vp, i64, vp]),
     "mmk_stft_n_frames": (i64, [i64, i32, i32, i32]),
     "mmk_stft_mag_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, vp, vp]),
     "mmk_stft_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, i32, i32, vp, vp]),
@@ -533,6 +537,66 @@ def cum_entropy(items: torch.Tensor, per_step: bool = False):
     check(lib().mmk_cum_entropy_i64(ptr(items), items.stride(0), batch, t, ptr(total), ptr(e), t if per_step else 0, stream_ptr(items.device)),
           "mmk_cum_entropy_i64")
     return (total, e) if per_step else total
+
+
+def nn_cosine_self(x: torch.Tensor, inv_norm: Optional[torch.Tensor] = None):
+    """x (rows >= 2, k), inv_norm (rows,) = inv_row_norm(x) (computed here if not given) -> (index (rows,) int64, cos_best (rows,) fp32): per
+    row the first OTHER row of x of the largest cosine similarity and that cosine.  The (rows, rows) matrix is never formed"""
+    x = _nnn_frames(x, 2, "nn_cosine_self")
+    rows, k = x.shape
+    if rows < 2 or k < 1:
+        raise ValueError(f"nn_cosine_self: at least two frames of at least one bin, got {tuple(x.shape)}")
+    rx = inv_row_norm(x) if inv_norm is None else inv_norm
+    require_device(rx)
+    if rx.shape != (rows,) or rx.dtype != torch.float32 or not rx.is_contiguous():
+        raise ValueError(f"nn_cosine_self: inv_norm must be {rows} contiguous float32 values, got {tuple(rx.shape)} {rx.dtype}")
+    index = torch.empty((rows,), dtype=torch.int64, device=x.device)
+    best = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    n_work = lib().mmk_nn_cosine_workspace_bytes(rows, rows)
+    work = torch.empty((n_work // 4,), dtype=torch.float32, device=x.device)
+    check(lib().mmk_nn_cosine_self_f32(ptr(x), x.stride(0), ptr(rx), rows, k, ptr(index), ptr(best), ptr(work), n_work, stream_ptr(x.device)),
+          "mmk_nn_cosine_self_f32")
+    return index, best
+
+
+def nn_components(nearest: torch.Tensor):
+    """nearest (n,) int64 with entries in [0, n) -> (labels (n,) int64, n_components () int64, on the device): the weakly connected components
+    of the graph i -> nearest[i], numbered by rising smallest member"""
+    if not isinstance(nearest, torch.Tensor):
+        raise TypeError(f"nn_components: expected a torch.Tensor, got {type(nearest)}")
+    if nearest.dtype != torch.int64:
+        raise TypeError(f"nn_components takes int64 indices, got {nearest.dtype}")
+    if nearest.dim() != 1 or nearest.shape[0] < 1:
+        raise ValueError(f"nn_components: expected (n >= 1,) indices, got shape {tuple(nearest.shape)}")
+    require_device(nearest)
+    nearest = nearest.contiguous()
+    n = nearest.shape[0]
+    labels = torch.empty((n,), dtype=torch.int64, device=nearest.device)
+    count = torch.empty((), dtype=torch.int64, device=nearest.device)
+    n_work = lib().mmk_nn_components_workspace_bytes(n)
+    work = torch.empty((n_work // 4,), dtype=torch.int32, device=nearest.device)
+    check(lib().mmk_nn_components_i64(ptr(nearest), n, ptr(labels), ptr(count), ptr(work), n_work, stream_ptr(nearest.device)),
+          "mmk_nn_components_i64")
+    return labels, count
+
+
+def segment_mean(x: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+    """x (n, k) fp32, order (n,) int64 row numbers, offsets (S + 1,) int64 rising positions in `order` -> (S, k) fp32: row s is the mean of the
+    rows x[order[offsets[s] : offsets[s + 1]]], added in that order in fp64 and rounded once"""
+    x = _nnn_frames(x, 2, "segment_mean")
+    n, k = x.shape
+    for name, t in (("order", order), ("offsets", offsets)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1:
+            raise TypeError(f"segment_mean: {name} must be a 1-D int64 tensor")
+    require_device(order, offsets)
+    n_segments = offsets.shape[0] - 1
+    if n < 1 or k < 1 or order.shape[0] != n or n_segments < 1 or n_segments > n:
+        raise ValueError(f"segment_mean: x {tuple(x.shape)}, order {tuple(order.shape)}, {n_segments} segments")
+    order, offsets = order.contiguous(), offsets.contiguous()
+    out = torch.empty((n_segments, k), dtype=torch.float32, device=x.device)
+    check(lib().mmk_segment_mean_f32(ptr(x), x.stride(0), n, k, ptr(order), ptr(offsets), n_segments, ptr(out), out.stride(0),
+                                     stream_ptr(x.device)), "mmk_segment_mean_f32")
+    return out
 
 
 def _rows(x: torch.Tensor) -> torch.Tensor:
