@@ -218,6 +218,45 @@ int mmk_nn_components_i64(const int64_t* nearest, int64_t n, int64_t* labels, in
 int mmk_segment_mean_f32(const float* x, int64_t x_row_stride, int64_t n, int32_t k, const int64_t* order, const int64_t* offsets,
                          int64_t n_segments, float* out, int64_t out_row_stride, mmk_stream_t stream);
 
+/* The k nearest frames and the components of a graph (mimikit/extract/clusters.py:27-98 QCluster).
+ *
+ * mmk_nn_topk_f32: for `rows` query frames x and m corpus frames y over k bins, with a scale per query, a scale and a shift per corpus frame,
+ *     key[r, j] = clamp((<x_r, y_j> * qscale[r]) * cscale[j] + cshift[j], key_min, key_max)        (three roundings after the sum; limits of
+ *     -inf and +inf: no clamp)
+ * index[r][0 .. t) (int64) = the t corpus frames of the largest keys, in falling key order, equal keys in rising index order; key[r][0 .. t)
+ * those keys.  Cosine similarity: the two inverse norms of mmk_inv_row_norm_f32, a shift of 0 and the limits -1 and 1 - with t = 1 the index
+ * and key are those of mmk_nn_cosine_f32 / mmk_nn_cosine_self_f32.  Euclidean distance: scales of 1, no limits and cshift =
+ * mmk_half_neg_sqnorm_f32(y) = -|y_j|^2 / 2: the largest key is the smallest distance.  self_exclude != 0: the corpus IS the
+ * queries (y == x, the same stride, m == rows, or MMK_ERR_INVALID) and frame r is left out of row r.  Where a row has fewer than t
+ * candidates the slots behind them hold index -1 and key -inf.  The same tile walk, order of the sum over k and span / merge scheme as
+ * mmk_nn_cosine_f32: a lane keeps its rows' t best in registers across a span, one list per row and span goes to `workspace`
+ * (mmk_nn_topk_workspace_bytes(rows, m, t) = 8 t bytes per row and span, never O(rows * m)), a second launch joins the spans in rising span
+ * order.  No atomics: repeated calls agree bit for bit.  t > MMK_NN_TOPK_MAX, m >= 2^31 - MMK_NN_SPAN: MMK_ERR_UNSUPPORTED; rows, m, k or
+ * t < 1: MMK_ERR_INVALID; a workspace that is too small: MMK_ERR_WORKSPACE.  NaN and inf in the inputs are not handled.
+ *
+ * mmk_half_neg_sqnorm_f32: out[j] = -|y_j|^2 / 2, the squares added in fp64 in one fixed order and rounded to fp32 once.
+ *
+ * mmk_edge_components_i64: labels[i] (int64) = the number of the connected component of node i in the undirected graph of the n_edges edges
+ * (src[e], dst[e]) over n nodes, components numbered by rising smallest member; *n_components (one int64 on the device) = their count.
+ * Self-loops, repeated and reversed edges are allowed, n_edges may be 0 (src and dst may then be NULL), a node without an edge is a
+ * component of its own; an edge with an endpoint outside [0, n) is the caller's error and is left out.  Min-hooking with an integer
+ * atomicMin and pointer jumping until a round changes nothing; the fixed point is every node's smallest fellow member in whatever order the
+ * atomics land, so two calls give the same labels.  THE CALL WAITS FOR THE STREAM once per four rounds to read its changed-flag: it cannot be
+ * captured into a graph.  Workspace: mmk_edge_components_workspace_bytes(n) = 12 bytes per node, 4 per 256 nodes and 4.  n < 1,
+ * n_edges < 0: MMK_ERR_INVALID; n >= 2^31: MMK_ERR_UNSUPPORTED.
+ *
+ * Raw pointers and strides, 4-byte alignment of the float data (8 of the int64 data) is enough, tails are masked here, nothing but the stated
+ * outputs and workspace is written. */
+#define MMK_NN_TOPK_MAX 16
+size_t mmk_nn_topk_workspace_bytes(int64_t rows, int64_t m, int32_t t);
+int mmk_nn_topk_f32(const float* x, int64_t x_row_stride, const float* qscale, int64_t rows, const float* y, int64_t y_row_stride,
+                    const float* cscale, const float* cshift, float key_min, float key_max, int64_t m, int32_t k, int32_t t, int32_t self_exclude,
+                    int64_t* index, float* key, void* workspace, size_t workspace_bytes, mmk_stream_t stream);
+int mmk_half_neg_sqnorm_f32(const float* y, int64_t y_row_stride, int64_t rows, int32_t k, float* out, mmk_stream_t stream);
+size_t mmk_edge_components_workspace_bytes(int64_t n);
+int mmk_edge_components_i64(const int64_t* src, const int64_t* dst, int64_t n_edges, int64_t n, int64_t* labels, int64_t* n_components,
+                            void* workspace, size_t workspace_bytes, mmk_stream_t stream);
+
 /* STFT.torch_func with coordinate="mag" == MagSpec.torch_func
  * (mimikit/features/functionals.py:507-524, :576-606): periodic-Hann framed
  * real FFT magnitudes.  x: (batch, n_samples) rows `x_row_stride` apart,

@@ -22,6 +22,20 @@
 //   segment_mean out[s] = the mean of the rows x[order[offsets[s] .. offsets[s + 1])]: one workgroup per segment, a lane per bin (consecutive
 //                lanes on consecutive bins: every member row is read coalesced), members added in the order given in fp64, one division and
 //                ONE rounding to fp32.
+//   edge components   (mmk_edge_components_i64; QCluster's graph, mimikit/extract/clusters.py:83) the connected components of an undirected edge
+//                list over n nodes - self-loops, repeated and reversed edges allowed, a node without an edge is a singleton - numbered the
+//                same way.  parent[i] starts at i and only ever falls, and it only ever takes the number of a node of i's own component:
+//                  ec_hook_kernel     a thread per edge (u, v): a = parent[u], b = parent[v]; if they differ, atomicMin(parent[max(a, b)],
+//                                     min(a, b)) and the same on the endpoint whose parent was the larger, and the round's flag is raised
+//                  ec_jump_kernel     parent[i] <- parent[parent[i]] (twice per round), raising the flag where that moves parent[i]
+//                A round that leaves the flag down has written nothing, so it has read ONE state in which every edge joins two nodes of
+//                the same parent and every parent is its own parent: parent is constant on a component, at most its smallest member
+//                (parent[i] <= i) and a member of it - it IS the smallest member, whatever the order the atomics landed in (integer
+//                minima; no float goes through an atomic).  The values are bounded below, so the rounds end.  Convergence is found by
+//                the flag, not by a proven count: the entry point runs kEcGroup rounds, lowers the flag before the last of them, copies
+//                it to the host and waits for the stream - one synchronisation per group of rounds, which is why this entry point (alone
+//                in this file) cannot be captured into a graph.  The numbering is cc_count / cc_scan / cc_rank / cc_label above with
+//                rep = parent and cmin = the identity.  Three int32 arrays of n, one of the blocks and the flag as workspace.
 // No workgroup waits for another, no scratch, and two calls give the same bits.  NaN in the inputs is not handled.
 #include "mmk_common.h"
 
@@ -131,6 +145,42 @@ __global__ __launch_bounds__(256) void segment_mean_kernel(const float* __restri
 
 static int cc_blocks(int64_t n) { return (int)((n + kCcThreads - 1) / kCcThreads); }
 
+// ---- components of an undirected edge list ----------------------------------------------------------------------------------------------
+constexpr int kEcGroup = 4;       // rounds between two looks at the flag
+
+__global__ __launch_bounds__(kCcThreads) void ec_init_kernel(int32_t n, int32_t* __restrict__ parent, int32_t* __restrict__ ident) {
+  const int64_t i = (int64_t)blockIdx.x * kCcThreads + threadIdx.x;
+  if (i >= n) return;
+  parent[i] = (int32_t)i;
+  ident[i] = (int32_t)i;
+}
+
+// (an endpoint outside [0, n) is the caller's error: the edge is left out, never used as an address)
+__global__ __launch_bounds__(kCcThreads) void ec_hook_kernel(const int64_t* __restrict__ src, const int64_t* __restrict__ dst, int64_t n_edges,
+                                                            int32_t n, int32_t* parent, int32_t* __restrict__ changed) {
+  const int64_t e = (int64_t)blockIdx.x * kCcThreads + threadIdx.x;
+  if (e >= n_edges) return;
+  const int64_t u = src[e], v = dst[e];
+  if (u < 0 || v < 0 || u >= n || v >= n || u == v) return;
+  const int32_t a = parent[u], b = parent[v];
+  if (a == b) return;
+  const int32_t lo = min(a, b), hi = max(a, b);
+  atomicMin(&parent[hi], lo);
+  atomicMin(&parent[a > b ? u : v], lo);
+  *changed = 1;
+}
+
+__global__ __launch_bounds__(kCcThreads) void ec_jump_kernel(int32_t n, int32_t* parent, int32_t* __restrict__ changed) {
+  const int64_t i = (int64_t)blockIdx.x * kCcThreads + threadIdx.x;
+  if (i >= n) return;
+  const int32_t p = parent[i];
+  const int32_t g = parent[p];
+  if (g != p) {                   // (g < p: parents only fall)
+    atomicMin(&parent[i], g);
+    *changed = 1;
+  }
+}
+
 }  // namespace mmk
 
 extern "C" size_t mmk_nn_components_workspace_bytes(int64_t n) {
@@ -181,6 +231,68 @@ extern "C" int mmk_nn_components_i64(const int64_t* nearest, int64_t n, int64_t*
   hipLaunchKernelGGL(cc_rank_kernel, grid, wg, 0, st, rep, cmin, counts, nn, rank);
   MMK_HIP(hipGetLastError());
   hipLaunchKernelGGL(cc_label_kernel, grid, wg, 0, st, rep, cmin, rank, nn, labels);
+  MMK_HIP(hipGetLastError());
+  return MMK_OK;
+}
+
+extern "C" size_t mmk_edge_components_workspace_bytes(int64_t n) {
+  using namespace mmk;
+  if (n < 1 || n > 0x7fffffffLL) return 0;
+  return ((size_t)3 * (size_t)n + (size_t)cc_blocks(n) + 1) * sizeof(int32_t);
+}
+
+extern "C" int mmk_edge_components_i64(const int64_t* src, const int64_t* dst, int64_t n_edges, int64_t n, int64_t* labels,
+                                       int64_t* n_components, void* workspace, size_t workspace_bytes, mmk_stream_t stream) {
+  using namespace mmk;
+  if (n < 1) return fail(MMK_ERR_INVALID, "edge_components: n = %lld < 1 (nodes)", (long long)n);
+  if (n_edges < 0) return fail(MMK_ERR_INVALID, "edge_components: n_edges = %lld < 0", (long long)n_edges);
+  if (n > 0x7fffffffLL) return fail(MMK_ERR_UNSUPPORTED, "edge_components: n = %lld nodes: indices are kept in 32 bits", (long long)n);
+  if ((n_edges + kCcThreads - 1) / kCcThreads > 0x7fffffffLL)
+    return fail(MMK_ERR_UNSUPPORTED, "edge_components: %lld edges are more than one launch takes", (long long)n_edges);
+  if ((n_edges > 0 && (!src || !dst)) || !labels || !n_components || !workspace)
+    return fail(MMK_ERR_INVALID, "edge_components: bad arguments (null pointer)");
+  if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(labels) |
+       reinterpret_cast<uintptr_t>(n_components)) & 7)
+    return fail(MMK_ERR_INVALID, "edge_components: src, dst, labels and n_components must be 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(workspace) & 3) return fail(MMK_ERR_INVALID, "edge_components: the workspace must be 4-byte aligned");
+  if (workspace_bytes < mmk_edge_components_workspace_bytes(n))
+    return fail(MMK_ERR_WORKSPACE, "edge_components: the workspace has %zu bytes, %zu are needed", workspace_bytes,
+                mmk_edge_components_workspace_bytes(n));
+  hipStream_t st = (hipStream_t)stream;
+  const int32_t nn = (int32_t)n;
+  const int blocks = cc_blocks(n);
+  int32_t* w = static_cast<int32_t*>(workspace);
+  int32_t* parent = w;
+  int32_t* ident = w + n;
+  int32_t* rank = w + 2 * n;
+  int32_t* counts = w + 3 * n;
+  int32_t* changed = counts + blocks;
+  const dim3 grid((unsigned)blocks), wg(kCcThreads);
+  const dim3 egrid((unsigned)((n_edges + kCcThreads - 1) / kCcThreads));
+  hipLaunchKernelGGL(ec_init_kernel, grid, wg, 0, st, nn, parent, ident);
+  MMK_HIP(hipGetLastError());
+  for (bool again = n_edges > 0; again;) {
+    for (int r = 0; r < kEcGroup; ++r) {
+      if (r == kEcGroup - 1) MMK_HIP(hipMemsetAsync(changed, 0, sizeof(int32_t), st));
+      hipLaunchKernelGGL(ec_hook_kernel, egrid, wg, 0, st, src, dst, n_edges, nn, parent, changed);
+      MMK_HIP(hipGetLastError());
+      for (int jump = 0; jump < 2; ++jump) {
+        hipLaunchKernelGGL(ec_jump_kernel, grid, wg, 0, st, nn, parent, changed);
+        MMK_HIP(hipGetLastError());
+      }
+    }
+    int32_t flag = 0;
+    MMK_HIP(hipMemcpyAsync(&flag, changed, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    MMK_HIP(hipStreamSynchronize(st));
+    again = flag != 0;
+  }
+  hipLaunchKernelGGL(cc_count_kernel, grid, wg, 0, st, parent, ident, nn, counts);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(cc_scan_kernel, dim3(1), wg, 0, st, counts, (int32_t)blocks, n_components);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(cc_rank_kernel, grid, wg, 0, st, parent, ident, counts, nn, rank);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(cc_label_kernel, grid, wg, 0, st, parent, ident, rank, nn, labels);
   MMK_HIP(hipGetLastError());
   return MMK_OK;
 }

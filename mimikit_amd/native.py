@@ -170,6 +170,11 @@ _SIGNATURES = {
     "mmk_nn_components_workspace_bytes": (C.c_size_t, [i64]),
     "mmk_nn_components_i64": (i32, [vp, i64, vp, vp, vp, C.c_size_t, vp]),
     "mmk_segment_mean_f32": (i32, [vp, i64, i64, i32, vp, vp, i64, vp, i64, vp]),
+    "mmk_nn_topk_workspace_bytes": (C.c_size_t, [i64, i64, i32]),
+    "mmk_nn_topk_f32": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, f32, f32, i64, i32, i32, i32, vp, vp, vp, C.c_size_t, vp]),
+    "mmk_half_neg_sqnorm_f32": (i32, [vp, i64, i64, i32, vp, vp]),
+    "mmk_edge_components_workspace_bytes": (C.c_size_t, [i64]),
+    "mmk_edge_components_i64": (i32, [vp, vp, i64, i64, vp, vp, vp, C.c_size_t, vp]),
     "mmk_stft_n_frames": (i64, [i64, i32, i32, i32]),
     "mmk_stft_mag_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, vp, vp]),
     "mmk_stft_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, i32, i32, vp, vp]),
@@ -597,6 +602,83 @@ def segment_mean(x: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor) ->
     check(lib().mmk_segment_mean_f32(ptr(x), x.stride(0), n, k, ptr(order), ptr(offsets), n_segments, ptr(out), out.stride(0),
                                      stream_ptr(x.device)), "mmk_segment_mean_f32")
     return out
+
+
+# include/mmk.h: MMK_NN_TOPK_MAX - the neighbours per row a lane of the k-best kernel keeps in registers (csrc/qcluster.hip)
+NN_TOPK_MAX = 16
+NN_TOPK_METRICS = ("euclidean", "cosine")
+
+
+def nn_topk(x: torch.Tensor, y: torch.Tensor, t: int, metric: str = "euclidean", self_exclude: bool = False):
+    """x (rows, k), y (M, k), 1 <= t <= NN_TOPK_MAX -> (index (rows, t) int64, key (rows, t) fp32): per row of x the t nearest rows of y
+    under `metric`, nearest first, equal keys by rising index; slots past the last candidate hold -1 / -inf.  key is the cosine similarity
+    ("cosine": clamped to [-1, 1], with t = 1 exactly nn_cosine / nn_cosine_self) or <x, y> - |y|^2 / 2 ("euclidean": the largest key is the smallest distance; |x - y|^2 = |x|^2 - 2 key).  With
+    ``self_exclude`` y must be x itself and row r is left out of its own list.  The (rows, M) matrix is never formed: the workspace is
+    8 t bytes per row and span of NN_SPAN rows of y, allocated in one piece - this wrapper does not walk the rows in blocks (268 MB at
+    rows = M = 65536, t = 16)"""
+    same = y is x
+    x = _nnn_frames(x, 2, "nn_topk")
+    y = x if self_exclude and same else _nnn_frames(y, 2, "nn_topk")
+    if metric not in NN_TOPK_METRICS:
+        raise NotImplementedError(f"nn_topk: metric={metric!r} is not on the HIP path ({', '.join(NN_TOPK_METRICS)})")
+    rows, k = x.shape
+    m = y.shape[0]
+    if y.shape[1] != k:
+        raise ValueError(f"nn_topk: the queries have {k} bins, the corpus {y.shape[1]}")
+    if min(rows, m, k) < 1:
+        raise ValueError(f"nn_topk: empty input (rows={rows}, M={m}, bins={k})")
+    t = int(t)
+    if t < 1:
+        raise ValueError(f"nn_topk: t = {t} < 1")
+    if t > NN_TOPK_MAX:
+        raise NotImplementedError(f"nn_topk: t = {t} neighbours per row, the limit is {NN_TOPK_MAX} (NN_TOPK_MAX)")
+    if self_exclude and (y.data_ptr() != x.data_ptr() or y.shape != x.shape or y.stride() != x.stride()):
+        raise ValueError("nn_topk: self_exclude takes y = x, the same rows")
+    dev = x.device
+    if metric == "cosine":
+        qscale = inv_row_norm(x)
+        cscale = qscale if self_exclude else inv_row_norm(y)
+        cshift = torch.zeros((m,), dtype=torch.float32, device=dev)
+        lo, hi = -1.0, 1.0
+    else:
+        lo, hi = float("-inf"), float("inf")
+        qscale = torch.ones((max(rows, m),), dtype=torch.float32, device=dev)
+        cscale = qscale
+        cshift = torch.empty((m,), dtype=torch.float32, device=dev)
+        check(lib().mmk_half_neg_sqnorm_f32(ptr(y), y.stride(0), m, k, ptr(cshift), stream_ptr(dev)), "mmk_half_neg_sqnorm_f32")
+    index = torch.empty((rows, t), dtype=torch.int64, device=dev)
+    key = torch.empty((rows, t), dtype=torch.float32, device=dev)
+    n_work = lib().mmk_nn_topk_workspace_bytes(rows, m, t)
+    work = torch.empty((n_work // 4,), dtype=torch.float32, device=dev)
+    check(lib().mmk_nn_topk_f32(ptr(x), x.stride(0), ptr(qscale), rows, ptr(y), y.stride(0), ptr(cscale), ptr(cshift), lo, hi, m, k, t,
+                                1 if self_exclude else 0, ptr(index), ptr(key), ptr(work), n_work, stream_ptr(dev)), "mmk_nn_topk_f32")
+    return index, key
+
+
+def edge_components(src: torch.Tensor, dst: torch.Tensor, n: int):
+    """src, dst (n_edges,) int64 with entries in [0, n) -> (labels (n,) int64, n_components () int64, on the device): the connected
+    components of the undirected graph of those edges over n nodes, numbered by rising smallest member.  The call waits for the stream
+    once per four rounds of hooking (it reads a changed-flag back)"""
+    for name, e in (("src", src), ("dst", dst)):
+        if not isinstance(e, torch.Tensor):
+            raise TypeError(f"edge_components: expected a torch.Tensor for {name}, got {type(e)}")
+        if e.dtype != torch.int64:
+            raise TypeError(f"edge_components takes int64 indices, {name} is {e.dtype}")
+        if e.dim() != 1:
+            raise ValueError(f"edge_components: expected (n_edges,) indices, {name} has shape {tuple(e.shape)}")
+    n = int(n)
+    if src.shape != dst.shape or n < 1:
+        raise ValueError(f"edge_components: src {tuple(src.shape)}, dst {tuple(dst.shape)}, n = {n}")
+    require_device(src, dst)
+    src, dst = src.contiguous(), dst.contiguous()
+    labels = torch.empty((n,), dtype=torch.int64, device=src.device)
+    count = torch.empty((), dtype=torch.int64, device=src.device)
+    n_work = lib().mmk_edge_components_workspace_bytes(n)
+    work = torch.empty((n_work // 4,), dtype=torch.int32, device=src.device)
+    n_edges = src.shape[0]
+    check(lib().mmk_edge_components_i64(ptr(src) if n_edges else None, ptr(dst) if n_edges else None, n_edges, n, ptr(labels), ptr(count),
+                                        ptr(work), n_work, stream_ptr(src.device)), "mmk_edge_components_i64")
+    return labels, count
 
 
 def _rows(x: torch.Tensor) -> torch.Tensor:
