@@ -1,6 +1,8 @@
 """CPU restatement of the reference's generate-path algorithms (TEST INFRASTRUCTURE ONLY).
 
-This file is the ORACLE of the repo: plain fp32 PyTorch/numpy on the host, no
+This file is the ORACLE of the repo: plain PyTorch/numpy on the host (fp32 with fp32
+weights, as the reference runs; the network functions compute in the dtype of the state
+dict they are given, so float64 weights give a float64 run of the same function), no
 dependence on the product package, each function citing the reference lines it
 restates (paths relative to the reference root, ``mimikit/...``).  It executes the
 reference's ALGORITHM literally -- in particular the naive WaveNet generation that
@@ -19,6 +21,7 @@ Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s cpu_baseline leg
 import this module.  All functions take a ``state_dict``-like mapping with the
 reference's parameter names.
 """
+import contextlib
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -162,10 +165,39 @@ def resample(x: torch.Tensor, orig_sr: int, target_sr: int, lowpass_filter_width
 # ---------------------------------------------------------------------------
 # head: MLP with learned temperature + categorical sampler
 # ---------------------------------------------------------------------------
+# the three a run may swap (``activation_formulas``): the gates of the WaveNet layers and of the recurrent cells, the MLP heads' Mish
+_FORMULAS = {"sigmoid": torch.sigmoid, "tanh": torch.tanh, "mish": F.mish}
+
+
+def _sigmoid(v):
+    return _FORMULAS["sigmoid"](v)
+
+
+def _tanh(v):
+    return _FORMULAS["tanh"](v)
+
+
+def _mish(v):
+    return _FORMULAS["mish"](v)
+
+
 # the members of mimikit's ActivationEnum (modules/activations.py:25-39) that are plain element-wise functions: nn.<name>() of torch, Abs / Sin / Cos of
 # the reference's own three-line modules (:66-78)
-ACTIVATIONS = {"Tanh": torch.tanh, "Sigmoid": torch.sigmoid, "Mish": F.mish, "ReLU": torch.relu, "Softplus": F.softplus, "Identity": lambda v: v,
+ACTIVATIONS = {"Tanh": _tanh, "Sigmoid": _sigmoid, "Mish": _mish, "ReLU": torch.relu, "Softplus": F.softplus, "Identity": lambda v: v,
                "Abs": torch.abs, "Sin": torch.sin, "Cos": torch.cos}
+
+
+@contextlib.contextmanager
+def activation_formulas(sigmoid=None, tanh=None, mish=None):
+    """Within the block, the sigmoid / tanh gates (WaveNet layers, LSTM / GRU / RNN cells) and the Mish of the MLP heads are evaluated by
+    the given element-wise functions instead of torch's: a reference-side measurement of what another formula of the same function
+    costs (tests/net_refs.py).  The learned-temperature sigmoid of ``mlp_logits`` belongs to the sampler and is not swapped."""
+    old = dict(_FORMULAS)
+    _FORMULAS.update({k: f for k, f in (("sigmoid", sigmoid), ("tanh", tanh), ("mish", mish)) if f is not None})
+    try:
+        yield
+    finally:
+        _FORMULAS.update(old)
 
 
 def mlp_raw(sd: SD, prefix: str, x: torch.Tensor, n_hidden: int = 0, act: str = "Mish", n_dropouts: int = 0) -> torch.Tensor:
@@ -187,7 +219,7 @@ def mlp_logits(raw: torch.Tensor, min_temp: Optional[float] = 1e-4) -> torch.Ten
     if min_temp is None:
         return raw
     temp = torch.sigmoid(raw[..., -1:])
-    return raw[..., :-1] / torch.maximum(temp, torch.tensor(min_temp))
+    return raw[..., :-1] / torch.maximum(temp, torch.tensor(min_temp, dtype=raw.dtype))
 
 
 def categorical(logits: torch.Tensor, temperature=None, uniforms: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -197,12 +229,12 @@ def categorical(logits: torch.Tensor, temperature=None, uniforms: Optional[torch
     (softmax(logits / T)) at caller-supplied uniforms, which is what the device kernel does."""
     if temperature is None:
         return logits.argmax(dim=-1)
-    t = torch.as_tensor(temperature, dtype=torch.float32).reshape(-1, *([1] * (logits.dim() - 1)))
+    t = torch.as_tensor(temperature, dtype=logits.dtype).reshape(-1, *([1] * (logits.dim() - 1)))
     l = logits / t
     l = l - l.max(dim=-1, keepdim=True).values
     e = torch.exp(l)
     cdf = torch.cumsum(e, dim=-1)
-    target = uniforms.reshape(*logits.shape[:-1], 1).to(torch.float32) * cdf[..., -1:]
+    target = uniforms.reshape(*logits.shape[:-1], 1).to(logits.dtype) * cdf[..., -1:]
     hit = (cdf > target) & (e > 0)
     first = torch.where(hit.any(-1), hit.float().argmax(-1), (e > 0).float().cumsum(-1).argmax(-1))
     return first
@@ -229,7 +261,8 @@ def wavenet_window_forward(sd: SD, inputs: Tuple[torch.Tensor, ...], kernels: Se
                            gated: bool = True, layerwise_inputs: bool = False,
                            res_layers: Optional[Sequence[bool]] = None, affine: bool = False,
                            cond_classes: Optional[Sequence[int]] = None, heads_n_hidden: Optional[Sequence[int]] = None,
-                           act_f: str = "Tanh", act_g: str = "Sigmoid", mlp_act: str = "Mish", mlp_dropouts: int = 0):
+                           act_f: str = "Tanh", act_g: str = "Sigmoid", mlp_act: str = "Mish", mlp_dropouts: int = 0,
+                           every_position: bool = False):
     """Full-window eval forward (wavenet_v2.py:276-293 with WNLayer.forward :131-176, pad_side=0):
     returns the RAW head outputs (B, 1, q+1) of the FIRST computable position (eval_slice, :273).
     ``groups`` applies to the dilated convolutions only (:93); ``head`` "linear" / "linear_abs" is the
@@ -243,16 +276,18 @@ def wavenet_window_forward(sd: SD, inputs: Tuple[torch.Tensor, ...], kernels: Se
     ``cond_classes[j]`` > 0: conditioning input j is a stream of class indices through an EmbeddingIO (from_config :231-234 builds
     the module of EVERY input from its spec); ``heads_n_hidden`` (one entry per target): the network has that many output modules
     (:240-243) and the function returns the tuple of their raw outputs (:293).  ``act_f`` / ``act_g``: Config.act_f / act_g by their
-    ActivationEnum names (modules/activations.py:25-39; WNLayer.forward :151 / :163 applies whatever modules they name)."""
+    ActivationEnum names (modules/activations.py:25-39; WNLayer.forward :151 / :163 applies whatever modules they name).
+    Everything is computed in the dtype of the state dict.  ``every_position``: the outputs of ALL computable positions of a window longer
+    than rf, (B, T - rf + 1, q+1) - row j is the output for the window that starts at j: a teacher-forced run of many steps as one forward."""
     f_act, g_act = ACTIVATIONS[act_f], ACTIVATIONS[act_g]
     if embedding:
         h = F.embedding(inputs[0], sd["input_modules.0.0.weight"])
     else:
-        h = F.linear(inputs[0], sd["input_modules.0.0.weight"], sd["input_modules.0.0.bias"])
+        h = F.linear(inputs[0].to(sd["input_modules.0.0.weight"].dtype), sd["input_modules.0.0.weight"], sd["input_modules.0.0.bias"])
     h = h.transpose(1, 2).contiguous()
     x0 = h
     conds = [(F.embedding(inputs[1 + j], sd[f"input_modules.{1 + j}.0.weight"]) if cond_classes and cond_classes[j] > 0 else
-              F.linear(inputs[1 + j], sd[f"input_modules.{1 + j}.0.weight"], sd[f"input_modules.{1 + j}.0.bias"]))
+              F.linear(inputs[1 + j].to(sd[f"input_modules.{1 + j}.0.weight"].dtype), sd[f"input_modules.{1 + j}.0.weight"], sd[f"input_modules.{1 + j}.0.bias"]))
              .transpose(1, 2).contiguous() for j in range(n_cond)]
     skips = None
     n_layers = len(kernels)
@@ -293,7 +328,9 @@ def wavenet_window_forward(sd: SD, inputs: Tuple[torch.Tensor, ...], kernels: Se
         if layerwise_inputs:
             h = h + x0[..., -h.size(-1):]
         conds = [c[:, :, cause:] for c in conds]
-    y = (skips if has_skips else h).transpose(1, 2).contiguous()[:, 0:1]
+    y = (skips if has_skips else h).transpose(1, 2).contiguous()
+    if not every_position:
+        y = y[:, 0:1]
     if heads_n_hidden is not None:
         return tuple(mlp_raw(sd, f"output_modules.{k}.estimator.0.", y, n, mlp_act, mlp_dropouts) for k, n in enumerate(heads_n_hidden))
     if head == "mlp":
@@ -307,7 +344,7 @@ def wavenet_generate_frames(sd: SD, prompt: torch.Tensor, n_steps: int, kernels,
     (magspec_io): every step's (B, 1, bins) output is written back as the next input frame"""
     rf = wavenet_rf(kernels, dilations)
     prior = prompt.size(1)
-    x = torch.cat([prompt, torch.zeros(prompt.size(0), n_steps, prompt.size(2))], dim=1)
+    x = torch.cat([prompt, torch.zeros(prompt.size(0), n_steps, prompt.size(2), dtype=prompt.dtype)], dim=1)
     for t in range(prior, prior + n_steps):
         x[:, t:t + 1] = wavenet_window_forward(sd, (x[:, t - rf:t],), kernels, dilations, embedding=False, **arch)
     return x
@@ -365,9 +402,9 @@ def wavenet_generate_streams(sd: SD, prompts: Sequence[torch.Tensor], n_steps: i
 # ---------------------------------------------------------------------------
 # SampleRNN
 # ---------------------------------------------------------------------------
-def _linearize(q: torch.Tensor, class_size: int) -> torch.Tensor:
-    """Linearizer, modules/io.py:106-112"""
-    return ((q.float() / class_size) - .5) * 2
+def _linearize(q: torch.Tensor, class_size: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Linearizer, modules/io.py:106-112 (``q.float()`` there; here in the dtype of the weights it meets)"""
+    return ((q.to(dtype) / class_size) - .5) * 2
 
 
 def _rnn_cell(kind: str, sd: SD, p: str, x: torch.Tensor, state, layer: int = 0):
@@ -378,19 +415,19 @@ def _rnn_cell(kind: str, sd: SD, p: str, x: torch.Tensor, state, layer: int = 0)
         h, c = state
         g = F.linear(x, w_ih, b_ih) + F.linear(h, w_hh, b_hh)
         i, f, gg, o = g.chunk(4, dim=-1)
-        c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
-        h = torch.sigmoid(o) * torch.tanh(c)
+        c = _sigmoid(f) * c + _sigmoid(i) * _tanh(gg)
+        h = _sigmoid(o) * _tanh(c)
         return h, (h, c)
     if kind == "gru":
         h = state
         gi, gh = F.linear(x, w_ih, b_ih), F.linear(h, w_hh, b_hh)
         i_r, i_z, i_n = gi.chunk(3, dim=-1)
         h_r, h_z, h_n = gh.chunk(3, dim=-1)
-        r, z = torch.sigmoid(i_r + h_r), torch.sigmoid(i_z + h_z)
-        n = torch.tanh(i_n + r * h_n)
+        r, z = _sigmoid(i_r + h_r), _sigmoid(i_z + h_z)
+        n = _tanh(i_n + r * h_n)
         h = (h - n) * z + n
         return h, h
-    h = torch.tanh(F.linear(x, w_ih, b_ih) + F.linear(state, w_hh, b_hh))
+    h = _tanh(F.linear(x, w_ih, b_ih) + F.linear(state, w_hh, b_hh))
     return h, h
 
 
@@ -446,16 +483,17 @@ class SampleRNNOracle:
         frames = (frames,) if isinstance(frames, torch.Tensor) else tuple(frames)
         classes = self.in_classes or (self.q,) * len(frames)
         M = len(frames)
+        dtype = sd[p + f"heads.0.{leaf}weight"].dtype
         if self.inputs_mode == "sum":
-            w = torch.ones(M)
+            w = torch.ones(M, dtype=dtype)
         elif self.inputs_mode == "mean":
-            w = torch.ones(M) / M
+            w = torch.ones(M, dtype=dtype) / M
         else:
             w = torch.softmax(sd[p + "weights"], dim=0)
 
         def head(m):
             wt = sd[p + f"heads.{m}.{leaf}weight"]
-            return F.linear(_linearize(frames[m], classes[m]), wt.reshape(self.H, -1), sd[p + f"heads.{m}.{leaf}bias"])
+            return F.linear(_linearize(frames[m], classes[m], wt.dtype), wt.reshape(self.H, -1), sd[p + f"heads.{m}.{leaf}bias"])
 
         if M == 1 and self.in_classes is None:
             return head(0)            # (one input: every mode weights it by 1)
@@ -471,8 +509,8 @@ class SampleRNNOracle:
             x = x + upper
         if self.hidden[i] is None:
             init = getattr(torch, self.h0)
-            self.hidden[i] = [(init(x.size(0), self.H), init(x.size(0), self.H)) if self.kind == "lstm" else init(x.size(0), self.H)
-                              for _ in range(self.n_rnn)]
+            self.hidden[i] = [(init(x.size(0), self.H, dtype=x.dtype), init(x.size(0), self.H, dtype=x.dtype)) if self.kind == "lstm" else
+                              init(x.size(0), self.H, dtype=x.dtype) for _ in range(self.n_rnn)]
         for k in range(self.n_rnn):      # layer k's input is layer k-1's output at this time step
             x, self.hidden[i][k] = _rnn_cell(self.kind, sd, p + "rnn.", x, self.hidden[i][k], layer=k)
         up = self.fs[i] // (self.fs[i + 1] if i < len(self.fs) - 2 else 1)
@@ -562,16 +600,16 @@ def _bilstm(sd: SD, p: str, x: torch.Tensor, state=None):
     D = sd[p + "weight_hh_l0"].shape[1]
     outs, hs, cs = [], [], []
     for d, sfx in enumerate(("", "_reverse")):
-        h = torch.zeros(B, D) if state is None else state[0][d]
-        c = torch.zeros(B, D) if state is None else state[1][d]
+        h = torch.zeros(B, D, dtype=x.dtype) if state is None else state[0][d]
+        c = torch.zeros(B, D, dtype=x.dtype) if state is None else state[1][d]
         seq = range(T) if d == 0 else range(T - 1, -1, -1)
         ys = [None] * T
         for t in seq:
             g = F.linear(x[:, t], sd[p + "weight_ih_l0" + sfx], sd[p + "bias_ih_l0" + sfx]) + \
                 F.linear(h, sd[p + "weight_hh_l0" + sfx], sd[p + "bias_hh_l0" + sfx])
             i, f, gg, o = g.chunk(4, dim=-1)
-            c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
-            h = torch.sigmoid(o) * torch.tanh(c)
+            c = _sigmoid(f) * c + _sigmoid(i) * _tanh(gg)
+            h = _sigmoid(o) * _tanh(c)
             ys[t] = h
         outs.append(torch.stack(ys, 1))
         hs.append(h)
@@ -592,7 +630,9 @@ def s2s_step(sd: SD, x: torch.Tensor, hop: int, out_abs: bool = True, downsampli
     return_raw the head's outputs before the learned-temperature division are returned beside the classes."""
     D = sd["enc.fc_out.weight"].shape[0]
     if "input_module.heads.0.0.weight" in sd:
-        x = F.embedding(x, sd["input_module.heads.0.0.weight"]) * torch.ones(())
+        x = F.embedding(x, sd["input_module.heads.0.0.weight"]) * torch.ones((), dtype=sd["enc.fc_out.weight"].dtype)
+    else:
+        x = x.to(sd["enc.fc_out.weight"].dtype)
     n_enc = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("enc.lstm."))
     n_dec = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("dec.lstm."))
     hidden = None
@@ -622,7 +662,7 @@ def s2s_step(sd: SD, x: torch.Tensor, hop: int, out_abs: bool = True, downsampli
     if mlp + "fc.0.weight" in sd:
         n_hidden = max(int(k[len(mlp) + 3:].split(".")[0]) for k in sd if k.startswith(mlp + "fc.")) // 2 - 1
         raw = mlp_raw(sd, mlp, z, n_hidden)
-        classes = categorical(mlp_logits(raw, min_temp)) * torch.ones(())
+        classes = categorical(mlp_logits(raw, min_temp)) * torch.ones((), dtype=raw.dtype)
         return (classes, raw) if return_raw else classes
     out = F.linear(z, sd["output_module.heads.0.0.weight"], sd["output_module.heads.0.0.bias"])
     return out.abs() if out_abs else out

@@ -1,0 +1,136 @@
+"""The references of tests/net_refs.py against each other, on the host: for every case of test_gpu_networks_f64.py, on the fp32 oracle's own
+free-running history, the float64 run is the same function as the fp32 one, both fp32 runs lie inside the envelope, the oracle's own picks
+pass check_picks on every step, and each of the four defects leaves the envelope.  And the kernels' activation formulas
+(csrc/mmk_common.h) against float64."""
+import functools
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import net_refs as R
+
+torch.set_grad_enabled(False)
+IDS = [f"{net}-{case.id}" for net, case in R.ALL_CASES]
+
+
+@functools.lru_cache(maxsize=None)
+def _run(index):
+    case = R.ALL_CASES[index][1]
+    prompt, conds = case.inputs()
+    hist = R.free_run(case, prompt, conds)
+    return case, hist, conds, R.envelope(hist, case, conds)
+
+
+@pytest.mark.parametrize("index", range(len(R.ALL_CASES)), ids=IDS)
+def test_fp32_oracle_lies_inside_its_own_envelope(index):
+    case, hist, conds, env = _run(index)
+    rows = case.rows()
+    R64, E = env.R64[:, rows], env.E[:, rows]
+    assert env.R64.dtype == torch.float64 and env.R64.shape[:2] == (case.clips, case.n)
+    scale = float(env.R64.abs().max())
+    worst = float((env.R32.double() - env.R64).abs().max())
+    assert worst <= 1e-5 * scale, f"the float64 run is another function: |R32 - R64| up to {worst:.3e} at an output scale of {scale:.3e}"
+    tol_max, tol_rms = R.tolerance(E)
+    assert tol_max > 0
+    for name, run in (("R32", env.R32), ("R32k", env.R32k)):
+        got = run[:, rows]
+        print(f"[net_refs] {IDS[index]} {name}: max / rms error {float((got.double() - R64).abs().max()):.3e} / {R.rms(got.double() - R64):.3e}, "
+              f"ratios {R.ratios(got, R64, E)}, output scale {scale:.3g}")
+        R.check_outputs(got, R64, tol_max, tol_rms, f"{IDS[index]} {name}")
+    if case.classes:
+        picks = hist[:, case.P:] if case.kind != "s2s_classes" else hist[:, case.P:].long()
+        R.check_picks(picks, env.R64, tol_max, f"{IDS[index]} the fp32 oracle's own picks")
+
+
+@pytest.mark.parametrize("index", range(len(R.ALL_CASES)), ids=IDS)
+def test_every_defect_leaves_the_envelope(index):
+    case, hist, conds, env = _run(index)
+    rows = case.rows()
+    tol_max, _ = R.tolerance(env.E[:, rows])
+    for name, out in R.defects(case, hist, conds, env.R64):
+        print(f"[net_refs] {IDS[index]} {name}: moves the compared outputs by up to {float((out[:, rows] - env.R64[:, rows]).abs().max()):.3e}, "
+              f"tol_max {tol_max:.3e}")
+        R.check_near_miss(out[:, rows], env.R64[:, rows], tol_max, f"{IDS[index]} {name}")
+
+
+def test_seq2seq_dropped_reverse_bias_is_seen_now():
+    """entries of dec.lstm.0.bias_hh_l0_reverse zeroed one at a time, resident bi-LSTM geometry (128, 8, 16, 2 layers): some move the frames by
+    less than the 2e-4 max|want| the older test allows, and every one of them leaves the envelope"""
+    index = next(i for i, (_, c) in enumerate(R.ALL_CASES) if c.id == "resident-128-8-16-2layers")
+    case, hist, conds, env = _run(index)
+    tol_max, _ = R.tolerance(env.E)
+    old = 2e-4 * float(env.R64.abs().max())
+    unseen = 0
+    for entry in range(0, 512, 37):
+        name, out = R.bias_dropped(case, hist, conds, entry)
+        assert "dec.lstm.0.bias_hh_l0_reverse" in name
+        moved = float((out - env.R64).abs().max())
+        print(f"[net_refs] {name}: moves the frames by {moved:.3e}; older tolerance {old:.3e}, tol_max {tol_max:.3e}")
+        unseen += moved <= old
+        with pytest.raises(AssertionError):
+            R.check_outputs(out, env.R64, tol_max, float("inf"), "the defect as a device output")
+        R.check_near_miss(out, env.R64, tol_max, name)
+    assert unseen > 0, "the older tolerance would have seen every one of these"
+
+
+def test_split_k_cases_force_a_split_the_default_does_not_take():
+    """the arithmetic of csrc/gemm.hip for the split-K cases: the GEMM has at least three stages, the forced split is honoured as it stands (no
+    clamp) and is not what the launch would choose by itself; and why model_dim 128 would not do"""
+    cases = [c for _, c in R.ALL_CASES if c.forced_split]
+    assert sorted(c.forced_split[3] for c in cases) == [2, 3]
+    for c in cases:
+        M, N, K, forced = c.forced_split
+        assert M == c.clips * c.hop >= 128 and K == c.sd["enc.fc_out.weight"].shape[0] and N == c.sd["output_module.heads.0.0.weight"].shape[0]
+        assert c.env["MMK_GEMM_KSPLIT"] == str(forced)
+        ks, stages = R.gemm_k_split(M, N, K, forced)
+        default, _ = R.gemm_k_split(M, N, K)
+        assert stages >= 3 and ks == forced and ks != default, (c.id, ks, stages, default)
+    assert R.gemm_k_split(128, 65, 128, 3) == (2, 2) and R.gemm_k_split(128, 65, 128) == (2, 2)
+
+
+def test_check_picks_refuses_a_clear_second_best():
+    R64 = torch.tensor([[[0.0, 1.0, 0.5, 9.0]]], dtype=torch.float64)      # (the last column is the temperature's)
+    R.check_picks(torch.tensor([[1]]), R64, 1e-6)
+    with pytest.raises(AssertionError):
+        R.check_picks(torch.tensor([[2]]), R64, 1e-6)
+    with pytest.raises(AssertionError):
+        R.check_picks(torch.tensor([[3]]), R64, 1e-6)
+    R.check_picks(torch.tensor([[2]]), R64, 0.25)
+
+
+# ---- the formulas themselves ---------------------------------------------------------------------------------------------------------------------------
+def _grid():
+    """[-30, 30] in steps of 1 / 2048 and, around 0, +- 2^-k / 2^-k (1 + 2^-3 j): every binade down to 2^-40"""
+    small = torch.cat([2.0 ** -k * (1 + torch.arange(8) / 8.0) for k in range(0, 41)])
+    return torch.cat([torch.linspace(-30, 30, 60 * 2048 + 1), small, -small, torch.zeros(1)]).float()
+
+
+U = 2.0 ** -24
+# sigmoid_fast: t = fl(x c), c = fl(-log2 e): |dt| <= 2 u |t|, which 2^t turns into a relative 2 u |x| of e = exp(-x); exp2, the sum and the
+# quotient add 3 u (relative, the CPU's are correctly rounded to ~1 ulp): |ds| <= s (1 - s) 2 u |x| + 3 u s <= (2 * 0.2239 + 3) u -> 4 u
+SIGMOID_ABS = 4 * U
+# tanh_fast = 2 s(2 x) - 1: twice that at 2 x, and the last sum: 9 u absolute.  RELATIVE to tanh(x) ~ x the formula has no bound near 0 (the
+# 1 is subtracted from a rounded 2 s): below |x| = u it returns 0 or 2 u
+TANH_ABS = 9 * U
+# mish_fast = x n / (n + 2): e = exp(min(x, 20)) (~1 ulp), n = e (e + 2), the quotient and the product: every step a relative rounding, no
+# cancellation (all terms positive): <= 8 u relative over the whole range
+MISH_REL = 8 * U
+
+
+def test_kernel_formulas_against_float64():
+    """the figures recorded beside sigmoid_fast / tanh_fast / mish_fast in csrc/mmk_common.h (torch's exp2 / exp and an exact division stand for
+    v_exp_f32 / v_rcp_f32 here)"""
+    x = _grid()
+    x64 = x.double()
+    worst = {}
+    for name, f, ref in (("sigmoid", R.k_sigmoid, torch.sigmoid), ("tanh", R.k_tanh, torch.tanh), ("mish", R.k_mish, F.mish)):
+        got, want = f(x).double(), ref(x64)
+        assert got.dtype == torch.float64 and f(x).dtype == torch.float32
+        err = (got - want).abs()
+        rel = torch.where(want != 0, err / want.abs(), torch.zeros_like(err))
+        worst[name] = (float(err.max()), float(rel.max()), float(rel[x.abs() >= 2.0 ** -6].max()))
+        print(f"[formulas] {name}_fast vs float64 over [-30, 30]: worst absolute {worst[name][0]:.3e} ({worst[name][0] / U:.2f} u), worst relative "
+              f"{worst[name][1]:.3e}, worst relative for |x| >= 2^-6 {worst[name][2]:.3e}")
+    assert worst["sigmoid"][0] <= SIGMOID_ABS and worst["tanh"][0] <= TANH_ABS and worst["mish"][1] <= MISH_REL
+    assert worst["tanh"][1] >= 0.5          # (the comment says so: no relative bound near 0)
