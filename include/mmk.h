@@ -257,6 +257,52 @@ size_t mmk_edge_components_workspace_bytes(int64_t n);
 int mmk_edge_components_i64(const int64_t* src, const int64_t* dst, int64_t n_edges, int64_t n, int64_t* labels, int64_t* n_components,
                             void* workspace, size_t workspace_bytes, mmk_stream_t stream);
 
+/* Principal components of corpus frames (mimikit/features/functionals.py:1114-1138 PCA: sklearn's StandardScaler, then sklearn's PCA).
+ * x: n frames of d bins, fp32, rows x_row_stride apart; everything else is fp64 on the device and contiguous.
+ *
+ * mmk_pca_colstats_f64: scale[j] = the population (ddof 0) standard deviation of column j, or 1 where the column counts as constant by
+ * sklearn's rule var <= n eps var + (n mu eps)^2 (eps = 2^-52); mean[j] = mu_j + m_j scale[j], where mu is the column mean and m the
+ * column mean of (x - mu) / scale - the mean that sklearn's PCA subtracts after the scaler, folded in.  Three passes of per-chunk partial
+ * sums added in rising chunk order.  Workspace: mmk_pca_colstats_workspace_bytes(n, d).
+ *
+ * mmk_pca_cov_f64: c (d, d) = Z^T Z / (n - 1) with Z = (x - mean) / scale, formed while the tiles are loaded and never written.
+ * v_mfma_f64_16x16x4_f64 on 64 x 64 blocks of the lower block triangle, the rows split into runs over workgroups whose partial blocks
+ * (workspace: mmk_pca_cov_workspace_bytes(n, d)) a second launch adds in rising run order; c[i][j] and c[j][i] are one value.  n < 2:
+ * MMK_ERR_INVALID.
+ *
+ * mmk_pca_eig_f64: the n_components eigenpairs of the symmetric c with the largest eigenvalues, falling: components (n_components, d),
+ * each of unit length with its entry of largest magnitude (the first of equals) positive - sklearn 1.5+'s svd_flip(u_based_decision=
+ * False) - and variance (n_components) = the eigenvalues, negative ones as 0.  Block subspace iteration with a Rayleigh-Ritz step on
+ * min(d, n_components + 16) columns from a fixed start block: Householder QR (orthonormal whatever the block's rank), C Q by
+ * v_mfma_f64_16x16x4_f64, a cyclic Jacobi eigensolver of the small matrix in one workgroup.  It stops when
+ * max_k |C q_k - theta_k q_k|_2 <= MMK_PCA_TOL |C|_inf over the first n_components columns; a device flag freezes the result at that
+ * iteration, which *n_iter (HOST memory) receives.  THE CALL WAITS FOR THE STREAM every 8 iterations to read the flag: it cannot be
+ * captured into a graph.  max_iter = 0: MMK_PCA_MAX_ITER; reaching the cap is MMK_ERR_CONVERGENCE and the message names the residual.
+ * No eigendecomposition of size d is formed.  Workspace: mmk_pca_eig_workspace_bytes(d, n_components).
+ *
+ * mmk_pca_project_f32: out[i][k] (fp32, rows out_row_stride apart) = sum_j ((y[i][j] - mean[j]) / scale[j]) components[k][j], per entry
+ * one fp64 fma chain over rising j, rounded to fp32 once.
+ *
+ * d > MMK_PCA_MAX_D, n_components > MMK_PCA_MAX_COMPONENTS: MMK_ERR_UNSUPPORTED.  fp32 data 4-byte, fp64 data and workspaces 8-byte
+ * aligned; tails are masked here; nothing but the stated outputs and workspace is written; no atomics: two calls give the same bits.
+ * NaN and inf in the inputs are not handled. */
+#define MMK_ERR_CONVERGENCE (-7) /* an iteration reached its cap before its stop rule */
+#define MMK_PCA_MAX_D 4096
+#define MMK_PCA_MAX_COMPONENTS 64
+#define MMK_PCA_MAX_ITER 4000
+#define MMK_PCA_TOL 1e-12
+size_t mmk_pca_colstats_workspace_bytes(int64_t n, int32_t d);
+int mmk_pca_colstats_f64(const float* x, int64_t x_row_stride, int64_t n, int32_t d, double* mean, double* scale, void* workspace,
+                         size_t workspace_bytes, mmk_stream_t stream);
+size_t mmk_pca_cov_workspace_bytes(int64_t n, int32_t d);
+int mmk_pca_cov_f64(const float* x, int64_t x_row_stride, int64_t n, int32_t d, const double* mean, const double* scale, double* c,
+                    void* workspace, size_t workspace_bytes, mmk_stream_t stream);
+size_t mmk_pca_eig_workspace_bytes(int32_t d, int32_t n_components);
+int mmk_pca_eig_f64(const double* c, int32_t d, int32_t n_components, int32_t max_iter, double* components, double* variance,
+                    int32_t* n_iter, void* workspace, size_t workspace_bytes, mmk_stream_t stream);
+int mmk_pca_project_f32(const float* y, int64_t y_row_stride, int64_t m, int32_t d, const double* mean, const double* scale,
+                        const double* components, int32_t n_components, float* out, int64_t out_row_stride, mmk_stream_t stream);
+
 /* STFT.torch_func with coordinate="mag" == MagSpec.torch_func
  * (mimikit/features/functionals.py:507-524, :576-606): periodic-Hann framed
  * real FFT magnitudes.  x: (batch, n_samples) rows `x_row_stride` apart,

@@ -1,0 +1,765 @@
+// Principal components of corpus frames (mimikit/features/functionals.py:1114-1138 PCA = sklearn's StandardScaler, then sklearn's PCA).  Everything is
+// fp64 inside; the frames and the scores are fp32.  Four entry points, no atomics, every sum in one fixed order: two calls give the same bits.
+//
+//   column statistics     three passes over the rows, each a launch of per-chunk partial sums (a chunk is a fixed run of rows: the partials
+//                         of 64 columns by one workgroup) and a launch that adds the chunks' partials in rising order:
+//                         mu = sum x / N;  var = sum (x - mu)^2 / N, scale = 1 where var <= N eps var + (N mu eps)^2 (sklearn's
+//                         _is_constant_feature) and sqrt(var) elsewhere;  m = sum ((x - mu) / scale) / N, the mean that sklearn's PCA
+//                         subtracts again, folded into the mean that leaves: mean = mu + m scale.
+//   covariance            C = Z^T Z / (N - 1), Z = (x - mean) / scale formed while a tile is loaded and never written.  A workgroup owns one
+//                         64 x 64 block of the lower block triangle and one run of rows; its four waves hold 2 x 2 products of
+//                         v_mfma_f64_16x16x4_f64 each (C/D: col = lane & 15, row = (lane >> 4) + 4 reg).  The runs' partial blocks go to the
+//                         workspace and a second launch adds them in rising run order, divides once and writes C[i][j] and C[j][i] from the
+//                         one value computed for j <= i.
+//   top-k eigenpairs      block subspace iteration with a Rayleigh-Ritz step on a block of b = min(D, k + 16) columns:
+//                             Q' = orth(Y)   Householder QR in one workgroup - reflectors, not a Cholesky of Y^T Y: Q' is orthonormal whatever
+//                                            the rank of Y (a zero column leaves its reflector the identity)
+//                             Z = C Q'       v_mfma_f64_16x16x4_f64, C read through its mirror so that both operands are coalesced
+//                             H = Q'^T Z     W, theta = eig(H): cyclic Jacobi in one workgroup, H in LDS, round-robin pairs (b / 2
+//                                            rotations at a time), eigenvalues sorted falling
+//                             Q = Q' W, Y = Z W (= C Q up to rounding), res_k = |Y_k - theta_k Q_k|_2
+//                         until max_k res_k <= kPcTol |C|_inf over the first k columns.  The start block is a counter-based hash.  A device
+//                         flag holds the iteration that converged; every kernel of a later iteration returns at once when it is set, and the
+//                         host reads the flag every kPcPoll iterations - the result does not depend on when the host looks.
+//                         At the end each vector's sign makes its entry of largest magnitude (the first of equals) positive.
+//   projection            scores = ((y - mean) / scale) components^T, per (row, component) one fp64 fma chain over rising column, rounded to
+//                         fp32 once.
+#include "mmk_common.h"
+
+#include <math.h>
+
+namespace mmk {
+
+typedef double pc_f64x4 __attribute__((ext_vector_type(4)));
+
+constexpr double kPcTol = MMK_PCA_TOL;  // the stop rule's tolerance, relative to |C|_inf
+constexpr int kPcPoll = 8;              // the host reads the convergence flag every kPcPoll iterations
+constexpr int kPcExtra = 16;            // guard columns of the block beyond n_components
+constexpr int kPcMaxBlock = MMK_PCA_MAX_COMPONENTS + kPcExtra;
+constexpr int kPcSweeps = 40;           // cap of the Jacobi sweeps (8 to 10 are typical)
+constexpr int kPcWide = 1024;           // threads of the one-workgroup kernels
+constexpr int kStChunks = 1024;         // most row chunks of the column statistics
+constexpr int kStMinRows = 256;
+constexpr int kCvTile = 64;
+constexpr int kCvRows = 16;             // rows per LDS chunk
+constexpr int kCvPitch = 68;
+constexpr int kCvMinRows = 256;         // fewest rows of a run
+constexpr int kCvTargetGroups = 1024;   // workgroups asked for across blocks and runs
+constexpr int kPjRows = 16;
+constexpr int kPjCols = 64;
+static_assert(kPcMaxBlock == 80, "the Jacobi kernel's LDS is sized for 80 columns");
+
+// ---------------------------------------------------------------------------------------------------------------- column statistics
+static int st_chunks(int64_t n) {
+  const int64_t c = (n + kStMinRows - 1) / kStMinRows;
+  return (int)(c < kStChunks ? c : kStChunks);
+}
+
+// MODE 0: x;  1: (x - a)^2;  2: (x - a) / s
+template <int MODE>
+__global__ __launch_bounds__(256) void pca_colsum_kernel(const float* __restrict__ x, int64_t x_row_stride, int64_t n, int32_t d,
+                                                         const double* __restrict__ a, const double* __restrict__ s, int64_t rows_per_chunk,
+                                                         double* __restrict__ partial) {
+  __shared__ double red[4][64];
+  const int col = blockIdx.x * 64 + (threadIdx.x & 63), rl = threadIdx.x >> 6;
+  const int64_t rbeg = (int64_t)blockIdx.y * rows_per_chunk;
+  const int64_t rend = rbeg + rows_per_chunk < n ? rbeg + rows_per_chunk : n;
+  double acc = 0.0;
+  if (col < d) {
+    const double av = MODE > 0 ? a[col] : 0.0, sv = MODE == 2 ? s[col] : 1.0;
+    for (int64_t r = rbeg + rl; r < rend; r += 4) {
+      const double v = (double)x[r * x_row_stride + col];
+      if (MODE == 0) acc += v;
+      if (MODE == 1) acc = fma(v - av, v - av, acc);
+      if (MODE == 2) acc += (v - av) / sv;
+    }
+  }
+  red[rl][threadIdx.x & 63] = acc;
+  __syncthreads();
+  if (rl == 0 && col < d) partial[(int64_t)blockIdx.y * d + col] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void pca_colfin_kernel(const double* __restrict__ partial, int32_t chunks, int64_t n, int32_t d,
+                                                         double* __restrict__ mu, double* __restrict__ scale, double* __restrict__ mean) {
+  const int col = blockIdx.x * 256 + threadIdx.x;
+  if (col >= d) return;
+  double acc = 0.0;
+  for (int c = 0; c < chunks; ++c) acc += partial[(int64_t)c * d + col];
+  const double nn = (double)n;
+  if (MODE == 0) mu[col] = acc / nn;
+  if (MODE == 1) {
+    const double var = acc / nn, eps = 2.220446049250313e-16, m = mu[col];
+    const double t = nn * m * eps;
+    scale[col] = var <= nn * eps * var + t * t ? 1.0 : sqrt(var);
+  }
+  if (MODE == 2) mean[col] = fma(acc / nn, scale[col], mu[col]);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- covariance
+__device__ __forceinline__ void cv_pair(int pair, int& bi, int& bj) {
+  int i = (int)((sqrt(8.0 * (double)pair + 1.0) - 1.0) * 0.5);
+  while ((i + 1) * (i + 2) / 2 <= pair) ++i;
+  while (i * (i + 1) / 2 > pair) --i;
+  bi = i;
+  bj = pair - i * (i + 1) / 2;
+}
+
+struct CvPlan {
+  int nb, pairs, runs;
+  int64_t rows_per_run;
+};
+static CvPlan cv_plan(int64_t n, int32_t d) {
+  CvPlan p;
+  p.nb = (d + kCvTile - 1) / kCvTile;
+  p.pairs = p.nb * (p.nb + 1) / 2;
+  int64_t want = (kCvTargetGroups + p.pairs - 1) / p.pairs;
+  const int64_t most = (n + kCvMinRows - 1) / kCvMinRows;
+  if (want > most) want = most;
+  if (want < 1) want = 1;
+  p.rows_per_run = round_up((n + want - 1) / want, kCvRows);
+  p.runs = (int)((n + p.rows_per_run - 1) / p.rows_per_run);
+  return p;
+}
+
+__global__ __launch_bounds__(256) void pca_cov_kernel(const float* __restrict__ x, int64_t x_row_stride, int64_t n, int32_t d,
+                                                      const double* __restrict__ mean, const double* __restrict__ scale, int64_t rows_per_run,
+                                                      int32_t n_pairs, double* __restrict__ partial) {
+  __shared__ double zi[kCvRows * kCvPitch];
+  __shared__ double zj[kCvRows * kCvPitch];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave & 1, wn = wave >> 1;
+  const int pair = blockIdx.x % n_pairs, run = blockIdx.x / n_pairs;
+  int bi, bj;
+  cv_pair(pair, bi, bj);
+  const int col = tid & 63, r0 = tid >> 6;
+  const int ci = bi * kCvTile + col, cj = bj * kCvTile + col;
+  const bool ini = ci < d, inj = cj < d;
+  const int cic = ini ? ci : d - 1, cjc = inj ? cj : d - 1;
+  const double mi = mean[cic], si = scale[cic], mj = mean[cjc], sj = scale[cjc];
+  const int64_t rbeg = (int64_t)run * rows_per_run;
+  const int64_t rend = rbeg + rows_per_run < n ? rbeg + rows_per_run : n;
+
+  pc_f64x4 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[a][b][q] = 0.0;
+
+  float gi[4], gj[4];
+  auto gload = [&](int64_t rb) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int64_t r = rb + q * 4 + r0;
+      const int64_t rc = r < n ? r : n - 1;
+      gi[q] = x[rc * x_row_stride + cic];
+      gj[q] = x[rc * x_row_stride + cjc];
+    }
+  };
+  if (rbeg < rend) gload(rbeg);
+  for (int64_t rb = rbeg; rb < rend; rb += kCvRows) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const bool ok = rb + q * 4 + r0 < rend;
+      zi[(q * 4 + r0) * kCvPitch + col] = (ok && ini) ? ((double)gi[q] - mi) / si : 0.0;
+      zj[(q * 4 + r0) * kCvPitch + col] = (ok && inj) ? ((double)gj[q] - mj) / sj : 0.0;
+    }
+    __syncthreads();
+    if (rb + kCvRows < rend) gload(rb + kCvRows);
+#pragma unroll
+    for (int kk = 0; kk < kCvRows; kk += 4) {
+      double av[2], bv[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        av[t] = zi[(kk + (lane >> 4)) * kCvPitch + wm * 32 + t * 16 + (lane & 15)];
+        bv[t] = zj[(kk + (lane >> 4)) * kCvPitch + wn * 32 + t * 16 + (lane & 15)];
+      }
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[a], bv[b], acc[a][b], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  double* out = partial + ((int64_t)run * n_pairs + pair) * (kCvTile * kCvTile);
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int row = wm * 32 + a * 16 + (lane >> 4) + 4 * q;      // the f64 map: NOT 4 (lane >> 4) + q
+        const int cc = wn * 32 + b * 16 + (lane & 15);
+        out[row * kCvTile + cc] = acc[a][b][q];
+      }
+}
+
+__global__ __launch_bounds__(256) void pca_cov_reduce_kernel(const double* __restrict__ partial, int32_t n_pairs, int32_t runs, int32_t d,
+                                                             double denom, double* __restrict__ c) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int pair = (int)(idx / (kCvTile * kCvTile)), e = (int)(idx % (kCvTile * kCvTile));
+  if (pair >= n_pairs) return;
+  int bi, bj;
+  cv_pair(pair, bi, bj);
+  const int i = bi * kCvTile + e / kCvTile, j = bj * kCvTile + e % kCvTile;
+  if (i >= d || j >= d || j > i) return;
+  double acc = 0.0;
+  for (int r = 0; r < runs; ++r) acc += partial[((int64_t)r * n_pairs + pair) * (kCvTile * kCvTile) + e];
+  const double v = acc / denom;
+  c[(int64_t)i * d + j] = v;
+  c[(int64_t)j * d + i] = v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- eigenpairs
+// wave tree, then the waves' sums in rising order; every thread gets the sum.  `red` holds blockDim.x / 64 doubles
+__device__ __forceinline__ double pc_block_sum(double v, double* red) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  const int nw = blockDim.x >> 6;
+  __syncthreads();                                   // (red may still be read from the call before)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int w = 0; w < nw; ++w) s += red[w];
+  return s;
+}
+
+__global__ __launch_bounds__(256) void pca_start_kernel(int32_t d, int32_t b, double* __restrict__ y) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)d * b) return;
+  uint32_t h = (uint32_t)idx * 0x9E3779B9u + 0x7F4A7C15u;
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  y[idx] = (double)(h >> 8) * (1.0 / 8388608.0) - 1.0;      // [-1, 1), exact
+}
+
+// |C|_inf: one workgroup per row, then one thread takes the largest
+__global__ __launch_bounds__(256) void pca_rowsum_kernel(const double* __restrict__ c, int32_t d, double* __restrict__ rowsum) {
+  __shared__ double red[4];
+  double acc = 0.0;
+  for (int j = threadIdx.x; j < d; j += 256) acc += fabs(c[(int64_t)blockIdx.x * d + j]);
+  acc = pc_block_sum(acc, red);
+  if (threadIdx.x == 0) rowsum[blockIdx.x] = acc;
+}
+__global__ __launch_bounds__(64) void pca_cnorm_kernel(const double* __restrict__ rowsum, int32_t d, double* __restrict__ stat) {
+  if (threadIdx.x != 0) return;
+  double m = 0.0;
+  for (int i = 0; i < d; ++i) m = rowsum[i] > m ? rowsum[i] : m;
+  stat[0] = m;
+}
+
+// Householder QR of y (d, b) row-major in place, then qp (d, b) = the first b columns of the product of the reflectors.  One workgroup of
+// kPcWide threads: thread (g, j) = (tid / b, tid % b) walks the rows g, g + nrg, ... of column j.
+__global__ __launch_bounds__(kPcWide) void pca_qr_kernel(int32_t d, int32_t b, double* __restrict__ y, double* __restrict__ qp,
+                                                         const int32_t* __restrict__ done) {
+  __shared__ double part[kPcWide];
+  __shared__ double red[kPcWide / 64];
+  __shared__ double betas[kPcMaxBlock];
+  if (*done) return;
+  const int tid = threadIdx.x;
+  const int nrg = kPcWide / b;
+  const int g = tid / b, j = tid % b;
+  const bool live = g < nrg;
+  for (int k = 0; k < b; ++k) {
+    double ss = 0.0;
+    for (int i = k + tid; i < d; i += kPcWide) {
+      const double v = y[(int64_t)i * b + k];
+      ss = fma(v, v, ss);
+    }
+    const double x0 = y[(int64_t)k * b + k];
+    ss = pc_block_sum(ss, red);
+    const double nrm = sqrt(ss);
+    double beta = 0.0, v0 = x0;
+    if (nrm > 0.0) {
+      const double alpha = x0 >= 0.0 ? -nrm : nrm;
+      v0 = x0 - alpha;
+      beta = -1.0 / (alpha * v0);
+    }
+    __syncthreads();                                 // every thread has read x0
+    if (tid == 0) {
+      y[(int64_t)k * b + k] = v0;
+      betas[k] = beta;
+    }
+    __syncthreads();
+    double p = 0.0;
+    if (live && j > k)
+      for (int i = k + g; i < d; i += nrg) p = fma(y[(int64_t)i * b + k], y[(int64_t)i * b + j], p);
+    part[tid] = p;
+    __syncthreads();
+    if (live && j > k) {
+      double s = 0.0;
+      for (int gg = 0; gg < nrg; ++gg) s += part[gg * b + j];
+      s *= beta;
+      for (int i = k + g; i < d; i += nrg) y[(int64_t)i * b + j] = fma(-s, y[(int64_t)i * b + k], y[(int64_t)i * b + j]);
+    }
+    __syncthreads();
+  }
+  for (int64_t idx = tid; idx < (int64_t)d * b; idx += kPcWide) qp[idx] = (idx / b == idx % b) ? 1.0 : 0.0;
+  __syncthreads();
+  for (int k = b - 1; k >= 0; --k) {
+    const double beta = betas[k];
+    double p = 0.0;
+    if (live && j >= k)
+      for (int i = k + g; i < d; i += nrg) p = fma(y[(int64_t)i * b + k], qp[(int64_t)i * b + j], p);
+    part[tid] = p;
+    __syncthreads();
+    if (live && j >= k) {
+      double s = 0.0;
+      for (int gg = 0; gg < nrg; ++gg) s += part[gg * b + j];
+      s *= beta;
+      for (int i = k + g; i < d; i += nrg) qp[(int64_t)i * b + j] = fma(-s, y[(int64_t)i * b + k], qp[(int64_t)i * b + j]);
+    }
+    __syncthreads();
+  }
+}
+
+// z (d, b) = C qp: a workgroup owns a 16 x 16 tile of z, its four waves a quarter of the sum each, added in rising wave order
+__global__ __launch_bounds__(256) void pca_cq_kernel(const double* __restrict__ c, int32_t d, int32_t b, const double* __restrict__ qp,
+                                                     double* __restrict__ z, const int32_t* __restrict__ done) {
+  __shared__ double red[4][256];
+  if (*done) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r0 = blockIdx.x * 16, c0 = blockIdx.y * 16;
+  const int kq = ((d + 3) / 4 + 3) & ~3;
+  const int kbeg = wave * kq, kend = (wave + 1) * kq < d ? (wave + 1) * kq : d;
+  const int row = r0 + (lane & 15), colq = c0 + (lane & 15);
+  const int rowc = row < d ? row : d - 1, colc = colq < b ? colq : b - 1;
+  pc_f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+  for (int k0 = kbeg; k0 < kend; k0 += 4) {
+    const int k = k0 + (lane >> 4);
+    const int kc = k < d ? k : d - 1;
+    const double av = c[(int64_t)kc * d + rowc];     // = C[row][k]: C is mirrored exactly
+    const double bv = qp[(int64_t)kc * b + colc];
+    const bool kin = k < kend;
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64((kin && row < d) ? av : 0.0, (kin && colq < b) ? bv : 0.0, acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) red[wave][q * 64 + lane] = acc[q];
+  __syncthreads();
+  if (wave == 0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int orow = r0 + (lane >> 4) + 4 * q, ocol = c0 + (lane & 15);
+      const double v = ((red[0][q * 64 + lane] + red[1][q * 64 + lane]) + red[2][q * 64 + lane]) + red[3][q * 64 + lane];
+      if (orow < d && ocol < b) z[(int64_t)orow * b + ocol] = v;
+    }
+  }
+}
+
+// h (b, b) = qp^T z: workgroup a computes row a
+__global__ __launch_bounds__(kPcWide) void pca_h_kernel(int32_t d, int32_t b, const double* __restrict__ qp, const double* __restrict__ z,
+                                                        double* __restrict__ h, const int32_t* __restrict__ done) {
+  __shared__ double part[kPcWide];
+  if (*done) return;
+  const int tid = threadIdx.x, a = blockIdx.x;
+  const int nrg = kPcWide / b;
+  const int g = tid / b, j = tid % b;
+  double p = 0.0;
+  if (g < nrg)
+    for (int i = g; i < d; i += nrg) p = fma(qp[(int64_t)i * b + a], z[(int64_t)i * b + j], p);
+  part[tid] = p;
+  __syncthreads();
+  if (tid < b) {
+    double s = 0.0;
+    for (int gg = 0; gg < nrg; ++gg) s += part[gg * b + tid];
+    h[a * b + tid] = s;
+  }
+}
+
+// eigenvectors (columns of w2, sorted by falling eigenvalue theta) of the symmetrised h: cyclic Jacobi, b / 2 disjoint rotations at a time
+__global__ __launch_bounds__(kPcWide) void pca_jacobi_kernel(int32_t b, const double* __restrict__ h, double* __restrict__ w, double* __restrict__ w2,
+                                                             double* __restrict__ theta, const int32_t* __restrict__ done) {
+  constexpr int P = kPcMaxBlock + 1;
+  __shared__ double hs[kPcMaxBlock * P];
+  __shared__ double cs[kPcMaxBlock / 2], sn[kPcMaxBlock / 2];
+  __shared__ int pp[kPcMaxBlock / 2], qq[kPcMaxBlock / 2], rank[kPcMaxBlock];
+  __shared__ int rotated;
+  if (*done) return;
+  const int tid = threadIdx.x;
+  for (int idx = tid; idx < b * b; idx += kPcWide) {
+    const int a = idx / b, c = idx % b;
+    hs[a * P + c] = 0.5 * (h[a * b + c] + h[c * b + a]);
+    w[idx] = a == c ? 1.0 : 0.0;
+  }
+  const int m = (b + 1) & ~1, half = m / 2;
+  __syncthreads();
+  for (int sweep = 0; sweep < kPcSweeps; ++sweep) {
+    if (tid == 0) rotated = 0;
+    __syncthreads();
+    for (int r = 0; r < m - 1; ++r) {
+      if (tid < half) {
+        int p = tid == 0 ? m - 1 : (r + tid) % (m - 1);
+        int q = tid == 0 ? r : (r - tid + (m - 1)) % (m - 1);
+        if (p > q) {
+          const int t = p;
+          p = q;
+          q = t;
+        }
+        double c = 1.0, s = 0.0;
+        if (q < b) {
+          const double apq = hs[p * P + q], app = hs[p * P + p], aqq = hs[q * P + q];
+          const double g = 100.0 * fabs(apq);
+          if (apq != 0.0 && !(fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq))) {
+            const double th = (aqq - app) / (2.0 * apq);
+            const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
+            c = 1.0 / sqrt(t * t + 1.0);
+            s = t * c;
+            rotated = 1;
+          }
+        }
+        pp[tid] = p;
+        qq[tid] = q;
+        cs[tid] = c;
+        sn[tid] = s;
+      }
+      __syncthreads();
+      for (int idx = tid; idx < b * half; idx += kPcWide) {      // H <- H J, W <- W J
+        const int i = idx / half, t = idx % half;
+        const int p = pp[t], q = qq[t];
+        const double c = cs[t], s = sn[t];
+        if (q < b && s != 0.0) {
+          const double hp = hs[i * P + p], hq = hs[i * P + q];
+          hs[i * P + p] = c * hp - s * hq;
+          hs[i * P + q] = s * hp + c * hq;
+          const double wp = w[i * b + p], wq = w[i * b + q];
+          w[i * b + p] = c * wp - s * wq;
+          w[i * b + q] = s * wp + c * wq;
+        }
+      }
+      __syncthreads();
+      for (int idx = tid; idx < b * half; idx += kPcWide) {      // H <- J^T H
+        const int jc = idx / half, t = idx % half;
+        const int p = pp[t], q = qq[t];
+        const double c = cs[t], s = sn[t];
+        if (q < b && s != 0.0) {
+          const double hp = hs[p * P + jc], hq = hs[q * P + jc];
+          hs[p * P + jc] = c * hp - s * hq;
+          hs[q * P + jc] = s * hp + c * hq;
+        }
+      }
+      __syncthreads();
+    }
+    const int any = rotated;
+    __syncthreads();
+    if (!any) break;
+  }
+  if (tid < b) {
+    const double mine = hs[tid * P + tid];
+    int rk = 0;
+    for (int i = 0; i < b; ++i) {
+      const double o = hs[i * P + i];
+      rk += (o > mine || (o == mine && i < tid)) ? 1 : 0;
+    }
+    rank[tid] = rk;
+    theta[rk] = mine;
+  }
+  __syncthreads();
+  for (int idx = tid; idx < b * b; idx += kPcWide) w2[(idx / b) * b + rank[idx % b]] = w[idx];
+}
+
+// q (d, b) = qp w2, y (d, b) = z w2
+__global__ __launch_bounds__(256) void pca_rotate_kernel(int32_t d, int32_t b, const double* __restrict__ qp, const double* __restrict__ z,
+                                                         const double* __restrict__ w2, double* __restrict__ q, double* __restrict__ y,
+                                                         const int32_t* __restrict__ done) {
+  if (*done) return;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)d * b) return;
+  const int64_t i = idx / b;
+  const int j = (int)(idx % b);
+  double aq = 0.0, ay = 0.0;
+  for (int k = 0; k < b; ++k) {
+    const double wv = w2[k * b + j];
+    aq = fma(qp[i * b + k], wv, aq);
+    ay = fma(z[i * b + k], wv, ay);
+  }
+  q[idx] = aq;
+  y[idx] = ay;
+}
+
+__global__ __launch_bounds__(256) void pca_resid_kernel(int32_t d, int32_t b, const double* __restrict__ q, const double* __restrict__ y,
+                                                        const double* __restrict__ theta, double* __restrict__ resid,
+                                                        const int32_t* __restrict__ done) {
+  __shared__ double red[4];
+  if (*done) return;
+  const int k = blockIdx.x;
+  const double th = theta[k];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < d; i += 256) {
+    const double r = fma(-th, q[(int64_t)i * b + k], y[(int64_t)i * b + k]);
+    acc = fma(r, r, acc);
+  }
+  acc = pc_block_sum(acc, red);
+  if (threadIdx.x == 0) resid[k] = sqrt(acc);
+}
+
+// stat[0] = |C|_inf, stat[1] = the largest residual of the last iteration that ran; *done = that iteration once it meets the stop rule
+__global__ __launch_bounds__(64) void pca_check_kernel(int32_t ncomp, int32_t iter, const double* __restrict__ resid, double* __restrict__ stat,
+                                                       int32_t* __restrict__ done) {
+  if (threadIdx.x != 0 || *done) return;
+  double m = 0.0;
+  for (int k = 0; k < ncomp; ++k) m = (resid[k] > m || resid[k] != resid[k]) ? resid[k] : m;
+  stat[1] = m;
+  if (m <= kPcTol * stat[0]) *done = iter;
+}
+
+// components[k][0 .. d) = +-q[.][k], the sign that makes the entry of largest magnitude (the first of equals) positive
+__global__ __launch_bounds__(256) void pca_finish_kernel(int32_t d, int32_t b, const double* __restrict__ q, const double* __restrict__ theta,
+                                                         double* __restrict__ components, double* __restrict__ variance) {
+  __shared__ double bv[256];
+  __shared__ int bi[256];
+  const int k = blockIdx.x, tid = threadIdx.x;
+  double best = -1.0;
+  int at = 0x7fffffff;
+  for (int i = tid; i < d; i += 256) {
+    const double a = fabs(q[(int64_t)i * b + k]);
+    if (a > best) {
+      best = a;
+      at = i;
+    }
+  }
+  bv[tid] = best;
+  bi[tid] = at;
+  __syncthreads();
+  for (int off = 128; off >= 1; off >>= 1) {
+    if (tid < off && (bv[tid + off] > bv[tid] || (bv[tid + off] == bv[tid] && bi[tid + off] < bi[tid]))) {
+      bv[tid] = bv[tid + off];
+      bi[tid] = bi[tid + off];
+    }
+    __syncthreads();
+  }
+  const double sign = q[(int64_t)bi[0] * b + k] < 0.0 ? -1.0 : 1.0;
+  for (int i = tid; i < d; i += 256) components[(int64_t)k * d + i] = sign * q[(int64_t)i * b + k];
+  if (tid == 0) variance[k] = theta[k] > 0.0 ? theta[k] : 0.0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- projection
+__global__ __launch_bounds__(256) void pca_project_kernel(const float* __restrict__ y, int64_t y_row_stride, int64_t m, int32_t d,
+                                                          const double* __restrict__ mean, const double* __restrict__ scale,
+                                                          const double* __restrict__ components, int32_t ncomp, float* __restrict__ out,
+                                                          int64_t out_row_stride) {
+  __shared__ double zs[kPjRows * (kPjCols + 1)];
+  __shared__ double cs[MMK_PCA_MAX_COMPONENTS * (kPjCols + 1)];
+  const int tid = threadIdx.x;
+  const int col = tid & 63, r4 = tid >> 6;
+  const int row = tid & 15, kg = tid >> 4;
+  const int64_t rbase = (int64_t)blockIdx.x * kPjRows;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int j0 = 0; j0 < d; j0 += kPjCols) {
+    const int j = j0 + col;
+    const bool jin = j < d;
+    const double mj = jin ? mean[j] : 0.0, sj = jin ? scale[j] : 1.0;
+#pragma unroll
+    for (int q = 0; q < kPjRows / 4; ++q) {
+      const int64_t r = rbase + q * 4 + r4;
+      zs[(q * 4 + r4) * (kPjCols + 1) + col] = (jin && r < m) ? ((double)y[r * y_row_stride + j] - mj) / sj : 0.0;
+    }
+    for (int kk = r4; kk < ncomp; kk += 4) cs[kk * (kPjCols + 1) + col] = jin ? components[(int64_t)kk * d + j] : 0.0;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int k = kg + 16 * q;
+      if (k < ncomp) {
+        double a = acc[q];
+        for (int jj = 0; jj < kPjCols; ++jj) a = fma(zs[row * (kPjCols + 1) + jj], cs[k * (kPjCols + 1) + jj], a);
+        acc[q] = a;
+      }
+    }
+    __syncthreads();
+  }
+  const int64_t r = rbase + row;
+  if (r < m) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int k = kg + 16 * q;
+      if (k < ncomp) out[r * out_row_stride + k] = (float)acc[q];
+    }
+  }
+}
+
+static int pc_block(int32_t d, int32_t ncomp) { return d < ncomp + kPcExtra ? d : ncomp + kPcExtra; }
+
+static bool pc_misaligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(a - 1)) != 0; }
+
+}  // namespace mmk
+
+// ---------------------------------------------------------------------------------------------------------------- entry points
+extern "C" size_t mmk_pca_colstats_workspace_bytes(int64_t n, int32_t d) {
+  using namespace mmk;
+  if (n < 1 || d < 1 || d > MMK_PCA_MAX_D) return 0;
+  return ((size_t)st_chunks(n) + 1) * (size_t)d * sizeof(double);
+}
+
+extern "C" int mmk_pca_colstats_f64(const float* x, int64_t x_row_stride, int64_t n, int32_t d, double* mean, double* scale, void* workspace,
+                                    size_t workspace_bytes, mmk_stream_t stream) {
+  using namespace mmk;
+  if (n < 1 || d < 1) return fail(MMK_ERR_INVALID, "pca_colstats: n = %lld rows, d = %d columns (both at least 1)", (long long)n, d);
+  if (d > MMK_PCA_MAX_D) return fail(MMK_ERR_UNSUPPORTED, "pca_colstats: d = %d columns, the limit is %d (MMK_PCA_MAX_D)", d, MMK_PCA_MAX_D);
+  if (!x || !mean || !scale || !workspace || x_row_stride < 0)
+    return fail(MMK_ERR_INVALID, "pca_colstats: bad arguments (null pointer or negative stride %lld)", (long long)x_row_stride);
+  if (pc_misaligned(x, 4) || pc_misaligned(mean, 8) || pc_misaligned(scale, 8) || pc_misaligned(workspace, 8))
+    return fail(MMK_ERR_INVALID, "pca_colstats: x must be 4-byte aligned, mean, scale and the workspace 8-byte aligned");
+  if (workspace_bytes < mmk_pca_colstats_workspace_bytes(n, d))
+    return fail(MMK_ERR_WORKSPACE, "pca_colstats: the workspace has %zu bytes, %zu are needed", workspace_bytes,
+                mmk_pca_colstats_workspace_bytes(n, d));
+  hipStream_t st = (hipStream_t)stream;
+  const int chunks = st_chunks(n);
+  const int64_t rows_per_chunk = (n + chunks - 1) / chunks;
+  double* mu = static_cast<double*>(workspace);
+  double* partial = mu + d;
+  const dim3 grid((unsigned)((d + 63) / 64), (unsigned)chunks), fin((unsigned)((d + 255) / 256)), wg(256);
+  hipLaunchKernelGGL(pca_colsum_kernel<0>, grid, wg, 0, st, x, x_row_stride, n, d, (const double*)nullptr, (const double*)nullptr, rows_per_chunk, partial);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pca_colfin_kernel<0>, fin, wg, 0, st, partial, chunks, n, d, mu, scale, mean);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pca_colsum_kernel<1>, grid, wg, 0, st, x, x_row_stride, n, d, mu, (const double*)nullptr, rows_per_chunk, partial);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pca_colfin_kernel<1>, fin, wg, 0, st, partial, chunks, n, d, mu, scale, mean);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pca_colsum_kernel<2>, grid, wg, 0, st, x, x_row_stride, n, d, mu, scale, rows_per_chunk, partial);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pca_colfin_kernel<2>, fin, wg, 0, st, partial, chunks, n, d, mu, scale, mean);
+  MMK_HIP(hipGetLastError());
+  return MMK_OK;
+}
+
+extern "C" size_t mmk_pca_cov_workspace_bytes(int64_t n, int32_t d) {
+  using namespace mmk;
+  if (n < 2 || d < 1 || d > MMK_PCA_MAX_D) return 0;
+  const CvPlan p = cv_plan(n, d);
+  return (size_t)p.runs * (size_t)p.pairs * kCvTile * kCvTile * sizeof(double);
+}
+
+extern "C" int mmk_pca_cov_f64(const float* x, int64_t x_row_stride, int64_t n, int32_t d, const double* mean, const double* scale, double* c,
+                               void* workspace, size_t workspace_bytes, mmk_stream_t stream) {
+  using namespace mmk;
+  if (n < 2 || d < 1) return fail(MMK_ERR_INVALID, "pca_cov: n = %lld rows (at least 2), d = %d columns (at least 1)", (long long)n, d);
+  if (d > MMK_PCA_MAX_D) return fail(MMK_ERR_UNSUPPORTED, "pca_cov: d = %d columns, the limit is %d (MMK_PCA_MAX_D)", d, MMK_PCA_MAX_D);
+  if (!x || !mean || !scale || !c || !workspace || x_row_stride < 0)
+    return fail(MMK_ERR_INVALID, "pca_cov: bad arguments (null pointer or negative stride %lld)", (long long)x_row_stride);
+  if (pc_misaligned(x, 4) || pc_misaligned(mean, 8) || pc_misaligned(scale, 8) || pc_misaligned(c, 8) || pc_misaligned(workspace, 8))
+    return fail(MMK_ERR_INVALID, "pca_cov: x must be 4-byte aligned, mean, scale, c and the workspace 8-byte aligned");
+  if (workspace_bytes < mmk_pca_cov_workspace_bytes(n, d))
+    return fail(MMK_ERR_WORKSPACE, "pca_cov: the workspace has %zu bytes, %zu are needed", workspace_bytes, mmk_pca_cov_workspace_bytes(n, d));
+  hipStream_t st = (hipStream_t)stream;
+  const CvPlan p = cv_plan(n, d);
+  double* partial = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(pca_cov_kernel, dim3((unsigned)(p.pairs * p.runs)), dim3(256), 0, st, x, x_row_stride, n, d, mean, scale, p.rows_per_run, p.pairs,
+                     partial);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pca_cov_reduce_kernel, dim3((unsigned)(p.pairs * (kCvTile * kCvTile / 256))), dim3(256), 0, st, partial, p.pairs, p.runs, d,
+                     (double)(n - 1), c);
+  MMK_HIP(hipGetLastError());
+  return MMK_OK;
+}
+
+extern "C" size_t mmk_pca_eig_workspace_bytes(int32_t d, int32_t n_components) {
+  using namespace mmk;
+  if (d < 1 || d > MMK_PCA_MAX_D || n_components < 1 || n_components > MMK_PCA_MAX_COMPONENTS || n_components > d) return 0;
+  const size_t b = (size_t)pc_block(d, n_components);
+  return (4 * (size_t)d * b + 3 * b * b + b + (size_t)d + (size_t)n_components + 4) * sizeof(double);
+}
+
+extern "C" int mmk_pca_eig_f64(const double* c, int32_t d, int32_t n_components, int32_t max_iter, double* components, double* variance,
+                               int32_t* n_iter, void* workspace, size_t workspace_bytes, mmk_stream_t stream) {
+  using namespace mmk;
+  if (d < 1 || n_components < 1 || n_components > d)
+    return fail(MMK_ERR_INVALID, "pca_eig: n_components = %d must lie in [1, d = %d]", n_components, d);
+  if (d > MMK_PCA_MAX_D) return fail(MMK_ERR_UNSUPPORTED, "pca_eig: d = %d columns, the limit is %d (MMK_PCA_MAX_D)", d, MMK_PCA_MAX_D);
+  if (n_components > MMK_PCA_MAX_COMPONENTS)
+    return fail(MMK_ERR_UNSUPPORTED, "pca_eig: n_components = %d, the limit is %d (MMK_PCA_MAX_COMPONENTS: the Jacobi step's block fits LDS)",
+                n_components, MMK_PCA_MAX_COMPONENTS);
+  if (max_iter < 0) return fail(MMK_ERR_INVALID, "pca_eig: max_iter = %d < 0 (0: MMK_PCA_MAX_ITER)", max_iter);
+  if (!c || !components || !variance || !n_iter || !workspace) return fail(MMK_ERR_INVALID, "pca_eig: bad arguments (null pointer)");
+  if (pc_misaligned(c, 8) || pc_misaligned(components, 8) || pc_misaligned(variance, 8) || pc_misaligned(workspace, 8))
+    return fail(MMK_ERR_INVALID, "pca_eig: c, components, variance and the workspace must be 8-byte aligned");
+  if (workspace_bytes < mmk_pca_eig_workspace_bytes(d, n_components))
+    return fail(MMK_ERR_WORKSPACE, "pca_eig: the workspace has %zu bytes, %zu are needed", workspace_bytes,
+                mmk_pca_eig_workspace_bytes(d, n_components));
+  hipStream_t st = (hipStream_t)stream;
+  const int b = pc_block(d, n_components);
+  const int cap = max_iter > 0 ? max_iter : MMK_PCA_MAX_ITER;
+  const int64_t db = (int64_t)d * b;
+  double* y = static_cast<double*>(workspace);
+  double* qp = y + db;
+  double* z = qp + db;
+  double* q = z + db;
+  double* h = q + db;
+  double* w = h + b * b;
+  double* w2 = w + b * b;
+  double* theta = w2 + b * b;
+  double* rowsum = theta + b;
+  double* resid = rowsum + d;
+  double* stat = resid + n_components;                   // |C|_inf, the last residual, then the flag
+  int32_t* done = reinterpret_cast<int32_t*>(stat + 2);
+  const dim3 wg(256), wide(kPcWide), per_elem((unsigned)((db + 255) / 256));
+  MMK_HIP(hipMemsetAsync(stat, 0, 4 * sizeof(double), st));
+  hipLaunchKernelGGL(pca_start_kernel, per_elem, wg, 0, st, d, b, y);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pca_rowsum_kernel, dim3((unsigned)d), wg, 0, st, c, d, rowsum);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pca_cnorm_kernel, dim3(1), dim3(64), 0, st, rowsum, d, stat);
+  MMK_HIP(hipGetLastError());
+  struct {
+    double cnorm, resid;
+    int32_t done, pad;
+  } host = {0.0, 0.0, 0, 0};
+  int it = 0;
+  while (it < cap && !host.done) {
+    ++it;
+    hipLaunchKernelGGL(pca_qr_kernel, dim3(1), wide, 0, st, d, b, y, qp, done);
+    MMK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(pca_cq_kernel, dim3((unsigned)((d + 15) / 16), (unsigned)((b + 15) / 16)), wg, 0, st, c, d, b, qp, z, done);
+    MMK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(pca_h_kernel, dim3((unsigned)b), wide, 0, st, d, b, qp, z, h, done);
+    MMK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(pca_jacobi_kernel, dim3(1), wide, 0, st, b, h, w, w2, theta, done);
+    MMK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(pca_rotate_kernel, per_elem, wg, 0, st, d, b, qp, z, w2, q, y, done);
+    MMK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(pca_resid_kernel, dim3((unsigned)n_components), wg, 0, st, d, b, q, y, theta, resid, done);
+    MMK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(pca_check_kernel, dim3(1), dim3(64), 0, st, n_components, it, resid, stat, done);
+    MMK_HIP(hipGetLastError());
+    if (it % kPcPoll == 0 || it == cap) {
+      MMK_HIP(hipMemcpyAsync(&host, stat, sizeof(host), hipMemcpyDeviceToHost, st));
+      MMK_HIP(hipStreamSynchronize(st));
+      if (host.resid != host.resid) break;              // NaN: no later iteration mends it
+    }
+  }
+  if (!host.done)
+    return fail(MMK_ERR_CONVERGENCE,
+                "pca_eig: %d iterations of the subspace iteration left a residual of %.3e, the stop rule asks for %.3e (= %.0e |C|_inf) "
+                "over the first %d of %d columns",
+                it, host.resid, kPcTol * host.cnorm, kPcTol, n_components, b);
+  *n_iter = host.done;
+  hipLaunchKernelGGL(pca_finish_kernel, dim3((unsigned)n_components), wg, 0, st, d, b, q, theta, components, variance);
+  MMK_HIP(hipGetLastError());
+  return MMK_OK;
+}
+
+extern "C" int mmk_pca_project_f32(const float* y, int64_t y_row_stride, int64_t m, int32_t d, const double* mean, const double* scale,
+                                   const double* components, int32_t n_components, float* out, int64_t out_row_stride, mmk_stream_t stream) {
+  using namespace mmk;
+  if (m < 1 || d < 1 || n_components < 1)
+    return fail(MMK_ERR_INVALID, "pca_project: m = %lld rows, d = %d columns, n_components = %d (all at least 1)", (long long)m, d, n_components);
+  if (d > MMK_PCA_MAX_D) return fail(MMK_ERR_UNSUPPORTED, "pca_project: d = %d columns, the limit is %d (MMK_PCA_MAX_D)", d, MMK_PCA_MAX_D);
+  if (n_components > MMK_PCA_MAX_COMPONENTS)
+    return fail(MMK_ERR_UNSUPPORTED, "pca_project: n_components = %d, the limit is %d (MMK_PCA_MAX_COMPONENTS)", n_components,
+                MMK_PCA_MAX_COMPONENTS);
+  if ((m + kPjRows - 1) / kPjRows > 0x7fffffffLL)
+    return fail(MMK_ERR_UNSUPPORTED, "pca_project: %lld rows are more than one launch takes", (long long)m);
+  if (!y || !mean || !scale || !components || !out || y_row_stride < 0 || out_row_stride < n_components)
+    return fail(MMK_ERR_INVALID, "pca_project: bad arguments (null pointer, negative stride %lld or an output stride %lld below n_components)",
+                (long long)y_row_stride, (long long)out_row_stride);
+  if (pc_misaligned(y, 4) || pc_misaligned(out, 4) || pc_misaligned(mean, 8) || pc_misaligned(scale, 8) || pc_misaligned(components, 8))
+    return fail(MMK_ERR_INVALID, "pca_project: y and out must be 4-byte aligned, mean, scale and components 8-byte aligned");
+  hipLaunchKernelGGL(pca_project_kernel, dim3((unsigned)((m + kPjRows - 1) / kPjRows)), dim3(256), 0, (hipStream_t)stream, y, y_row_stride, m, d, mean,
+                     scale, components, n_components, out, out_row_stride);
+  MMK_HIP(hipGetLastError());
+  return MMK_OK;
+}

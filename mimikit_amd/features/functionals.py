@@ -22,6 +22,8 @@ here:
 * ``Envelop`` / ``EnvelopBank`` / ``Interpolate`` / ``Derivative`` (:794-1004), the envelope followers the reference's
   ``Samplifyer`` is built on: frame energies as an epilogue of the STFT kernels (``native.stft_energy``: the spectrogram
   is never written), interpolation and the lagged-difference stencil in ``csrc/envelope.hip``.  Results stay on the device.
+* ``PCA`` (:1114-1138), the dimension reduction of the clusterizer's pre-processing pipeline: column statistics, an fp64 MFMA
+  covariance, a block subspace iteration for the leading eigenvectors and the projection, all in ``csrc/pca.hip``.
 * float64 tensors are computed in fp32 on the device (the kernels are fp32; the reference computes in the input's
   dtype, so float64 mu-law codes may differ from it for inputs within one fp32 ulp of a bin edge).
 """
@@ -39,6 +41,7 @@ from .item_spec import Frame, Sample, Unit, convert
 __all__ = [
     "Continuous", "Discrete", "Functional", "Identity", "Compose", "FileToSignal", "RemoveDC", "Normalize", "Emphasis", "Deemphasis",
     "MuLawCompress", "MuLawExpand", "STFT", "ISTFT", "MagSpec", "GLA", "Resample", "Envelop", "EnvelopBank", "Interpolate", "Derivative",
+    "PCA",
 ]
 
 N_FFT = 2048
@@ -791,6 +794,94 @@ class EnvelopBank(Functional):
 
     def torch_func(self, inputs):
         return torch.cat([e(inputs) for e in self.envelops], dim=-1)
+
+    @property
+    def inv(self) -> Functional:
+        return Identity()
+
+
+@dtc.dataclass
+class PCA(Functional):
+    """reference :1114-1138: ``sklearn.decomposition.PCA(n_components).fit_transform(StandardScaler().fit_transform(x))`` for (N, D) float32
+    frames on the device, computed in float64 and returned as (N, n_components) float32 scores (``csrc/pca.hip``):
+
+        native.pca_colstats   mean and population standard deviation of every bin (a constant bin gets scale 1, by sklearn's rule), with the
+                              mean sklearn's PCA subtracts after the scaler folded in
+        native.pca_cov        C = Z^T Z / (N - 1), Z = (x - mean_) / scale_, by v_mfma_f64_16x16x4_f64; Z is never written
+        native.pca_eig        the n_components leading eigenvectors of C by block subspace iteration (no D x D eigendecomposition); waits for
+                              the stream every 8 iterations
+        native.pca_project    Z components_^T
+
+    The sign of a component makes its entry of largest magnitude positive: the ``svd_flip(u_based_decision=False)`` of sklearn 1.5 and
+    later (older versions decide by the scores' largest entry, and may return a component and its scores negated).  A component whose
+    eigenvalue is below the solver's resolution (the rank of the frames is below n_components) is some unit vector of C's null space,
+    as it is in sklearn; its scores are zero to about 1e-8 of the largest score.  ``random_seed`` is kept for the YAML form and unused:
+    nothing here is random.  ``fit`` stores ``mean_``, ``scale_``, ``components_`` (n_components, D), ``explained_variance_`` (float64,
+    on the device) and ``n_iter_`` (int); ``transform`` projects any (M, D) float32 device tensor with them."""
+    n_components: int = 16
+    random_seed: int = 42
+
+    def __post_init__(self):
+        self.mean_: Optional[torch.Tensor] = None
+        self.scale_: Optional[torch.Tensor] = None
+        self.components_: Optional[torch.Tensor] = None
+        self.explained_variance_: Optional[torch.Tensor] = None
+        self.n_iter_: Optional[int] = None
+
+    @property
+    def unit(self) -> Optional[Unit]:
+        return None
+
+    @property
+    def elem_type(self) -> Optional[EventType]:
+        return None
+
+    @staticmethod
+    def _frames(x, what: str) -> torch.Tensor:
+        if not isinstance(x, torch.Tensor):
+            raise TypeError(f"{what}: expected a torch.Tensor, got {type(x)}")
+        if x.dtype != torch.float32:
+            raise TypeError(f"{what} takes float32 frames on the HIP path, got {x.dtype}")
+        if x.dim() != 2 or x.shape[1] < 1:
+            raise ValueError(f"{what}: x must be (N, D >= 1) frames, got shape {tuple(x.shape)}")
+        return x
+
+    def fit(self, x: torch.Tensor) -> "PCA":
+        from .. import native
+        x = self._frames(x, "PCA")
+        n, d = x.shape
+        k = int(self.n_components)
+        if n < 2:
+            raise ValueError(f"PCA: N = {n} frames, at least 2 are needed (the covariance divides by N - 1)")
+        if not 1 <= k <= min(n, d):
+            raise ValueError(f"PCA: n_components = {k} must lie in [1, min(N, D) = {min(n, d)}]")
+        if d > native.PCA_MAX_D:
+            raise NotImplementedError(f"PCA: D = {d} bins, the limit of the HIP path is {native.PCA_MAX_D} (native.PCA_MAX_D)")
+        if k > native.PCA_MAX_COMPONENTS:
+            raise NotImplementedError(f"PCA: n_components = {k}, the limit of the HIP path is {native.PCA_MAX_COMPONENTS} "
+                                      "(native.PCA_MAX_COMPONENTS)")
+        native.require_device(x)
+        self.mean_, self.scale_ = native.pca_colstats(x)
+        c = native.pca_cov(x, self.mean_, self.scale_)
+        self.components_, self.explained_variance_, self.n_iter_ = native.pca_eig(c, k)
+        return self
+
+    def transform(self, y: torch.Tensor) -> torch.Tensor:
+        from .. import native
+        if self.components_ is None:
+            raise RuntimeError("PCA.transform before PCA.fit")
+        y = self._frames(y, "PCA.transform")
+        if y.shape[0] < 1 or y.shape[1] != self.mean_.shape[0]:
+            raise ValueError(f"PCA.transform: y must be (M >= 1, D = {self.mean_.shape[0]}), got shape {tuple(y.shape)}")
+        native.require_device(y)
+        return native.pca_project(y, self.mean_, self.scale_, self.components_)
+
+    def np_func(self, inputs):
+        raise NotImplementedError("PCA runs on device tensors only (csrc/pca.hip): pass a float32 tensor on the HIP device; this package has "
+                                  "no CPU path")
+
+    def torch_func(self, inputs):
+        return self.fit(inputs).transform(inputs)
 
     @property
     def inv(self) -> Functional:

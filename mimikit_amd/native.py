@@ -175,6 +175,13 @@ _SIGNATURES = {
     "mmk_half_neg_sqnorm_f32": (i32, [vp, i64, i64, i32, vp, vp]),
     "mmk_edge_components_workspace_bytes": (C.c_size_t, [i64]),
     "mmk_edge_components_i64": (i32, [vp, vp, i64, i64, vp, vp, vp, C.c_size_t, vp]),
+    "mmk_pca_colstats_workspace_bytes": (C.c_size_t, [i64, i32]),
+    "mmk_pca_colstats_f64": (i32, [vp, i64, i64, i32, vp, vp, vp, C.c_size_t, vp]),
+    "mmk_pca_cov_workspace_bytes": (C.c_size_t, [i64, i32]),
+    "mmk_pca_cov_f64": (i32, [vp, i64, i64, i32, vp, vp, vp, vp, C.c_size_t, vp]),
+    "mmk_pca_eig_workspace_bytes": (C.c_size_t, [i32, i32]),
+    "mmk_pca_eig_f64": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]),
+    "mmk_pca_project_f32": (i32, [vp, i64, i64, i32, vp, vp, vp, i32, vp, i64, vp]),
     "mmk_stft_n_frames": (i64, [i64, i32, i32, i32]),
     "mmk_stft_mag_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, vp, vp]),
     "mmk_stft_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, i32, i32, vp, vp]),
@@ -679,6 +686,97 @@ def edge_components(src: torch.Tensor, dst: torch.Tensor, n: int):
     check(lib().mmk_edge_components_i64(ptr(src) if n_edges else None, ptr(dst) if n_edges else None, n_edges, n, ptr(labels), ptr(count),
                                         ptr(work), n_work, stream_ptr(src.device)), "mmk_edge_components_i64")
     return labels, count
+
+
+# include/mmk.h: MMK_PCA_* - the widest frames and the most components of the PCA kernels (csrc/pca.hip), the stop rule of the eigen step
+PCA_MAX_D = 4096
+PCA_MAX_COMPONENTS = 64
+PCA_MAX_ITER = 4000
+PCA_TOL = 1e-12
+
+
+def _pca_limits(d: int, n_components: int, what: str):
+    if d > PCA_MAX_D:
+        raise NotImplementedError(f"{what}: D = {d} bins, the limit of the HIP path is {PCA_MAX_D} (native.PCA_MAX_D)")
+    if n_components > PCA_MAX_COMPONENTS:
+        raise NotImplementedError(f"{what}: n_components = {n_components}, the limit of the HIP path is {PCA_MAX_COMPONENTS} "
+                                  "(native.PCA_MAX_COMPONENTS)")
+
+
+def _f64_vector(t: torch.Tensor, shape, what: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != tuple(shape):
+        raise TypeError(f"{what} must be a float64 tensor of shape {tuple(shape)}")
+    require_device(t)
+    return t.contiguous()
+
+
+def pca_colstats(x: torch.Tensor):
+    """x (N, D) fp32 -> (mean (D,), scale (D,)) fp64 on the device: sklearn's StandardScaler statistics (population standard deviation, 1 for
+    a constant column) with the mean that sklearn's PCA subtracts afterwards folded into `mean`"""
+    x = _nnn_frames(x, 2, "pca_colstats")
+    n, d = x.shape
+    if n < 1 or d < 1:
+        raise ValueError(f"pca_colstats: empty input {tuple(x.shape)}")
+    _pca_limits(d, 1, "pca_colstats")
+    mean = torch.empty((d,), dtype=torch.float64, device=x.device)
+    scale = torch.empty((d,), dtype=torch.float64, device=x.device)
+    n_work = lib().mmk_pca_colstats_workspace_bytes(n, d)
+    work = torch.empty((n_work // 8,), dtype=torch.float64, device=x.device)
+    check(lib().mmk_pca_colstats_f64(ptr(x), x.stride(0), n, d, ptr(mean), ptr(scale), ptr(work), n_work, stream_ptr(x.device)),
+          "mmk_pca_colstats_f64")
+    return mean, scale
+
+
+def pca_cov(x: torch.Tensor, mean: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """x (N >= 2, D) fp32, mean and scale (D,) fp64 -> C (D, D) fp64 = Z^T Z / (N - 1), Z = (x - mean) / scale; Z is never written"""
+    x = _nnn_frames(x, 2, "pca_cov")
+    n, d = x.shape
+    if n < 2 or d < 1:
+        raise ValueError(f"pca_cov: x must be (N >= 2, D >= 1), got {tuple(x.shape)}")
+    _pca_limits(d, 1, "pca_cov")
+    mean, scale = _f64_vector(mean, (d,), "pca_cov: mean"), _f64_vector(scale, (d,), "pca_cov: scale")
+    c = torch.empty((d, d), dtype=torch.float64, device=x.device)
+    n_work = lib().mmk_pca_cov_workspace_bytes(n, d)
+    work = torch.empty((n_work // 8,), dtype=torch.float64, device=x.device)
+    check(lib().mmk_pca_cov_f64(ptr(x), x.stride(0), n, d, ptr(mean), ptr(scale), ptr(c), ptr(work), n_work, stream_ptr(x.device)),
+          "mmk_pca_cov_f64")
+    return c
+
+
+def pca_eig(c: torch.Tensor, n_components: int, max_iter: int = 0):
+    """c (D, D) fp64 symmetric -> (components (n_components, D), variance (n_components,), n_iter): the eigenpairs of the largest
+    eigenvalues, falling, each vector's entry of largest magnitude positive.  Block subspace iteration to PCA_TOL |C|_inf; the call waits
+    for the stream every 8 iterations; reaching ``max_iter`` (0: PCA_MAX_ITER) raises RuntimeError with the residual reached"""
+    d = c.shape[0] if isinstance(c, torch.Tensor) and c.dim() == 2 else -1
+    c = _f64_vector(c, (d, d), "pca_eig: c")
+    n_components, max_iter = int(n_components), int(max_iter)
+    if d < 1 or not 1 <= n_components <= d or max_iter < 0:
+        raise ValueError(f"pca_eig: n_components = {n_components} must lie in [1, D = {d}], max_iter = {max_iter} at 0 or above")
+    _pca_limits(d, n_components, "pca_eig")
+    components = torch.empty((n_components, d), dtype=torch.float64, device=c.device)
+    variance = torch.empty((n_components,), dtype=torch.float64, device=c.device)
+    n_iter = i32(0)
+    n_work = lib().mmk_pca_eig_workspace_bytes(d, n_components)
+    work = torch.empty((n_work // 8,), dtype=torch.float64, device=c.device)
+    check(lib().mmk_pca_eig_f64(ptr(c), d, n_components, max_iter, ptr(components), ptr(variance), C.byref(n_iter), ptr(work), n_work,
+                                stream_ptr(c.device)), "mmk_pca_eig_f64")
+    return components, variance, int(n_iter.value)
+
+
+def pca_project(y: torch.Tensor, mean: torch.Tensor, scale: torch.Tensor, components: torch.Tensor) -> torch.Tensor:
+    """y (M, D) fp32, mean and scale (D,), components (k, D) fp64 -> (M, k) fp32 = ((y - mean) / scale) components^T, summed in fp64"""
+    y = _nnn_frames(y, 2, "pca_project")
+    m, d = y.shape
+    k = components.shape[0] if isinstance(components, torch.Tensor) and components.dim() == 2 else -1
+    if m < 1 or d < 1 or k < 1:
+        raise ValueError(f"pca_project: y {tuple(y.shape)}, {k} components")
+    _pca_limits(d, k, "pca_project")
+    mean, scale = _f64_vector(mean, (d,), "pca_project: mean"), _f64_vector(scale, (d,), "pca_project: scale")
+    components = _f64_vector(components, (k, d), "pca_project: components")
+    out = torch.empty((m, k), dtype=torch.float32, device=y.device)
+    check(lib().mmk_pca_project_f32(ptr(y), y.stride(0), m, d, ptr(mean), ptr(scale), ptr(components), k, ptr(out), out.stride(0),
+                                    stream_ptr(y.device)), "mmk_pca_project_f32")
+    return out
 
 
 def _rows(x: torch.Tensor) -> torch.Tensor:
