@@ -121,7 +121,8 @@ __device__ __forceinline__ void run_stage(const WnLpipeArgs& a, int clip, int st
     asm volatile("" : "+v"(wt[0]), "+v"(wt[1]), "+v"(b0), "+v"(b2), "+v"(bt));
   }
   if constexpr (FIRST) {
-    for (int i = tid; i < kQ * kC; i += kLpThreads) embs[i] = a.emb[i];
+    // (the table as bound holds the network's own classes: rows beyond them are zeros here, never read from behind the table's end)
+    for (int i = tid; i < kQ * kC; i += kLpThreads) embs[i] = i < a.emb_rows * kC ? a.emb[i] : 0.f;
   }
   // Is the stage I hand over to on my XCD?  Then my granules may stay in the XCD's L2 (plain stores; its CUs' sc1 loads find them there)
   // instead of being written through to memory.  Every workgroup registers its XCC id, then reads its successor's.

@@ -1057,7 +1057,7 @@ static int run_persistent(mmk_wavenet_plan* p, const WnCall& call, int64_t tau0,
       k.Bmax = p->Bmax;
       k.condall = p->C1 > 0 ? p->condall : nullptr; k.cond_steps = p->kCondBlock;
       k.kcA = 2 * (p->C / 16) + (int)round_up(p->C1, 16) / 16;
-      k.emb = p->emb; k.idx = (int64_t*)call.in0; k.idx_rs = call.in0_rs;
+      k.emb = p->emb; k.emb_rows = c.q_levels; k.idx = (int64_t*)call.in0; k.idx_rs = call.in0_rs;
       k.fc0_wp = p->lp_mlp0.Wp; k.fc0_bias = p->lp_mlp0.bias; k.fc2_wp = p->lp_mlp1.Wp; k.fc2_bias = p->lp_mlp1.bias;
       k.temperature = call.temperature;
       k.uniforms = call.uniforms ? call.uniforms + done : nullptr;

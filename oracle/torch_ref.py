@@ -570,10 +570,11 @@ class SampleRNNOracle:
 
 
     def _generate_streams(self, prompts, n_steps, temperature, uniforms, keep_logits, forced):
-        """several inputs / targets: one stream per input, output k written into stream k; ``uniforms`` (targets, batch, n_steps)"""
-        self.before_generate(prompts)
+        """several inputs / targets: one stream per input, output k written into stream k; ``uniforms`` (targets, batch, n_steps).  An input
+        no target feeds may be given for the whole prior + n_steps (a dataloader's own stream) instead of the prompt alone"""
         prior = prompts[0].size(1)
-        streams = [torch.cat([p, torch.zeros(p.size(0), n_steps, dtype=p.dtype)], dim=1) for p in prompts]
+        self.before_generate(tuple(p[:, :prior] for p in prompts))
+        streams = [p if p.size(1) == prior + n_steps else torch.cat([p, torch.zeros(p.size(0), n_steps, dtype=p.dtype)], dim=1) for p in prompts]
         hist = streams if forced is None else list(forced)
         n_tgt = len(self.heads) if self.heads is not None else 1
         logs = [[] for _ in range(n_tgt)]

@@ -19,9 +19,20 @@ Defects are variants of the float64 run, one at a time; each must leave tol_max 
 (check_near_miss), or the envelope is too loose to see what a kernel really gets wrong:
   (a) one bias entry dropped (the one of median magnitude: a typical entry, neither tame nor extreme): a recurrent bias_hh for SampleRNN and
       Seq2Seq, a conv_skip.bias for WaveNet
-  (b) the weights of one layer scaled by 1 + 1e-4
+  (b) the weights of one layer scaled by 1 + 1e-4: the dilated convolution of the middle layer (WaveNet), the decoder's first recurrent
+      matrix (Seq2Seq); for SampleRNN, by one rule for every case, the recurrent matrix weight_hh of the LAST stacked layer of the tier right
+      above the bottom - the tier that steps most often and the layer whose state the up-sampler reads, so the scaled product is taken once per
+      frame of that tier and reaches the compared row through one up-sampler only (tier 0's first layer, the choice before the option cases,
+      steps fs0 / fs[-2] times less often and, under stacked layers, is damped by every layer above it: at frame sizes 16, 8, 8 with three
+      stacked LSTM layers it moved the compared rows by 0.15 tol_max, the rule's choice moves them by 7 tol_max)
   (c) the last clip's rows replaced by the second-to-last clip's (a ragged tile that reads its neighbour)
   (d) one clip's window one step stale
+
+The option cases (WAVENET_OPTION_CASES, WAVENET_HEAD_CASES, MULTI_CASES, SRNN_OPTION_CASES, S2S_OPTION_CASES: every network option the plans
+branch on, on the per-layer launch path or the padded heads of the pipelines) add option defects, one per option of the case (the opt_*
+generators below; each says which device mistake it stands for).  They too are float64 variants, expressed through the state dict, the inputs
+or the oracle's keywords only, and each must leave tol_max.  A network of several targets has one output tensor, one E and one tolerance per
+target; a defect has left the envelope when it leaves tol_max of any one target.
 """
 import functools
 from typing import NamedTuple
@@ -60,8 +71,8 @@ KERNEL_FORMULAS = dict(sigmoid=k_sigmoid, tanh=k_tanh, mish=k_mish)
 
 
 # ---- networks ------------------------------------------------------------------------------------------------------------------------------------------
-def _wavenet(C, blocks, mlp_dim, seed, cond_dims=()):
-    io = H.mu_emb(mlp_dim=mlp_dim)
+def _wavenet(C, blocks, mlp_dim, seed, cond_dims=(), q=256):
+    io = H.mu_emb(mlp_dim=mlp_dim, q_levels=q)
     kw = {}
     if cond_dims:
         ext = mmk.Extractor("signal", mmk.FileToSignal(16000))
@@ -90,12 +101,48 @@ def _s2s(dim, hop, layers, seed, res=False, ds="edge_sum", us="linear_resample")
     return net, sd, dict(downsampling=ds, upsampling=us, enc_residuals=res, dec_residuals=res)
 
 
-def _s2s_classes():
+def _s2s_classes(tag="mlp0", hop=4):
     import warnings
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        net, sd, hop, arch = H.s2s_mulaw("mlp0", model_dim=128, mlp_dim=128)
-    assert hop == 4
+        net, sd, got, arch = H.s2s_mulaw(tag, model_dim=128, mlp_dim=128)
+    assert got == hop
+    return net, sd, arch
+
+
+def _s2s_stack(tag, dim, hop, seed, inputs=1):
+    """a network of helpers.S2S_STACKS (or the plain one, tag None) at another width and hop, with `inputs` magnitude-frame inputs added up"""
+    import warnings
+    kw = dict(H.S2S_STACKS[tag]) if tag else {}
+    io = mmk.IOSpec.magspec_io(mmk.IOSpec.MagSpecIOConfig(n_fft=128, hop_length=32))
+    io = mmk.IOSpec(inputs=(io.inputs[0],) * inputs, targets=io.targets)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        net = mmk.Seq2SeqLSTMNetwork.from_config(mmk.Seq2SeqLSTMNetwork.Config(io_spec=io, model_dim=dim, hop=hop, **kw)).eval()
+    sd = load_recipe(net, seed=seed, gain=1.5)
+    return net, sd, dict(downsampling=kw.get("enc_downsampling", "edge_sum"), enc_residuals=kw.get("enc_apply_residuals", False),
+                         dec_residuals=kw.get("dec_apply_residuals", False))
+
+
+def _no_n_cond(made):
+    """the helpers' (net, state dict, keywords) with the `n_cond` the oracle's callers pass themselves taken out of the keywords"""
+    net, sd, arch = made
+    arch = dict(arch)
+    arch.pop("n_cond", None)
+    return net, sd, arch
+
+
+def _mlp_head(tag):
+    net, sd, _, arch = H.mlp_head_case(tag)
+    return net, sd, arch
+
+
+def _multi_io(tag):
+    """helpers.multi_io with the oracle's keywords as one dict: a WaveNet's kernels and dilations beside the others"""
+    net, sd, arch, _ = H.multi_io(tag)
+    if not isinstance(arch, dict):
+        ks, ds, kw = arch
+        arch = dict(kw, kernels=ks, dilations=ds)
     return net, sd, arch
 
 
@@ -139,8 +186,23 @@ def _resident(warmups=None):
     return lambda p, k: p.resident_blocks() == k and (warmups is None or p.resident_warmups() == warmups)
 
 
-def _s2s_resident(layers):
-    return lambda p, k: p.resident_launches() == k * 2 * layers
+def _s2s_resident(layers, dec=None):
+    """every bi-LSTM layer of every step as one resident launch: `layers` per side, or `layers` in the encoder and `dec` in the decoder"""
+    return lambda p, k: p.resident_launches() == k * (layers + (layers if dec is None else dec))
+
+
+def flags(case, p):
+    """what the plan reports about the kernels it took, for the record a test prints"""
+    if case.kind in ("wavenet", "wavenet_frames"):
+        return {n: bool(getattr(p, n)) for n in ("persistent", "chain", "layer_pipelined", "stage_pipelined", "batch_pipelined", "pair_visits")}
+    if case.kind == "srnn":
+        return dict(bottom_kernel=p.bottom_kernel(), resident_blocks=p.resident_blocks())
+    return dict(resident_launches=p.resident_launches())
+
+
+def streams(x):
+    """a tuple of tensors as it is, one tensor as a tuple of one"""
+    return tuple(x) if isinstance(x, (tuple, list)) else (x,)
 
 
 def _s2s_per_frame(p, k):
@@ -149,11 +211,16 @@ def _s2s_per_frame(p, k):
 
 class Case:
     """kind: 'wavenet' | 'wavenet_frames' | 'srnn' | 's2s' | 's2s_classes'; make() -> (net, state dict, the oracle's keywords); env: the plan
-    switches; parts: the lengths of the consecutive generate_block calls (Seq2Seq: steps of `hop` frames per call); ran(plan, blocks so far)"""
+    switches; parts: the lengths of the consecutive generate_block calls (Seq2Seq: steps of `hop` frames per call); ran(plan, blocks so far);
+    cond: real-valued inputs beside the first (WaveNet: conditioning features, Seq2Seq: further frame inputs the network adds up), given for
+    the whole length; q: the class count of every class stream (one entry: the prompt's; several: a network of several class inputs, the
+    first `targets` of which the loop writes and the others of which are given for the whole length); options: the case's option defects"""
 
-    def __init__(self, id, kind, make, clips, parts, env, ran, cond=0, hop=None, seed=0, forced_split=None):
+    def __init__(self, id, kind, make, clips, parts, env, ran, cond=0, hop=None, seed=0, forced_split=None, q=(256,), targets=1, options=()):
         self.id, self.kind, self._make, self.clips, self.parts, self.env, self.ran = id, kind, make, clips, tuple(parts), dict(env), ran
         self.cond, self.hop, self.seed = cond, hop, seed
+        self.q, self.targets, self.options = tuple(q), targets, tuple(options)
+        self.multi = len(self.q) > 1              # histories and outputs are tuples: one stream per class input, one output per target
         # split-K cases: (rows, columns, K, forced split) of the tiled GEMM the switch reaches; the plan reports nothing about it, so the
         # device test also runs the case without the switch and requires other bits in the first step's frames
         self.forced_split = forced_split
@@ -205,8 +272,10 @@ class Case:
         if self.kind == "wavenet_frames":
             return torch.rand(self.clips, P, 33, generator=g), ()
         if self.kind == "s2s":
-            return torch.rand(self.clips, P, 65, generator=g), ()
-        prompt = torch.randint(0, 256, (self.clips, P), generator=g)
+            return torch.rand(self.clips, P, 65, generator=g), tuple(torch.rand(self.clips, P + self.n, 65, generator=g) for _ in range(self.cond))
+        if self.multi:
+            return tuple(torch.randint(0, q, (self.clips, P if k < self.targets else P + self.n), generator=g) for k, q in enumerate(self.q)), ()
+        prompt = torch.randint(0, self.q[0], (self.clips, P), generator=g)
         return prompt, tuple(torch.rand(self.clips, P + self.n, 12, generator=g) for _ in range(self.cond))
 
 
@@ -256,8 +325,9 @@ SRNN_CASES = [
 ]
 
 
-def _s2s_case(tag, dim, hop, clips, layers, env, ran, forced_split=None, **kw):
-    return Case(tag, "s2s", lambda: _s2s(dim, hop, layers, 7 + dim + hop, **kw), clips, (1, 1, 1), env, ran, hop=hop, forced_split=forced_split)
+def _s2s_case(tag, dim, hop, clips, layers, env, ran, forced_split=None, options=(), **kw):
+    return Case(tag, "s2s", lambda: _s2s(dim, hop, layers, 7 + dim + hop, **kw), clips, (1, 1, 1), env, ran, hop=hop, forced_split=forced_split,
+                options=options)
 
 
 def gemm_k_split(M, N, K, forced=0):
@@ -291,7 +361,7 @@ S2S_CASES = [
     Case("classes", "s2s_classes", _s2s_classes, 24, (1, 1, 1), {}, _s2s_resident(1), hop=4),
 ]
 
-ALL_CASES = [("wavenet", c) for c in WAVENET_CASES] + [("srnn", c) for c in SRNN_CASES] + [("s2s", c) for c in S2S_CASES]
+#   (the option cases and ALL_CASES: at the end of the module, behind the option defects they name)
 
 
 # ---- the oracle, teacher-forced ----------------------------------------------------------------------------------------------------------------------
@@ -299,21 +369,28 @@ def to64(sd):
     return {k: (v.double() if torch.is_floating_point(v) else v) for k, v in sd.items()}
 
 
-def reference(case, sd, hist, conds=()):
-    """the oracle's outputs of the case's n generated steps on the history `hist` (prompt + n steps), in the dtype of `sd`: raw head outputs
-    (clips, n, classes + 1) or frames (clips, n, bins)"""
-    n, P, arch = case.n, case.P, case.arch
+def reference(case, sd, hist, conds=(), arch=None):
+    """the oracle's outputs of the case's n generated steps on the history `hist` (prompt + n steps; a tuple of streams for a network of several
+    class inputs), in the dtype of `sd`: raw head outputs (clips, n, classes + 1) or frames (clips, n, bins) - for a network of several class
+    inputs the tuple of its targets' raw outputs.  `arch`: other keywords for the oracle than the case's own (an option defect)"""
+    n, P = case.n, case.P
+    arch = case.arch if arch is None else arch
     sd = O.fold_weight_norm(sd)                    # (in the dtype of `sd`; the Seq2Seq decoder with residuals is weight-normed)
     if case.kind in ("wavenet", "wavenet_frames"):
         rf = P - 3
         lo, hi = P - rf, P + n - 1                 # ONE forward over the n windows: output j belongs to the window that starts at lo + j
         kw = dict(arch, embedding=False) if case.kind == "wavenet_frames" else arch
-        return O.wavenet_window_forward(sd, (hist[:, lo:hi], *[c[:, lo:hi] for c in conds]), n_cond=len(conds), every_position=True, **kw)
+        inputs = tuple(x[:, lo:hi] for x in (*streams(hist), *conds))
+        return O.wavenet_window_forward(sd, inputs, n_cond=len(inputs) - 1, every_position=True, **kw)
     if case.kind == "srnn":
+        if case.multi:
+            return O.SampleRNNOracle(sd, **arch).generate(tuple(x[:, :P] for x in hist), n, keep_logits=True, forced=tuple(hist))[1]
         return O.SampleRNNOracle(sd, **arch).generate(hist[:, :P], n, keep_logits=True, forced=hist)[1]
     outs = []
     for t in range(P, P + n, case.hop):
         x = hist[:, t - case.hop:t]
+        for c in conds:                            # (further frame inputs: the network adds them up in front of the encoder)
+            x = x + c[:, t - case.hop:t]
         outs.append(O.s2s_step(sd, x, case.hop, return_raw=True, **arch)[1] if case.kind == "s2s_classes" else O.s2s_step(sd, x, case.hop, **arch))
     return torch.cat(outs, 1)
 
@@ -321,12 +398,20 @@ def reference(case, sd, hist, conds=()):
 def free_run(case, prompt, conds=()):
     """the fp32 oracle's own free-running history"""
     sd, arch = O.fold_weight_norm(case.sd), case.arch
+    if case.kind == "wavenet" and case.multi:
+        return (*O.wavenet_generate_streams(sd, prompt, case.n, **arch), *prompt[case.targets:])
     if case.kind == "wavenet":
         return O.wavenet_generate(sd, prompt, conds, case.n, **arch)
     if case.kind == "wavenet_frames":
         return O.wavenet_generate_frames(sd, prompt, case.n, **arch)
     if case.kind == "srnn":
         return O.SampleRNNOracle(sd, **arch).generate(prompt, case.n)
+    if conds:
+        hop, P = case.hop, case.P
+        frames = torch.cat([prompt, torch.zeros(case.clips, case.n, 65)], 1)
+        for t in range(P, P + case.n, hop):
+            frames[:, t:t + hop] = O.s2s_step(sd, frames[:, t - hop:t] + sum(c[:, t - hop:t] for c in conds), hop, **arch)
+        return frames
     out = O.s2s_generate(sd, prompt, case.n, case.hop, **arch)
     return out.long() if case.kind == "s2s_classes" else out
 
@@ -339,14 +424,24 @@ class Envelope(NamedTuple):
 
 
 def envelope(history, case, conds=()):
-    """the three teacher-forced runs on `history`: (R64, E, R32, R32k), every generated step"""
+    """the three teacher-forced runs on `history`: (R64, E, R32, R32k), every generated step - one Envelope, or for a network of several class
+    inputs the list of its targets' Envelopes"""
     sd = case.sd
     R64 = reference(case, to64(sd), history, conds)
     R32 = reference(case, sd, history, conds)
     with O.activation_formulas(**KERNEL_FORMULAS):
         R32k = reference(case, sd, history, conds)
-    assert R64.dtype == torch.float64 and R32.dtype == torch.float32 and R32k.dtype == torch.float32
-    return Envelope(R64, torch.maximum((R32.double() - R64).abs(), (R32k.double() - R64).abs()), R32, R32k)
+    envs = []
+    for r64, r32, r32k in zip(streams(R64), streams(R32), streams(R32k)):
+        assert r64.dtype == torch.float64 and r32.dtype == torch.float32 and r32k.dtype == torch.float32
+        envs.append(Envelope(r64, torch.maximum((r32.double() - r64).abs(), (r32k.double() - r64).abs()), r32, r32k))
+    assert len(envs) == case.targets
+    return envs if case.multi else envs[0]
+
+
+def per_target(x):
+    """the per-target list of a case's envelopes, outputs or defect outputs (one target: a list of one)"""
+    return list(x) if isinstance(x, (tuple, list)) and not isinstance(x, Envelope) else [x]
 
 
 def rms(x):
@@ -390,9 +485,14 @@ def check_picks(picks, R64, tol_max, what="picks"):
 
 
 def check_near_miss(defect, R64, tol_max, what):
-    """the float64 run with one defect must leave tol_max somewhere among the compared elements (NaN counts as leaving it)"""
-    assert bool((~((defect - R64).abs() <= tol_max)).any()), \
-        f"{what}: the defect moves the outputs by at most {float((defect - R64).abs().max()):.3e}, inside tol_max {tol_max:.3e} - the envelope is too loose"
+    """the float64 run with one defect must leave tol_max somewhere among the compared elements (NaN counts as leaving it).  Several targets:
+    lists with one entry per target, each target with its own tol_max; the defect has to leave one of them"""
+    defect, R64 = per_target(defect), per_target(R64)
+    tol_max = list(tol_max) if isinstance(tol_max, (tuple, list)) else [tol_max]
+    assert len(defect) == len(R64) == len(tol_max)
+    moved = [float((d - r).abs().max()) for d, r in zip(defect, R64)]
+    assert any(bool((~((d - r).abs() <= t)).any()) for d, r, t in zip(defect, R64, tol_max)), \
+        f"{what}: the defect moves the outputs by at most {moved}, inside tol_max {tol_max} - the envelope is too loose"
 
 
 def _keys(case, sd):
@@ -403,29 +503,313 @@ def _keys(case, sd):
             next(k for k in sd if k.startswith("layers.0.conv_dil") and k.endswith("bias"))
         return bias, next(k for k in sd if k.startswith(f"layers.{L // 2}.conv_dil") and k.endswith("weight"))
     if case.kind == "srnn":
-        return "tiers.0.rnn.bias_hh_l0", "tiers.0.rnn.weight_hh_l0"
+        # (b): the last stacked layer of the tier right above the bottom, for every case (the module docstring says why)
+        return "tiers.0.rnn.bias_hh_l0", f"tiers.{len(arch['frame_sizes']) - 2}.rnn.weight_hh_l{arch.get('n_rnn', 1) - 1}"
     return "dec.lstm.0.bias_hh_l0_reverse", "dec.lstm.0.weight_hh_l0"
+
+
+def _drop(sd, key, entry=None):
+    """(entry, the vector sd[key] with that entry zeroed) - by default the entry of median magnitude"""
+    b = sd[key].clone()
+    entry = int(b.abs().argsort()[b.numel() // 2]) if entry is None else entry
+    b.view(-1)[entry] = 0.0
+    return entry, b
+
+
+def _stale(x, clip=0):
+    """x with one clip's rows one step late"""
+    y = x.clone()
+    y[clip, 1:] = x[clip, :-1]
+    return y
 
 
 def bias_dropped(case, history, conds, entry=None):
     """defect (a): (name, the float64 outputs) with entry `entry` of the case's bias vector zeroed - by default the one of median magnitude"""
     sd64 = O.fold_weight_norm(to64(case.sd))
     bias_key, _ = _keys(case, sd64)
-    b = sd64[bias_key].clone()
-    entry = int(b.abs().argsort()[b.numel() // 2]) if entry is None else entry
-    b.view(-1)[entry] = 0.0
+    entry, b = _drop(sd64, bias_key, entry)
     return f"(a) entry {entry} of {bias_key} dropped", reference(case, {**sd64, bias_key: b}, history, conds)
 
 
 def defects(case, history, conds, R64):
-    """(name, the float64 outputs with that one defect) for the four defects of the module docstring"""
+    """(name, the float64 outputs with that one defect) for the four defects of the module docstring, then the case's option defects.
+    `R64`: the float64 outputs, or the list of them per target - the defects' outputs come in the same form"""
     sd64 = O.fold_weight_norm(to64(case.sd))
     _, weight_key = _keys(case, sd64)
     yield bias_dropped(case, history, conds)
     yield f"(b) {weight_key} scaled by 1 + 1e-4", reference(case, {**sd64, weight_key: sd64[weight_key] * (1 + 1e-4)}, history, conds)
-    c = R64.clone()
-    c[-1] = R64[-2]
-    yield "(c) the last clip's rows are the second-to-last clip's", c
-    stale = history.clone()
-    stale[0, 1:] = history[0, :-1]
+    swapped = []
+    for r in per_target(R64):
+        c = r.clone()
+        c[-1] = r[-2]
+        swapped.append(c)
+    yield "(c) the last clip's rows are the second-to-last clip's", swapped if case.multi else swapped[0]
+    stale = (_stale(history[0]), *history[1:]) if case.multi else _stale(history)
     yield "(d) clip 0's window one step stale", reference(case, sd64, stale, conds)
+    for option in case.options:
+        yield from option(case, sd64, history, conds)
+
+
+# ---- option defects: generators of (name, the float64 outputs with the option subtly off) over (case, folded float64 state dict, history, conds) --
+def _layer_key(case, sd, leaf):
+    """the key of the middle layer's dilated convolution (gated or not) that ends in `leaf`"""
+    L = len(case.arch["kernels"])
+    return next(k for k in sd if k.startswith(f"layers.{L // 2}.conv_dil") and k.endswith(leaf))
+
+
+def _head_biases(case, sd, k=0):
+    """the bias keys of target k's MLP head, in the order of its Linears (dropout modules between them shift the indices)"""
+    p = f"output_module.heads.{k}.estimator.0.fc." if case.kind.startswith("s2s") else f"output_modules.{k}.estimator.0.fc."
+    ns = sorted(int(key[len(p):].split(".")[0]) for key in sd if key.startswith(p) and key.endswith(".bias"))
+    return [f"{p}{n}.bias" for n in ns]
+
+
+def opt_oldest_tap(case, sd, hist, conds):
+    """kernel size 3 or 4: the oldest tap's slice of the middle layer's weight zeroed - a launch path that walks a kernel's taps in the wrong
+    order, or stops one short, as a kernel written for two taps would"""
+    key = _layer_key(case, sd, "weight")
+    w = sd[key].clone()
+    assert w.shape[2] > 2
+    w[:, :, 0] = 0.0
+    yield f"[kernel size] the oldest tap of {key} zeroed", reference(case, {**sd, key: w}, hist, conds)
+
+
+def opt_conditioning(case, sd, hist, conds):
+    """conditioning: clip 0's conditioning input one step stale (a conditioning row read at t - 1: the row of the step before, or of the ragged
+    clip's neighbour in time); with two inputs, also the two raw inputs swapped (their projections laid side by side in the wrong order)"""
+    yield "[conditioning] clip 0's conditioning input one step stale", reference(case, sd, hist, (_stale(conds[0]), *conds[1:]))
+    if len(conds) == 2:
+        yield "[conditioning] the two raw inputs swapped", reference(case, sd, hist, conds[::-1])
+
+
+def opt_affine_bias(case, sd, hist, conds):
+    """affine residuals: the median entry of a middle layer's aff_res.params.bias dropped - one of the three chunks (x_hat, a, b) of the
+    1x1 convolution packed without its bias"""
+    key = f"layers.{len(case.arch['kernels']) // 2}.aff_res.params.bias"
+    entry, b = _drop(sd, key)
+    yield f"[affine residuals] entry {entry} of {key} dropped", reference(case, {**sd, key: b}, hist, conds)
+
+
+def opt_hidden_bias(case, sd, hist, conds):
+    """a deeper head: the median bias entry of the hidden Linear dropped (the hidden blocks share ONE Linear, so in every copy of it) - a
+    head kernel that applies the hidden layer's bias only where the one-layer head has one"""
+    keys = _head_biases(case, sd)[1:-1]
+    assert keys and all(torch.equal(sd[k], sd[keys[0]]) for k in keys)
+    entry, b = _drop(sd, keys[0])
+    yield f"[deeper head] entry {entry} of {keys[0]} dropped", reference(case, {**sd, **{k: b for k in keys}}, hist, conds)
+
+
+def opt_narrow_head(case, sd, hist, conds):
+    """a head narrower than the pipelines' 128 x 256: the bias of the last real class q - 1 dropped, then that of the temperature column q -
+    the two columns that border the padding: a padded column (bias -inf) that leaks into its neighbour, or a temperature read from column 256"""
+    key, q = _head_biases(case, sd)[-1], case.q[0]
+    assert sd[key].numel() == q + 1 and q < 256
+    for entry, what in ((q - 1, "the last class"), (q, "the temperature column")):
+        yield f"[narrow head] the bias of {what} ({entry} of {key}) dropped", reference(case, {**sd, key: _drop(sd, key, entry)[1]}, hist, conds)
+
+
+def opt_targets(case, sd, hist, conds):
+    """several inputs and targets: for every target k > 0, the last bias entry of head k dropped (a second head that reads the first one's
+    bias vector, whose length differs); and the last stream one step stale for clip 0 (a class stream of the step before, or read at the first
+    stream's position)"""
+    for k in range(1, case.targets):
+        key = _head_biases(case, sd, k)[-1]
+        entry = sd[key].numel() - 1
+        yield f"[several targets] the last bias entry of head {k} ({key}) dropped", reference(case, {**sd, key: _drop(sd, key, entry)[1]}, hist, conds)
+    k = len(hist) - 1
+    yield f"[several inputs] stream {k} of clip 0 one step stale", reference(case, sd, (*hist[:k], _stale(hist[k])), conds)
+
+
+def opt_stacked_bias(case, sd, hist, conds):
+    """stacked recurrent layers: the median bias_hh entry of the LAST stacked layer of tier 0 dropped - a loop over the stack that binds layer
+    0's operands for every layer, or stops one layer short"""
+    key = f"tiers.0.rnn.bias_hh_l{case.arch['n_rnn'] - 1}"
+    entry, b = _drop(sd, key)
+    yield f"[stacked layers] entry {entry} of {key} dropped", reference(case, {**sd, key: b}, hist, conds)
+
+
+def _keyword(option, what, **kw):
+    def run(case, sd, hist, conds):
+        yield f"[{option}] {what}", reference(case, sd, hist, conds, arch=dict(case.arch, **kw))
+    return run
+
+
+# h0_init ones run from zeros: a warm-up that clears the state it was told to fill with ones
+opt_h0_zeros = _keyword("h0_init", "the hidden state starts from zeros", h0="zeros")
+# inputs_mode mean run as sum: the 1 / M of the mean left out where the inputs' projections are added up
+opt_mean_as_sum = _keyword("inputs_mode", "mean run as sum", inputs_mode="sum")
+# inputs_mode static_mix run as mean: the learned mixing weights never bound, every input weighted alike
+opt_mix_as_mean = _keyword("inputs_mode", "static_mix run as mean", inputs_mode="mean")
+# layerwise_inputs left out: the embedded input not added to every layer's output
+opt_not_layerwise = _keyword("layerwise_inputs", "the embedded input is not added to the layers' outputs", layerwise_inputs=False)
+
+
+def opt_layer_order(case, sd, hist, conds):
+    """reverse_layer_order: the layers' dilations in build order instead of run order (which layer has its residual 1x1 is fixed by the
+    weights) - a plan that reverses the weights but not the ring geometry"""
+    yield "[reverse_layer_order] the dilations in build order", reference(case, sd, hist, conds, arch=dict(case.arch, dilations=case.arch["dilations"][::-1]))
+
+
+def opt_no_gate(case, sd, hist, conds):
+    """act_g=None: the one activation of a layer evaluated by the gate's function instead of the filter's - a launch path that picks the
+    gate's slot of the activation pair.  (Running the gate itself cannot be expressed: the ungated convolution has half the channels.)"""
+    arch = dict(case.arch, act_f=case.arch.get("act_g", "Sigmoid"))
+    yield f"[no gate] the layers' activation is {arch['act_f']}", reference(case, sd, hist, conds, arch=arch)
+
+
+def opt_gate_swapped(case, sd, hist, conds):
+    """act_f / act_g: the two activations swapped between the filter half and the gate half of a layer's channels"""
+    arch = dict(case.arch, act_f=case.arch["act_g"], act_g=case.arch["act_f"])
+    yield "[activations] act_f and act_g swapped", reference(case, sd, hist, conds, arch=arch)
+
+
+def opt_pooling(case, sd, hist, conds):
+    """Seq2Seq pooling: edge_mean run as mean, edge_sum as sum, sum as edge_sum - they differ only in which frames of the window count: a
+    pooling kernel that takes every frame where it should take the two at the edges, or the reverse"""
+    other = {"edge_mean": "mean", "edge_sum": "sum", "sum": "edge_sum"}[case.arch["downsampling"]]
+    yield f"[pooling] {case.arch['downsampling']} run as {other}", reference(case, sd, hist, conds, arch=dict(case.arch, downsampling=other))
+
+
+def opt_interp(case, sd, hist, conds):
+    """Seq2Seq upsampling interp run as repeat: the encoder's two final states not spread over the decoder's frames (interp has no
+    up-sampling weights, so linear_resample cannot be run on its state dict)"""
+    assert "dec.fc.fc.weight" not in sd
+    yield "[upsampling] interp run as repeat", reference(case, sd, hist, conds, arch=dict(case.arch, upsampling="repeat"))
+
+
+def opt_deepest_bias(case, sd, hist, conds):
+    """asymmetric stacks: the median bias_hh entry of the deepest layer of the longer side dropped - a plan that sizes both stacks by one
+    side's depth never binds that layer's operands"""
+    depth = {side: 1 + max(int(k.split(".")[2]) for k in sd if k.startswith(side + ".lstm.")) for side in ("enc", "dec")}
+    assert depth["enc"] != depth["dec"]
+    side = max(depth, key=depth.get)
+    key = f"{side}.lstm.{depth[side] - 1}.bias_hh_l0"
+    entry, b = _drop(sd, key)
+    yield f"[stacks] entry {entry} of {key} dropped", reference(case, {**sd, key: b}, hist, conds)
+
+
+def opt_second_input(case, sd, hist, conds):
+    """several continuous inputs: clip 0's second input one step stale (swapping the inputs of a sum changes nothing) - the second input read
+    at another frame than the first"""
+    yield "[several inputs] clip 0's second input one step stale", reference(case, sd, hist, (_stale(conds[0]),))
+
+
+# ---- the option cases -----------------------------------------------------------------------------------------------------------------------------------
+def _wn_option_defects(kw):
+    """the option defects of a helpers.WAVENET_OPTIONS / WAVENET_ACTS entry"""
+    out = []
+    if kw.get("kernel_sizes", (2,))[0] > 2:
+        out.append(opt_oldest_tap)
+    if kw.get("cond"):
+        out.append(opt_conditioning)
+    if kw.get("with_affine_residuals"):
+        out.append(opt_affine_bias)
+    if kw.get("io", {}).get("n_mlp_layers"):
+        out.append(opt_hidden_bias)
+    if "act_g" in kw and kw["act_g"] is None:
+        out.append(opt_no_gate)
+    elif "act_f" in kw:
+        out.append(opt_gate_swapped)
+    if kw.get("layerwise_inputs"):
+        out.append(opt_not_layerwise)
+    if kw.get("reverse_layer_order"):
+        out.append(opt_layer_order)
+    return tuple(out)
+
+
+def _wn_stage(batched):
+    return lambda p, k: p.stage_pipelined and p.batch_pipelined == batched
+
+
+_BP = {"MMK_WN_SPIPE": "1", "MMK_WN_BPIPE": "1"}
+# 16 channels, 5 layers (freqnet: 32 channels, 3 layers), 9 clips: past a row group of 8, short of 16, odd; all on the per-layer launch path
+# (`tied` - tie_io_weights - and the dropout head change where the weights come from, not what is computed: the four standing defects only)
+WAVENET_OPTION_CASES = [
+    *[Case(f"opt-{tag}", "wavenet", lambda tag=tag: _no_n_cond(H.wavenet_option(tag)), 9, WN_PARTS, {}, _wn_launches, cond=int(bool(kw.get("cond"))),
+           options=_wn_option_defects(kw)) for tag, kw in H.WAVENET_OPTIONS.items()],
+    *[Case(f"act-{tag}", "wavenet", lambda tag=tag: _no_n_cond(H.wavenet_act(tag)), 9, WN_PARTS, {}, _wn_launches, cond=int(bool(kw.get("cond"))),
+           options=_wn_option_defects(kw)) for tag, kw in H.WAVENET_ACTS.items()],
+    Case("head-wn_relu_dp", "wavenet", lambda: _mlp_head("wn_relu_dp"), 9, WN_PARTS, {}, _wn_launches),
+    Case("head-wn_tanh_2", "wavenet", lambda: _mlp_head("wn_tanh_2"), 9, WN_PARTS, {}, _wn_launches, options=(opt_hidden_bias,)),
+    Case("frames-g1", "wavenet_frames", lambda: H.freqnet("g1"), 9, WN_PARTS, {}, _wn_launches),
+    Case("frames-g2abs", "wavenet_frames", lambda: H.freqnet("g2abs"), 9, WN_PARTS, {}, _wn_launches),
+]
+
+# the pipelines' padded heads: (q, mlp_dim, cond_dims, blocks, clips) of test_wavenet_stage_pipeline_takes_narrower_heads_and_two_conditioning_inputs
+# and (q, mlp_dim, blocks, clips) of test_wavenet_layer_pipeline_takes_narrower_heads (tests/test_gpu_networks.py), with their seeds
+WAVENET_HEAD_CASES = [
+    Case("spipe-narrow-200-100-33", "wavenet", lambda: _wavenet(256, (2, 2, 1), 100, 500 + 200 + 33, (32, 16), q=200), 33, WN_PARTS, _SP, _wn_stage(False),
+         cond=2, q=(200,), options=(opt_narrow_head, opt_conditioning)),
+    Case("bpipe-narrow-200-100-33", "wavenet", lambda: _wavenet(256, (2, 2, 1), 100, 500 + 200 + 33, (32, 16), q=200), 33, WN_PARTS, _BP, _wn_stage(True),
+         cond=2, q=(200,), options=(opt_narrow_head, opt_conditioning)),
+    Case("spipe-narrow-64-40-9", "wavenet", lambda: _wavenet(256, (4,), 40, 500 + 64 + 9, (16,), q=64), 9, WN_PARTS, _SP, _wn_stage(False),
+         cond=1, q=(64,), options=(opt_narrow_head, opt_conditioning)),
+    Case("lpipe-narrow-200-112-40", "wavenet", lambda: _wavenet(64, (4,), 112, 700 + 200, q=200), 40, WN_PARTS, {}, _wn_lpipe, q=(200,),
+         options=(opt_narrow_head,)),
+    Case("lpipe-narrow-64-32-13", "wavenet", lambda: _wavenet(64, (4, 3), 32, 700 + 64, q=64), 13, WN_PARTS, {}, _wn_lpipe, q=(64,),
+         options=(opt_narrow_head,)),
+]
+
+
+def _multi_case(tag):
+    kind, classes, heads, kw = H.MULTI_IO[tag]
+    options = (opt_targets,) + {"mean": (opt_mean_as_sum,), "static_mix": (opt_mix_as_mean,)}.get(kw.get("inputs_mode"), ())
+    if kind == "wavenet":      # (class conditioning streams and further targets: the launch path, csrc/wavenet_plan.hip)
+        return Case(f"multi-{tag}", "wavenet", lambda: _multi_io(tag), 9, WN_PARTS, {}, _wn_launches, q=classes, targets=len(heads), options=options)
+    # (several class streams: the kernels in turns, one launch per op, csrc/srnn_plan.hip)
+    return Case(f"multi-{tag}", "srnn", lambda: _multi_io(tag), 9, SRNN_PARTS, {}, _bottom(LAUNCHES), q=classes, targets=len(heads), options=options)
+
+
+MULTI_CASES = [_multi_case(tag) for tag in H.MULTI_IO]
+WAVENET_MULTI_CASES = [c for c in MULTI_CASES if c.kind == "wavenet"]
+SRNN_MULTI_CASES = [c for c in MULTI_CASES if c.kind == "srnn"]
+
+
+def _srnn_option_defects(kw):
+    out = []
+    if kw.get("n_rnn", 1) > 1:
+        out.append(opt_stacked_bias)
+    if kw.get("io", {}).get("n_mlp_layers"):
+        out.append(opt_hidden_bias)
+    if kw.get("h0_init") == "ones":
+        out.append(opt_h0_zeros)
+    return tuple(out)
+
+
+# hidden 32, 11 clips: the tier and bottom kernels take 128 hidden units and up, so every one of these runs one launch per op and never
+# resident (bottom_kernel 3, resident_blocks 0).  inputs_mode mean / static_mix of ONE input weight it by 1 (ZipReduceVariables): `gru_mean`
+# has no option defect, and `lstm_mix_ones` only the one of h0_init; weight norm and the heads' activations are held by the standing defects
+SRNN_OPTION_CASES = [
+    *[Case(f"opt-{tag}", "srnn", lambda tag=tag: H.srnn_option(tag), 11, SRNN_PARTS, {}, _bottom(LAUNCHES), options=_srnn_option_defects(kw))
+      for tag, kw in H.SRNN_OPTIONS.items()],
+    Case("weight_norm-gru", "srnn", lambda: H.srnn("gru", weight_norm=True), 11, SRNN_PARTS, {}, _bottom(LAUNCHES)),
+    Case("weight_norm-lstm", "srnn", lambda: H.srnn("lstm", weight_norm=True), 11, SRNN_PARTS, {}, _bottom(LAUNCHES)),
+    Case("head-srnn_softplus_dp1d", "srnn", lambda: _mlp_head("srnn_softplus_dp1d"), 11, SRNN_PARTS, {}, _bottom(LAUNCHES)),
+    Case("head-srnn_sigmoid", "srnn", lambda: _mlp_head("srnn_sigmoid"), 11, SRNN_PARTS, {}, _bottom(LAUNCHES)),
+]
+
+
+def _s2s_variant(ds, us):
+    options = ((opt_pooling,) if ds in ("edge_mean", "edge_sum", "sum") else ()) + ((opt_interp,) if us == "interp" else ())
+    return _s2s_case(f"{ds}-{us}", 128, 8, 16, 1, {}, _s2s_resident(1), ds=ds, us=us, options=options)
+
+
+def _s2s_stack_case(tag, enc, dec):
+    return Case(f"stack-{tag}", "s2s", lambda: _s2s_stack(tag, 128, 8, 143), 16, (1, 1, 1), {}, _s2s_resident(enc, dec), hop=8, options=(opt_deepest_bias,))
+
+
+# model_dim 128, hop 8, 16 clips: the smallest resident width, 128 rows (the tiled GEMM); every bi-LSTM layer of every step is one resident launch
+S2S_OPTION_CASES = [
+    *[_s2s_variant(ds, us) for ds, us in H.S2S_VARIANTS if (ds, us) != ("mean", "repeat")],      # (mean-repeat: S2S_CASES)
+    _s2s_stack_case("e2d1", 2, 1), _s2s_stack_case("e1d3", 1, 3), _s2s_stack_case("e3d1res_sum", 3, 1),
+    Case("classes-mlp2_stack", "s2s_classes", lambda: _s2s_classes("mlp2_stack", 2), 16, (1, 1, 1), {}, _s2s_resident(2), hop=2, options=(opt_hidden_bias,)),
+    # (two frame inputs: the network adds them up and has no block path - the device test goes step by step)
+    Case("two_inputs", "s2s", lambda: _s2s_stack(None, 128, 8, 141, inputs=2), 16, (1, 1, 1), {}, _s2s_resident(1), hop=8, cond=1, options=(opt_second_input,)),
+]
+
+WAVENET_ALL = WAVENET_CASES + WAVENET_OPTION_CASES + WAVENET_HEAD_CASES + WAVENET_MULTI_CASES
+SRNN_ALL = SRNN_CASES + SRNN_OPTION_CASES + SRNN_MULTI_CASES
+S2S_ALL = S2S_CASES + S2S_OPTION_CASES
+ALL_CASES = [("wavenet", c) for c in WAVENET_ALL] + [("srnn", c) for c in SRNN_ALL] + [("s2s", c) for c in S2S_ALL]
+
+
