@@ -1,64 +1,21 @@
 """SimpleTransformer on the HIP generate path (csrc/transformer_plan.hip): golden parity with the reference's GenerateLoopV2,
 the default-sized network against torch running the network's own modules on the device, sampled decode, geometry edges."""
 import json
-import math
 
 import numpy as np
 import pytest
 import torch
 
 import mimikit_amd as mmk
-from mimikit_amd import native
-from oracle.weights import recipe_state_dict
 from tests import helpers as H
-from tests.f64_bounds import ACT_F, ACT_LIP, U, attention_bound, check_bound, check_near_miss, gemm_bound, ln_bound, ln_ref
+from tests.f64_bounds import check_bound, check_near_miss
+from tests.transformer_refs import build, f64_walk, torch_outputs, torch_outputs_f64, windows_of
 
 pytestmark = pytest.mark.gpu
 
 G = H.golden("transformer.npz")
 CASES = json.loads(str(G["cases"]))
 LOGIT_TOL = dict(rtol=1e-4, atol=2e-4)
-
-
-def build(net_kw, io_kw, seed, gain=1.5, device="cuda"):
-    if io_kw["kind"] == "mulaw":
-        io = mmk.IOSpec.mulaw_io(mmk.IOSpec.MuLawIOConfig(input_module_type="embedding", mlp_dim=io_kw.get("mlp_dim", 32),
-                                                          n_mlp_layers=io_kw["n_mlp_layers"]))
-    else:
-        io = mmk.IOSpec.magspec_io(mmk.IOSpec.MagSpecIOConfig(n_fft=io_kw["n_fft"], hop_length=io_kw["n_fft"] // 4))
-    net = mmk.SimpleTransformer.from_config(mmk.SimpleTransformer.Config(io_spec=io, **net_kw)).eval()
-    fill(net, seed, gain)
-    return net.to(device)
-
-
-def fill(net, seed, gain=1.5):
-    """tests/golden/make_golden_transformer.py: the recipe for every parameter, the positional-encoding table as the network made it"""
-    sd = net.state_dict()
-    shapes = {k: tuple(v.shape) for k, v in sd.items() if torch.is_floating_point(v) and v.dim() > 0 and k != "pe.pe"}
-    with torch.no_grad():
-        for k, v in recipe_state_dict(shapes, seed, gain).items():
-            sd[k].copy_(v.to(sd[k].device))
-
-
-def torch_outputs(net, windows, chunk=512):
-    """the network's own modules, all windows of (N, rf[, bins]) in batched forwards: the raw MLP outputs (N, q + 1) or frames"""
-    rf = net.rf
-    mask = net._generate_square_subsequent_mask(rf).to(windows.device)
-    outs = []
-    with torch.no_grad():
-        for w in windows.split(chunk):
-            src = net.pe(net.input_module((w,)).permute(1, 0, 2).contiguous())
-            h = net.model(tgt=src, memory=src, tgt_mask=mask, memory_mask=mask)[-1]
-            head = net.output_modules[0]
-            outs.append(head.estimator[0].fc(h) if hasattr(head, "estimator") else head(h))
-    return torch.cat(outs)
-
-
-def windows_of(hist, t0, n, rf):
-    """(B, T[, bins]) -> the (B n, rf[, bins]) windows ending before t0 .. t0 + n - 1"""
-    w = hist.unfold(1, rf, 1)[:, t0 - rf:t0 - rf + n]          # (B, n, [bins,] rf)
-    w = w.movedim(-1, 2) if hist.dim() == 3 else w
-    return w.reshape(-1, rf, *hist.shape[2:]).contiguous()
 
 
 def loop_run(net, prompt, n_steps):
@@ -215,123 +172,10 @@ def test_loop_from_config_runs_end_to_end():
 
 # ---------------------------------------------------------------------------------------------------------------- float64 step check
 # The plan's raw head outputs against the network's own modules run in float64 on the CPU, within a bound derived from the kernels'
-# bounds (tests/f64_bounds.py, the bounds tests/test_gpu_kernels_f64.py holds every kernel to).  A walk of the network in float64 carries,
-# next to every activation X, an elementwise bound E on |X_plan - X64|: the bound of the kernel that made X (its own roundings), plus
-# the errors of its inputs carried through the first-order sensitivity of the operation.  The kernel bounds treat roundings as
-# independent (u sqrt(K) for K of them); the carried errors are treated the same way, summed in quadrature (rss) rather than in
-# magnitude - added in magnitude, the bound of a two-layer network is 1e8 times the error a float32 run of it shows:
-#   X0         embedding + pe: one fp32 add, u |X0|;  frames: the input Linear's bound, then that add
-#   Linear     E_y = Lip(act) rss_k(W_nk E_k) + gemm_bound(x, W, b)
-#   attention  E_o = attention_bound(q, k, v)                                    (the kernel's own)
-#                  + rss_j(w_ij (ds_ij + sum_k w_ik ds_ik) (|v_j| + |o_i|)) + rss_j(w_ij E_v_j)   (the softmax's first-order sensitivity)
-#              ds_ij = scale rss_d(E_q |k_j|, |q_i| E_k) + u |x_ij|         (x = scale q.k; scale = 1/sqrtf(hd) is one rounding off)
-#   add + LN   E_out = ln_bound(v) + |w| rstd (E_v + rss(E_v) / D + |d| rstd^2 rss(d E_v) / D),  v = y + res, E_v = E_y + E_res
-#                                                                              (|Jacobian| of LayerNorm, d = v - mean)
-# The walk's values must be the network's own float64 outputs (checked first), so the bound is about the network that ran.
-def _rss_mm(E, W):
-    """rss_k(W_nk E_k): E (..., K) @ W^T in quadrature"""
-    return torch.sqrt((E * E) @ (W * W).t())
-
-
-def _linear(x, E, W, b, act=0):
-    pre = x @ W.t() + b
-    y = ACT_F[act](pre)
-    return y, ACT_LIP[act] * _rss_mm(E, W) + gemm_bound(x, W, b, W.shape[1], act, y)
-
-
-def _attention(q, k, v, Eq, Ek, Ev, shift=0):
-    """(N, rf, H, hd) causal attention over the window; shift 1 lets every row see one key too many (a near miss)"""
-    n, hd = q.shape[1], q.shape[3]
-    scale = 1.0 / math.sqrt(hd)
-    vis = torch.arange(n)[None, :] <= torch.arange(n)[:, None] + shift
-    x = (torch.einsum("bihd,bjhd->bhij", q, k) * scale).masked_fill(~vis, -math.inf)
-    wts = torch.softmax(x, -1)
-    out = torch.einsum("bhij,bjhd->bihd", wts, v)
-    own = attention_bound(q, k, v, out, wts, x, vis, scale)
-    xv = torch.where(vis, x, torch.zeros_like(x))
-    sq = lambda t: t * t   # noqa: E731
-    ds = scale * torch.sqrt(torch.einsum("bihd,bjhd->bhij", sq(Eq), sq(k)) + torch.einsum("bihd,bjhd->bhij", sq(q), sq(Ek))) + U * xv.abs()
-    ds = torch.where(vis, ds, torch.zeros_like(ds))
-    coef = wts * (ds + (wts * ds).sum(-1, keepdim=True))
-    # rss_j(coef_ij (|v_jd| + |o_id|)) <= rss_j(coef_ij |v_jd|) + rss_j(coef_ij) |o_id|
-    carried = (torch.sqrt(torch.einsum("bhij,bjhd->bihd", sq(coef), sq(v))) + torch.sqrt(sq(coef).sum(-1)).permute(0, 2, 1)[..., None] * out.abs()
-               + torch.sqrt(torch.einsum("bhij,bjhd->bihd", sq(wts), sq(Ev))))
-    return out, own + carried
-
-
-def _add_ln(y, Ey, res, Eres, norm):
-    with_res = res is not None
-    v = y + res if with_res else y
-    Ev = Ey + Eres if with_res else Ey
-    w, b = norm.weight, norm.bias
-    out, mean, d, var, rstd = ln_ref(v, w, b)
-    own = ln_bound(v, w, with_res, out, mean, d, var, rstd)
-    D = v.shape[-1]
-    rss = lambda t: torch.sqrt((t * t).sum(-1, keepdim=True))   # noqa: E731
-    carried = w.abs() * rstd * (Ev + rss(Ev) / D + d.abs() * rstd ** 2 * rss(d * Ev) / D)
-    return out, own + carried
-
-
-def _mha(attn, x, Ex, mem, Emem, H, shift):
-    """nn.MultiheadAttention of the plan's decoder: self-attention (mem None) or cross-attention on the memory"""
-    D = x.shape[-1]
-    W, b = attn.in_proj_weight, attn.in_proj_bias
-    kv, Ekv = (x, Ex) if mem is None else (mem, Emem)
-    q, Eq = _linear(x, Ex, W[:D], b[:D])
-    k, Ek = _linear(kv, Ekv, W[D:2 * D], b[D:2 * D])
-    v, Ev = _linear(kv, Ekv, W[2 * D:], b[2 * D:])
-    heads = lambda t: t.reshape(*t.shape[:2], H, D // H)   # noqa: E731
-    o, Eo = _attention(heads(q), heads(k), heads(v), heads(Eq), heads(Ek), heads(Ev), shift)
-    return _linear(o.reshape(x.shape), Eo.reshape(x.shape), attn.out_proj.weight, attn.out_proj.bias)
-
-
-def torch_outputs_f64(net64, windows):
-    """torch_outputs of a float64 copy of the network on the CPU, with the mask in float64 too: given a float32 mask, torch's CPU attention
-    on float64 queries is wrong from 16 keys on (off by O(1) at rf 16 and 65)"""
-    mask = net64._generate_square_subsequent_mask(net64.rf).double()
-    src = net64.pe(net64.input_module((windows,)).permute(1, 0, 2).contiguous())
-    h = net64.model(tgt=src, memory=src, tgt_mask=mask, memory_mask=mask)[-1]
-    head = net64.output_modules[0]
-    return head.estimator[0].fc(h) if hasattr(head, "estimator") else head(h)
-
-
-def f64_walk(net64, windows, shift=0):
-    """the float64 network on (N, rf[, bins]) windows: the head's raw outputs of the last position and their bound"""
-    rf, D = net64.rf, net64.config.model_dim
-    H = net64.config.n_heads
-    pe = net64.pe.pe[:rf, 0]
-    if windows.dtype == torch.int64:
-        x0 = net64.input_module((windows,)) + pe
-        E0 = U * x0.abs()
-    else:
-        lin = net64.input_module.heads[0][0]
-        pre, E0 = _linear(windows, torch.zeros_like(windows), lin.weight, lin.bias)
-        x0 = pre + pe
-        E0 = E0 + U * x0.abs()
-    x, E = x0, E0
-    for layer in net64.model.layers:
-        y, Ey = _mha(layer.self_attn, x, E, None, None, H, shift)
-        x, E = _add_ln(y, Ey, x, E, layer.norm1)
-        y, Ey = _mha(layer.multihead_attn, x, E, x0, E0, H, shift)
-        x, E = _add_ln(y, Ey, x, E, layer.norm2)
-        h, Eh = _linear(x, E, layer.linear1.weight, layer.linear1.bias, native.ACT["ReLU"])
-        y, Ey = _linear(h, Eh, layer.linear2.weight, layer.linear2.bias)
-        x, E = _add_ln(y, Ey, x, E, layer.norm3)
-    h, Eh = x[:, -1], E[:, -1]
-    if net64.model.norm is not None:
-        h, Eh = _add_ln(h, Eh, None, None, net64.model.norm)
-    head = net64.output_modules[0]
-    if hasattr(head, "estimator"):                 # MLP: Linear, act, [Linear, act] * n, Linear (the plan's raw outputs)
-        fc = list(head.estimator[0].fc)
-        for i, m in enumerate(fc):
-            if isinstance(m, torch.nn.Linear):
-                nxt = fc[i + 1] if i + 1 < len(fc) else None
-                h, Eh = _linear(h, Eh, m.weight, m.bias, 0 if nxt is None else native.ACT[type(nxt).__name__])
-    else:                                          # magspec: Linear, Chunk, Abs
-        h, Eh = _linear(h, Eh, head[0].weight, head[0].bias, native.ACT["Abs"])
-    return h, Eh
-
-
+# bounds (tests/f64_bounds.py, the bounds tests/test_gpu_kernels_f64.py holds every kernel to): tests/transformer_refs.py has the walk that
+# carries the bound (f64_walk) and says how.  The walk's values must be the network's own float64 outputs (checked first), so the bound is
+# about the network that ran.  (The bound is 18 to 100 times four times the reference's own fp32 error: test_gpu_transformer_f64.py holds the same steps,
+# and the graph path, to that envelope.)
 @pytest.mark.parametrize("tag,net_kw,io_kw,batch", [
     ("head_dim12", dict(model_dim=48, n_heads=4, feedforward_dim=96, num_layers=3, rf=16), dict(kind="mulaw", n_mlp_layers=2), 3),
     # rf 65: the window crosses the 64-row workgroup and the 64-key tile; B rf = 130 >= 128 rows: the plan's GEMMs run on the tiled
