@@ -1,5 +1,5 @@
 // Labelling the frames of a corpus (mimikit/extract/clusters.py:157-205 HCluster): the pieces of one level besides the nearest-other-frame
-// arg-max, which is nn_cosine_kernel<true> of neighbors.hip.
+// arg-max, which is nn_search_kernel<1, true, NnCosineKey> of nn_search.h (mmk_nn_cosine_self_f32 in neighbors.hip).
 //
 //   components   the weakly connected components of the functional graph i -> f(i) = nearest[i], numbered by rising smallest member.  Every
 //                component of such a graph holds exactly one cycle, so the smallest node ON the cycle names the component:

@@ -1,29 +1,11 @@
 // Scoring generated clips against the training corpus (mimikit/extract/from_neighbors.py:13-19, :44-55 and demos/checkpoint_k_bests.py:36-46):
 // every generated frame's nearest corpus frame by angular distance, and the cumulative entropy of the series of those neighbours.
 //
-//   nn_cosine_kernel      A GEMM whose epilogue is a row arg-max and which never writes the matrix.  c[r, j] = clamp(<x_r, y_j> rx[r] ry[j], -1, 1)
-//                         for `rows` query frames against m corpus frames over k bins.  A workgroup of four waves owns kNnRows = 128 query
-//                         rows and one SPAN of MMK_NN_SPAN corpus frames, which it walks in tiles of kNnCols = 128 frames; a wave owns a
-//                         64 x 64 corner of the tile as 2 x 2 products of v_mfma_f32_32x32x2_f32 with A = corpus frames and B = query rows, so
-//                         that D has the query row on the lane (l & 31) and 16 corpus frames in the registers (frame (q & 3) + 8 (q >> 2) +
-//                         4 (l >> 5) of the product's 32): the arg-max over a tile is taken inside the lane, in rising frame order, and a lane's
-//                         running (value, index) pair of each of its two query rows stays in registers across the whole span.  Both operands go
-//                         through LDS in chunks of kNnKC = 32 bins: rows are loaded dword by dword with consecutive lanes on consecutive bins
-//                         (coalesced whatever the row stride and the base alignment; every load is unconditional at a clamped, valid address
-//                         and the mask picks zero afterwards - nothing is padded by the caller), the next chunk's loads are in flight while
-//                         this chunk's products run.  Lane (r = l & 31, h = l >> 5) reads bins 8 g + 4 h .. + 3 of its row as one 16-byte LDS
-//                         read and feeds MFMA e of group g with bin 8 g + 4 h + e - the same permutation of the bins on both operands and for
-//                         every row and column, so ONE order of the sum over k wherever a frame sits in a tile: two identical corpus frames
-//                         have bit-identical cosines.  The row pitch of 36 floats keeps the 16-lane groups of that read on 64 different banks.
-//                         At the end of the span the two halves of a wave (one shuffle) and the two waves that share query rows (LDS) are
-//                         joined by "greater value, then lower index" and one pair per query row goes to the workspace, span-major.
-//                         Workgroups are numbered so that those in flight together share few query blocks and few spans (kNnGroup query
-//                         blocks by all spans, query block fastest).
-//                         nn_cosine_kernel<true> (mmk_nn_cosine_self_f32) is the same kernel with the corpus = the queries and frame r left
-//                         out of row r: the nearest OTHER frame, every level of HCluster (hcluster.hip holds the rest of a level).  Its
-//                         instance keeps four registers in scratch, read once per tile outside the loop over the bins; <false> has none.
-//   nn_merge_kernel       one thread per query row joins the spans' pairs in rising span order (strictly greater wins: the lower index
-//                         stays) and writes index (int64) and cos_best.
+//   mmk_nn_cosine_f32     nn_cosine_kernel, the tile walk of nn_search.h with a list of one and the cosine key, kept as its own kernel (see
+//                         there): the row arg-max of c[r, j] = clamp(<x_r, y_j> rx[r] ry[j], -1, 1), greater value, then lower index;
+//                         nn_merge_kernel<1> of nn_search.h joins the spans and writes index (int64) and cos_best.
+//   mmk_nn_cosine_self_f32   nn_search_kernel<1, true, NnCosineKey> of nn_search.h, the corpus = the queries and frame r left out of row r:
+//                         the nearest OTHER frame, every level of HCluster (hcluster.hip holds the rest of a level).
 //   cum_entropy_kernel    one workgroup per row of t items.  e[s] = log(s + 1) - S(s) / (s + 1) with S(s) = sum_{u <= s} (f(r_u + 1) - f(r_u)),
 //                         f(c) = c log c, r_u = the number of earlier occurrences of item u in the row: the entropy of the running histogram
 //                         without an items x t table.  The row is walked in chunks of 256 positions: a thread counts its item's earlier
@@ -33,29 +15,14 @@
 //                         fp32 once, the total is a fixed-order fp64 sum of the clamped values rounded once.
 // No atomics, no workgroup waits for another; every sum has one order, so results are the same from run to run.
 // NaN in the inputs is not handled (> drops it silently).
-#include "mmk_common.h"
+#include "nn_search.h"
 
 namespace mmk {
 
-typedef float nn_f32x4 __attribute__((ext_vector_type(4)));
-typedef float nn_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kNnSpan = MMK_NN_SPAN;
-constexpr int kNnThreads = 256;
-constexpr int kNnRows = 128;      // query rows of a workgroup, 64 per wave pair
-constexpr int kNnCols = 128;      // corpus frames of a tile, 64 per wave pair
-constexpr int kNnKC = 32;         // bins per LDS chunk
-constexpr int kNnPitch = 36;      // floats between LDS rows: 16-byte aligned, and the 16 lanes of one read group fall into 64 different banks
-constexpr int kNnGroup = 16;      // query blocks that are in flight together
-constexpr int kNnLoads = (kNnRows + kNnCols) / 8;      // dwords a thread loads per chunk
-static_assert(kNnSpan % kNnCols == 0, "a span is a whole number of tiles");
-static_assert(kNnRows == 128 && kNnCols == 128 && kNnThreads == 256, "four waves, each a 64 x 64 corner of 2 x 2 MFMA products");
-
-__device__ __forceinline__ bool nn_better(float v, int j, float bv, int bj) { return v > bv || (v == bv && j < bj); }
-
-// kSelf: the corpus IS the queries (the host passes y = x, ry = rx, M = rows) and frame j == r is left out of row r's arg-max - every level
-// of HCluster (extract/clusters.py).  The <false> instance is the kernel as it was before the switch, statement for statement.
-template <bool kSelf>
+// The plain arg-max keeps the kernel it had before nn_search.h.  It is the walk of nn_search_kernel<1, false, NnCosineKey>, statement for
+// statement, and gives its bits (scripts/nn_search_parity.py); but as that instance it measured 0.2 % slower on scripts/neighbors_bench.py
+// than this kernel, outside the range of three runs, with the same instructions in the loop over the bins and in the tile's epilogue
+// (DESIGN.md section 5.6.3 has the figures).  Until the cause is known this entry point does not move; a change to the walk is made in both.
 __global__ __launch_bounds__(kNnThreads, 2) void nn_cosine_kernel(const float* __restrict__ x, int64_t x_row_stride, const float* __restrict__ rx,
                                                                int64_t rows, const float* __restrict__ y, int64_t y_row_stride,
                                                                const float* __restrict__ ry, int64_t M, int32_t K, int32_t n_blocks,
@@ -88,7 +55,7 @@ __global__ __launch_bounds__(kNnThreads, 2) void nn_cosine_kernel(const float* _
   }
   const float ninf = __int_as_float(0xff800000);
   float best[2] = {ninf, ninf};
-  int bidx[2] = {0x7fffffff, 0x7fffffff};
+  int bidx[2] = {kNnEmpty, kNnEmpty};
 
   int parity = 0;
   for (int64_t jt = jbeg; jt < jend; jt += kNnCols, parity ^= 1) {
@@ -147,13 +114,7 @@ __global__ __launch_bounds__(kNnThreads, 2) void nn_cosine_kernel(const float* _
       __syncthreads();
     }
 
-    // the tile's arg-max, inside the lane and in rising frame order: strictly greater wins, so the lowest index stays.  kSelf: self_jl is
-    // the tile's frame that IS this lane's first query row (the second one's lies 32 further on) where the diagonal crosses the tile, and
-    // no frame of the tile anywhere else - one epilogue, since a second copy of it for the diagonal's tiles does not fit the registers
-    int self_jl = -64;
-    if constexpr (kSelf) {
-      if (jt < rbase + kNnRows && jt + kNnCols > rbase) self_jl = wn * 64 + fr - (int)(jt - rbase);
-    }
+    // the tile's arg-max, inside the lane and in rising frame order: strictly greater wins, so the lowest index stays
 #pragma unroll
     for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
@@ -164,9 +125,7 @@ __global__ __launch_bounds__(kNnThreads, 2) void nn_cosine_kernel(const float* _
 #pragma unroll
         for (int tn = 0; tn < 2; ++tn) {
           const float c = fminf(fmaxf(acc[tm][tn][q] * rxq[tn] * ryj, -1.f), 1.f);
-          bool take = j < jend && c > best[tn];
-          if constexpr (kSelf) take = take && jl != self_jl + tn * 32;
-          if (take) {
+          if (j < jend && c > best[tn]) {
             best[tn] = c;
             bidx[tn] = (int)j;
           }
@@ -201,24 +160,6 @@ __global__ __launch_bounds__(kNnThreads, 2) void nn_cosine_kernel(const float* _
   }
 }
 
-__global__ __launch_bounds__(256) void nn_merge_kernel(const float* __restrict__ ws_val, const int32_t* __restrict__ ws_idx, int64_t rows,
-                                                       int32_t n_spans, int64_t* __restrict__ index, float* __restrict__ cos_best) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= rows) return;
-  float v = ws_val[r];
-  int j = ws_idx[r];
-  for (int s = 1; s < n_spans; ++s) {
-    const float sv = ws_val[(int64_t)s * rows + r];
-    if (sv > v) {
-      v = sv;
-      j = ws_idx[(int64_t)s * rows + r];
-    }
-  }
-  index[r] = j;
-  cos_best[r] = v;
-}
-
-// ---- cumulative entropy --------------------------------------------------------------------------------------------------------------
 constexpr int kCeThreads = 256;
 
 __device__ __forceinline__ double ce_f(double c) { return c > 0.0 ? c * log(c) : 0.0; }
@@ -274,28 +215,6 @@ __global__ __launch_bounds__(kCeThreads) void cum_entropy_kernel(const int64_t* 
   if (tid == 0) total[blockIdx.x] = (float)scan[0][0];
 }
 
-static int nn_spans(int64_t m) { return (int)((m + kNnSpan - 1) / kNnSpan); }
-
-// the two launches of one call, shared by the two entry points (kSelf: y = x, ry = rx, m = rows)
-template <bool kSelf>
-static int nn_launch(const char* who, const float* x, int64_t x_row_stride, const float* rx, int64_t rows, const float* y, int64_t y_row_stride,
-                     const float* ry, int64_t m, int32_t k, int64_t* index, float* cos_best, void* workspace, hipStream_t st) {
-  const int n_spans = nn_spans(m);
-  const int64_t n_blocks = (rows + kNnRows - 1) / kNnRows;
-  const int64_t groups = (n_blocks + kNnGroup - 1) / kNnGroup;
-  const int64_t grid = groups * kNnGroup * n_spans;
-  if (grid > 0x7fffffffLL)
-    return fail(MMK_ERR_UNSUPPORTED, "%s: %lld rows against %lld frames are more than one launch takes", who, (long long)rows, (long long)m);
-  float* ws_val = static_cast<float*>(workspace);
-  int32_t* ws_idx = reinterpret_cast<int32_t*>(ws_val + rows * n_spans);
-  hipLaunchKernelGGL(nn_cosine_kernel<kSelf>, dim3((unsigned)grid), dim3(kNnThreads), 0, st, x, x_row_stride, rx, rows, y, y_row_stride, ry, m, k,
-                     (int32_t)n_blocks, n_spans, ws_val, ws_idx);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, ws_val, ws_idx, rows, n_spans, index, cos_best);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
-}
-
 }  // namespace mmk
 
 extern "C" size_t mmk_nn_cosine_workspace_bytes(int64_t rows, int64_t m) {
@@ -323,7 +242,22 @@ extern "C" int mmk_nn_cosine_f32(const float* x, int64_t x_row_stride, const flo
   if (workspace_bytes < mmk_nn_cosine_workspace_bytes(rows, m))
     return fail(MMK_ERR_WORKSPACE, "nn_cosine: the workspace has %zu bytes, %zu are needed", workspace_bytes,
                 mmk_nn_cosine_workspace_bytes(rows, m));
-  return nn_launch<false>("nn_cosine", x, x_row_stride, rx, rows, y, y_row_stride, ry, m, k, index, cos_best, workspace, (hipStream_t)stream);
+  // nn_search_launch's grid and workspace (T = 1) around the kernel above: a second copy of that arithmetic, as the kernel is of the walk -
+  // a change to the kNnGroup numbering or to the workspace layout is made there, in nn_search_kernel and here
+  const int n_spans = nn_spans(m);
+  const int64_t n_blocks = (rows + kNnRows - 1) / kNnRows;
+  const int64_t grid = (n_blocks + kNnGroup - 1) / kNnGroup * kNnGroup * n_spans;
+  if (grid > 0x7fffffffLL)
+    return fail(MMK_ERR_UNSUPPORTED, "nn_cosine: %lld rows against %lld frames are more than one launch takes", (long long)rows, (long long)m);
+  float* ws_val = static_cast<float*>(workspace);
+  int32_t* ws_idx = reinterpret_cast<int32_t*>(ws_val + rows * n_spans);
+  hipLaunchKernelGGL(nn_cosine_kernel, dim3((unsigned)grid), dim3(kNnThreads), 0, (hipStream_t)stream, x, x_row_stride, rx, rows, y, y_row_stride,
+                     ry, m, k, (int32_t)n_blocks, n_spans, ws_val, ws_idx);
+  MMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(nn_merge_kernel<1>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ws_val, ws_idx, rows, 1, n_spans,
+                     index, cos_best);
+  MMK_HIP(hipGetLastError());
+  return MMK_OK;
 }
 
 extern "C" int mmk_nn_cosine_self_f32(const float* x, int64_t x_row_stride, const float* rx, int64_t rows, int32_t k, int64_t* index,
@@ -342,8 +276,8 @@ extern "C" int mmk_nn_cosine_self_f32(const float* x, int64_t x_row_stride, cons
   if (workspace_bytes < mmk_nn_cosine_workspace_bytes(rows, rows))
     return fail(MMK_ERR_WORKSPACE, "nn_cosine_self: the workspace has %zu bytes, %zu are needed", workspace_bytes,
                 mmk_nn_cosine_workspace_bytes(rows, rows));
-  return nn_launch<true>("nn_cosine_self", x, x_row_stride, rx, rows, x, x_row_stride, rx, rows, k, index, cos_best, workspace,
-                         (hipStream_t)stream);
+  return nn_search_launch<1, true>("nn_cosine_self", x, x_row_stride, rx, rows, x, x_row_stride, NnCosineKey{rx}, rows, k, 1, index, cos_best,
+                             workspace, (hipStream_t)stream);
 }
 
 extern "C" int mmk_cum_entropy_i64(const int64_t* items, int64_t row_stride, int32_t batch, int64_t t, float* total, float* e,

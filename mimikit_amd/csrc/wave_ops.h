@@ -1,7 +1,7 @@
 // Wave-level primitives of the kernels (gfx950, 64 lanes = 4 DPP rows of 16), once: the DPP row moves, the sums and reduce-scatters
 // inside a row, and the butterflies and the scan across the whole wave.  Every function has ONE fixed order of additions.
 // Look-alikes that are other operations, and stay where they are:
-//   * transformer.hip's attention takes a MAXIMUM over lanes n, n + 16, n + 32, n + 48; neighbors.hip joins (value, index) pairs with
+//   * transformer.hip's attention takes a MAXIMUM over lanes n, n + 16, n + 32, n + 48; nn_search.h joins (key, index) lists with
 //     the lane 32 further only;
 //   * filters.hip's lf_wave_scan is a scan that multiplies by powers;
 //   * sampler256.h's wave_max_dpp / wave_scan_dpp / wave_argmax_first go through the DPP rows and four scalar reads, where wave_max

@@ -496,8 +496,8 @@ def nnn_end_columns(prompt_frames: torch.Tensor, corpus: torch.Tensor, corpus_in
     return dtw_subseq(cost, prompt_frames.shape[1])
 
 
-# include/mmk.h: MMK_NN_SPAN / MMK_CUM_ENTROPY_MAX_T - corpus frames of one workgroup of the arg-max kernel and the longest row the entropy
-# kernel ranks (csrc/neighbors.hip); the tests place their sizes on these
+# include/mmk.h: MMK_NN_SPAN / MMK_CUM_ENTROPY_MAX_T - corpus frames of one workgroup of the search kernel (csrc/nn_search.h) and the longest row the
+# entropy kernel ranks (csrc/neighbors.hip); the tests place their sizes on these
 NN_SPAN = 2048
 CUM_ENTROPY_MAX_T = 32768
 
@@ -611,7 +611,7 @@ def segment_mean(x: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor) ->
     return out
 
 
-# include/mmk.h: MMK_NN_TOPK_MAX - the neighbours per row a lane of the k-best kernel keeps in registers (csrc/qcluster.hip)
+# include/mmk.h: MMK_NN_TOPK_MAX - the neighbours per row a lane of the search kernel keeps in registers (csrc/nn_search.h)
 NN_TOPK_MAX = 16
 NN_TOPK_METRICS = ("euclidean", "cosine")
 

@@ -1,4 +1,4 @@
-"""The clustering kernels on the MI355X (csrc/neighbors.hip nn_cosine_kernel<true>, csrc/hcluster.hip) against the float64 restatements and
+"""The clustering kernels on the MI355X (csrc/nn_search.h nn_search_kernel<1, true, NnCosineKey>, csrc/hcluster.hip) against the float64 restatements and
 derived bounds of tests/hcluster_refs.py: the three entry points through the C ABI on strided, misaligned rows with NaN-filled (poisoned)
 outputs and workspace, every call made twice for the same bits, and HCluster / ArgMax on device tensors against the reference's results of
 tests/golden/clusters.npz.  Each test prints its worst error / bound."""
