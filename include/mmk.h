@@ -363,6 +363,32 @@ int mmk_interp1d_f32(const float* x, int64_t x_row_stride, int32_t batch, int64_
 int mmk_derivative_f32(const float* x, int64_t x_row_stride, int32_t batch, int64_t n, int32_t max_lag, float* y, int64_t y_row_stride,
                        mmk_stream_t stream);
 
+/* HarmonicSource / PercussiveSource (mimikit/features/functionals.py:736-791): librosa.decompose.hpss(S, kernel_size, power, margin) of a
+ * non-negative spectrogram as ONE launch.  s: (batch, frames, bins), time-major (the layout before the reference's transpose); rows
+ * s_row_stride elements apart (>= bins), clips s_batch_stride apart, 4-byte aligned and no more.
+ *   harm_median[t][b] = running median over win_harm frames of bin b, perc_median[t][b] = running median over win_perc bins of frame t:
+ *     scipy.ndimage.median_filter(mode="reflect"): a window of s at i covers i - s/2 .. i - s/2 + s - 1, the result is its element of rank
+ *     s/2 (the upper median of an even window), indices outside the axis fold by half-sample reflection (d c b a | a b c d | d c b a).
+ *     Selections: bit-identical to scipy's.  A median never crosses a clip.
+ *   mask_harm = softmask(harm, fl(perc * margin_harm)), mask_perc = softmask(perc, fl(harm * margin_perc)) with
+ *     softmask(X, R): Z = max(X, R); bad = Z < FLT_MIN; m = (X / Z)^power, r = (R / Z)^power; m / (m + r), and where bad 0.5 if both margins
+ *     are 1, else 0.  power == 1 takes no powf; power == +inf is the hard mask X > R.
+ *   harmonic = s * mask_harm, percussive = s * mask_perc.
+ * Any of the four outputs may be NULL (at least one is not); only the others are written, rows out_row_stride (>= bins) and clips
+ * out_batch_stride apart; they may not overlap s or one another.  No workspace.  A workgroup owns MMK_HPSS_TILE_FRAMES x MMK_HPSS_TILE_BINS
+ * outputs and stages them with a halo of win - 1 along each axis in LDS; one wave walks the tile's bins along time, one its frames along
+ * frequency (the walk's step is the tile).
+ * A window < 1, frames < win_harm / 2 or bins < win_perc / 2 (scipy folds such an axis more than once; that rule is not reproduced),
+ * a margin < 1, power <= 0 or NaN, no output, frames / bins / batch < 1: MMK_ERR_INVALID.  A window > MMK_HPSS_MAX_KERNEL:
+ * MMK_ERR_UNSUPPORTED.  Negative or NaN bins are not looked for (librosa raises on negative ones): their results are unspecified. */
+#define MMK_HPSS_MAX_KERNEL 63
+#define MMK_HPSS_TILE_FRAMES 64
+#define MMK_HPSS_TILE_BINS 64
+int mmk_hpss_f32(const float* s, int64_t s_batch_stride, int64_t s_row_stride, int32_t batch, int64_t frames, int32_t bins,
+                 int32_t win_harm, int32_t win_perc, float power, float margin_harm, float margin_perc,
+                 float* harmonic, float* percussive, float* harm_median, float* perc_median,
+                 int64_t out_batch_stride, int64_t out_row_stride, mmk_stream_t stream);
+
 /* ISTFT.torch_func (mimikit/features/functionals.py:553-564):
  * torch.istft(spec^T, n_fft, hop, window=hann_window(n_fft)) with torch's defaults (center=True,
  * length=None): inverse real FFT of every frame, periodic-Hann window, overlap-add, division by the

@@ -24,6 +24,8 @@ here:
   is never written), interpolation and the lagged-difference stencil in ``csrc/envelope.hip``.  Results stay on the device.
 * ``PCA`` (:1114-1138), the dimension reduction of the clusterizer's pre-processing pipeline: column statistics, an fp64 MFMA
   covariance, a block subspace iteration for the leading eigenvectors and the projection, all in ``csrc/pca.hip``.
+* ``HarmonicSource`` / ``PercussiveSource`` (:736-791), librosa's median-filter harmonic / percussive separation of a magnitude
+  spectrogram: both running medians, the soft masks and the product in one launch (``native.hpss``, ``csrc/hpss.hip``).
 * float64 tensors are computed in fp32 on the device (the kernels are fp32; the reference computes in the input's
   dtype, so float64 mu-law codes may differ from it for inputs within one fp32 ulp of a bin edge).
 """
@@ -41,7 +43,7 @@ from .item_spec import Frame, Sample, Unit, convert
 __all__ = [
     "Continuous", "Discrete", "Functional", "Identity", "Compose", "FileToSignal", "RemoveDC", "Normalize", "Emphasis", "Deemphasis",
     "MuLawCompress", "MuLawExpand", "STFT", "ISTFT", "MagSpec", "GLA", "Resample", "Envelop", "EnvelopBank", "Interpolate", "Derivative",
-    "PCA",
+    "PCA", "HarmonicSource", "PercussiveSource",
 ]
 
 N_FFT = 2048
@@ -886,3 +888,52 @@ class PCA(Functional):
     @property
     def inv(self) -> Functional:
         return Identity()
+
+
+# ---------------------------------------------------------------------------
+# harmonic / percussive separation
+# ---------------------------------------------------------------------------
+@dtc.dataclass
+class _HPSSSource(Functional):
+    """reference :736-791: ``librosa.decompose.hpss(S=inputs.T, kernel_size, power, margin)[which].T`` of (T, F) or (B, T, F) non-negative
+    float32 magnitudes on the device, as one launch of ``native.hpss`` asking for the one output: the running median of every bin along
+    time and of every frame along frequency (scipy's ``median_filter(mode="reflect")``, bit for bit), librosa's soft masks, the product.
+    ``kernel_size`` and ``margin`` are a scalar or a pair (harmonic, percussive), as librosa takes them.
+
+    Differences from librosa: windows up to ``native.HPSS_MAX_KERNEL``; an axis shorter than half its window raises (scipy reflects it
+    more than once there); real input only (no ``magphase`` branch); negative or NaN bins are not looked for - librosa raises on
+    negative ones, here their results are unspecified; a batch is separated clip by clip."""
+    kernel_size: Union[int, Tuple[int, int]] = 31
+    power: float = 1.
+    margin: Union[float, Tuple[float, float]] = 1.
+
+    _which = 0
+
+    @property
+    def unit(self) -> Optional[Unit]:
+        return None
+
+    @property
+    def elem_type(self) -> Optional[EventType]:
+        return None
+
+    def np_func(self, inputs):
+        raise NotImplementedError("the numpy (librosa) HPSS belongs to dataset extraction; use the torch path on the HIP device")
+
+    def torch_func(self, inputs):
+        from .. import native
+        return native.hpss(inputs, self.kernel_size, self.power, self.margin, harmonic=self._which == 0, percussive=self._which == 1)[0]
+
+    @property
+    def inv(self) -> Functional:
+        return Identity()
+
+
+@dtc.dataclass
+class HarmonicSource(_HPSSSource):
+    _which = 0
+
+
+@dtc.dataclass
+class PercussiveSource(_HPSSSource):
+    _which = 1

@@ -188,6 +188,7 @@ _SIGNATURES = {
     "mmk_stft_energy_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, i32, vp, vp]),
     "mmk_interp1d_f32": (i32, [vp, i64, i32, i64, vp, i64, i64, i32, i32, vp]),
     "mmk_derivative_f32": (i32, [vp, i64, i32, i64, i32, vp, i64, vp]),
+    "mmk_hpss_f32": (i32, [vp, i64, i64, i32, i64, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, i64, i64, vp]),
     "mmk_istft_n_samples": (i64, [i64, i32, i32]),
     "mmk_istft_workspace_floats": (C.c_size_t, [i32, i64, i32]),
     "mmk_istft_f32": (i32, [vp, i32, i32, i64, i32, i32, vp, vp, vp]),
@@ -900,6 +901,66 @@ def derivative(x: torch.Tensor, max_lag: int) -> torch.Tensor:
     check(lib().mmk_derivative_f32(ptr(x2), x2.stride(0), batch, n, max_lag, ptr(out), out.stride(0), stream_ptr(x.device)),
           "mmk_derivative_f32")
     return out.reshape(x.shape)
+
+
+# include/mmk.h: MMK_HPSS_* - the largest median window of mmk_hpss_f32 and the frames x bins one workgroup of it owns (csrc/hpss.hip)
+HPSS_MAX_KERNEL = 63
+HPSS_TILE_FRAMES = 64
+HPSS_TILE_BINS = 64
+
+
+def _pair(v, what: str):
+    """a scalar sets both members, a 2-sequence gives (harmonic, percussive), as librosa.decompose.hpss takes them"""
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError(f"hpss: {what} must be a scalar or a pair (harmonic, percussive), got {v!r}")
+        return v[0], v[1]
+    return v, v
+
+
+def hpss(s: torch.Tensor, kernel_size=31, power: float = 1.0, margin=1.0, harmonic: bool = True, percussive: bool = True,
+         medians: bool = False):
+    """s: (T, F) or (B, T, F) non-negative fp32 magnitudes, time-major -> the requested tensors of s's shape, in the order harmonic,
+    percussive, harm_median, perc_median (``medians`` asks for the last two): librosa.decompose.hpss(s^T, kernel_size, power, margin) with
+    scipy's reflecting median filters (``mmk_hpss_f32``, one launch on the current stream, no synchronisation, no workspace).  An axis
+    shorter than half its window raises ValueError (scipy folds it more than once; not reproduced), a window above HPSS_MAX_KERNEL
+    NotImplementedError.  Negative or NaN bins are not looked for: librosa raises on negative ones, here their results are unspecified."""
+    if not isinstance(s, torch.Tensor):
+        raise TypeError(f"hpss: expected a torch.Tensor, got {type(s)}")
+    if s.is_complex():
+        raise NotImplementedError("hpss: complex input (librosa's magphase branch) is not on the HIP path: pass the magnitudes")
+    if s.dtype != torch.float32:
+        raise TypeError(f"hpss runs in float32 on the HIP path, got {s.dtype}")
+    if s.dim() not in (2, 3):
+        raise ValueError(f"hpss takes (T, F) or (B, T, F), got shape {tuple(s.shape)}")
+    win_harm, win_perc = (int(w) for w in _pair(kernel_size, "kernel_size"))
+    margin_harm, margin_perc = (float(m) for m in _pair(margin, "margin"))
+    power = float(power)
+    if win_harm < 1 or win_perc < 1:
+        raise ValueError(f"hpss: windows must be at least 1, got ({win_harm}, {win_perc})")
+    if margin_harm < 1 or margin_perc < 1:
+        raise ValueError(f"hpss: margins must be at least 1, got ({margin_harm}, {margin_perc})")
+    if not power > 0:
+        raise ValueError(f"hpss: power must be positive, got {power}")
+    if win_harm > HPSS_MAX_KERNEL or win_perc > HPSS_MAX_KERNEL:
+        raise NotImplementedError(f"hpss: windows ({win_harm}, {win_perc}), the limit of the HIP path is {HPSS_MAX_KERNEL} "
+                                  "(native.HPSS_MAX_KERNEL)")
+    if not (harmonic or percussive or medians):
+        raise ValueError("hpss: no output requested")
+    frames, bins = s.shape[-2], s.shape[-1]
+    if min(s.shape) < 1 or frames < win_harm // 2 or bins < win_perc // 2:
+        raise ValueError(f"hpss: windows ({win_harm}, {win_perc}) need at least ({win_harm // 2}, {win_perc // 2}) frames and bins, "
+                         f"got shape {tuple(s.shape)}")
+    require_device(s)
+    s3 = s if s.dim() == 3 else s.unsqueeze(0)
+    if s3.stride(2) != 1 or s3.stride(1) < bins or s3.stride(0) < 0:
+        s3 = s3.contiguous()
+    batch = s3.shape[0]
+    outs = [torch.empty((batch, frames, bins), dtype=torch.float32, device=s.device) if want else None
+            for want in (harmonic, percussive, medians, medians)]
+    check(lib().mmk_hpss_f32(ptr(s3), s3.stride(0), s3.stride(1), batch, frames, bins, win_harm, win_perc, power, margin_harm, margin_perc,
+                             *(ptr(o) for o in outs), frames * bins, bins, stream_ptr(s.device)), "mmk_hpss_f32")
+    return tuple(o.reshape(s.shape) for o in outs if o is not None)
 
 
 def istft(spec: torch.Tensor, n_fft: int, hop: int, polar: bool) -> torch.Tensor:
