@@ -389,6 +389,37 @@ int mmk_hpss_f32(const float* s, int64_t s_batch_stride, int64_t s_row_stride, i
                  float* harmonic, float* percussive, float* harm_median, float* perc_median,
                  int64_t out_batch_stride, int64_t out_row_stride, mmk_stream_t stream);
 
+/* MelSpec / MFCC (mimikit/features/functionals.py:650-707): librosa.feature.melspectrogram(S=...) and librosa.feature.mfcc(S=...) of
+ * magnitude frames, the mel filter bank in banded form.  librosa's bank has at most two non-zero weights per bin and each band's
+ * non-zeros are one run of bins, so band m is three int32 (first bin lo_m, length len_m >= 0, offset off_m into `weights`) and
+ *     mel[m] = sum_{j < len_m} weights[off_m + j] * mag[lo_m + j]
+ * added in ascending bin order as one fmaf chain from 0 in fp32; a band of length 0 gives 0.  With a DCT matrix,
+ *     out[c] = sum_{m < n_mels} dct[m * n_mfcc + c] * mel[m],   c < n_mfcc
+ * in ascending band order, the same way; the bands then stay in LDS.  Every entry below runs this one epilogue, so equal magnitudes
+ * give equal bits whichever entry made them.
+ *   band: (n_mels, 3) int32 on the device, band_host: the same values in host memory (read for the checks only, before the launch);
+ *   weights: n_weights floats on the device; bank_n_bins: the number of bins the bank was built for;
+ *   dct: NULL (then n_mfcc == 0), or the (n_mfcc, n_mels) matrix TRANSPOSED, (n_mels, n_mfcc) row-major on the device, 1 <= n_mfcc <= n_mels.
+ * Errors: n_mels < 1, n_mfcc outside its range, bank_n_bins != the frames' bins, a band with lo < 0, len < 0, lo + len > n_bins or
+ * off + len > n_weights: MMK_ERR_INVALID.
+ *
+ * mmk_melbank_f32: in (rows, n_bins) float32, rows in_row_stride (>= n_bins) apart -> out (rows, n_mels) contiguous, or (rows, n_mfcc) with a
+ * DCT.  band == NULL (with band_host, weights NULL and n_weights 0) is the DCT alone on rows that already are mel bands: n_bins == n_mels,
+ * dct not NULL.  A wave stages a row in LDS; n_bins + n_mels > MMK_MELBANK_MAX_ROW: MMK_ERR_UNSUPPORTED.
+ *
+ * mmk_stft_mel_f32: the arguments of mmk_stft_energy_f32 and a bank for n_fft/2 + 1 bins -> out (batch, mmk_stft_n_frames(), n_mels or n_mfcc)
+ * contiguous, as ONE launch: an epilogue (output mode 6) of the STFT kernels that keeps a frame's magnitudes in the transform's LDS
+ * buffer; the spectrogram is never written.  The magnitudes are those of mmk_stft_mag_f32, bit for bit, so with reflect == 0 the result
+ * equals mmk_melbank_f32 of mmk_stft_mag_f32's output bit for bit.  n_mels > n_fft/2: MMK_ERR_UNSUPPORTED (the bands of a frame pair
+ * share that buffer); the other limits and errors are those of mmk_stft_energy_f32. */
+#define MMK_MELBANK_MAX_ROW 4096
+int mmk_melbank_f32(const float* in, int64_t in_row_stride, int64_t rows, int32_t n_bins, int32_t bank_n_bins, int32_t n_mels,
+                    const int32_t* band_host, const int32_t* band, const float* weights, int32_t n_weights, const float* dct,
+                    int32_t n_mfcc, float* out, mmk_stream_t stream);
+int mmk_stft_mel_f32(const float* x, int64_t x_row_stride, int32_t batch, int64_t n_samples, int32_t n_fft, int32_t hop, int32_t center,
+                     int32_t reflect, int32_t bank_n_bins, int32_t n_mels, const int32_t* band_host, const int32_t* band,
+                     const float* weights, int32_t n_weights, const float* dct, int32_t n_mfcc, float* out, mmk_stream_t stream);
+
 /* ISTFT.torch_func (mimikit/features/functionals.py:553-564):
  * torch.istft(spec^T, n_fft, hop, window=hann_window(n_fft)) with torch's defaults (center=True,
  * length=None): inverse real FFT of every frame, periodic-Hann window, overlap-add, division by the

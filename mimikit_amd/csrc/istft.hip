@@ -16,6 +16,7 @@
 #include "mmk_common.h"
 #include "fft1024.h"
 #include "spectral_util.h"
+#include "melbank.h"
 
 namespace mmk {
 
@@ -775,10 +776,13 @@ void gla1024q_iter_kernel(const SpectralTables T, const float* __restrict__ wave
 constexpr int kStftWaves = 4;      // waves (= frame pairs in flight) per workgroup of the n_fft = 1024 STFT kernel
 constexpr int kStftWpe = 3;        // its waves per SIMD (launch bound and the host's count of resident workgroups)
 
-template <int OUT>
+// OUT 6: the mel bands or MFCCs (melbank.h) of the magnitudes of OUT 4, out (batch, n_frames, n_out).  The bank is the one member of `mel`, a
+// pack that is empty in every other mode: their arguments and code are what they were without it.
+template <int OUT, class... Mel>
 __global__ __launch_bounds__(64 * kStftWaves) __attribute__((amdgpu_waves_per_eu(kStftWpe, kStftWpe)))
 void stft1024_kernel(const SpectralTables T, const float* __restrict__ x, int64_t x_row_stride, int64_t n_samples, int hop, int center, int reflect,
-                     int64_t n_frames, int64_t total_pairs, int runs_per_row, float* __restrict__ out, float* __restrict__ tprev, float momentum) {
+                     int64_t n_frames, int64_t total_pairs, int runs_per_row, float* __restrict__ out, float* __restrict__ tprev, float momentum,
+                     Mel... mel) {
   constexpr int N = 1024, bins = 513;
   __shared__ cf32 bufs[kStftWaves * kFftWaveLds];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -847,12 +851,19 @@ void stft1024_kernel(const SpectralTables T, const float* __restrict__ x, int64_
     } else fft1024_wave_regtw<true>(v, buf, ltw, lane);
     // the two real spectra:  A[k] = (Z[k] + conj(Z[N-k])) / 2 ,  B[k] = (Z[k] - conj(Z[N-k])) / (2i)
     cf32 esum = cf32{0.f, 0.f};                              // OUT 5: this lane's share of sum |A|, sum |B|
+    cf32 mg[OUT == 6 ? 9 : 1];                               // OUT 6: this lane's |A|, |B|, until every lane has read its Z
 #pragma unroll
     for (int jj = 0; jj < 9; ++jj) {
       const int k = lane + 64 * jj;
       if (k < bins) {
         const cf32 z = buf[fft_swz(lane) + 64 * jj];
         const cf32 zc = buf[(((N - k) & (N - 1)) & ~63) | fft_swz((64 - lane) & 63)];
+        if (OUT == 6) {                                       // the magnitudes of OUT 4, kept
+          const cf32 pz = z + zc, mz = z - zc;
+          const cf32 pp = pz * pz, mm = mz * mz;
+          mg[jj] = cf32{0.5f * __builtin_amdgcn_sqrtf(pp.x + mm.y), 0.5f * __builtin_amdgcn_sqrtf(pp.y + mm.x)};
+          continue;
+        }
         if (OUT == 5) {                                       // the magnitudes of OUT 4, kept
           const cf32 pz = z + zc, mz = z - zc;
           const cf32 pp = pz * pz, mm = mz * mz;
@@ -899,6 +910,23 @@ void stft1024_kernel(const SpectralTables T, const float* __restrict__ x, int64_
         o[0] = ea_sum;
         if (has_b) o[1] = eb_sum;
       }
+    }
+    if constexpr (OUT == 6) {             // the pair's 2 x 513 magnitudes over its own Z, the bands for a DCT behind them (2 x n_mels <= 1024 floats)
+      const MelBank B = (mel, ...);
+      float* mag = reinterpret_cast<float*>(buf);
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int jj = 0; jj < 9; ++jj) {
+        const int k = lane + 64 * jj;
+        if (k < bins) {
+          mag[k] = mg[jj].x;
+          mag[bins + k] = mg[jj].y;
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+      float* o = out + (b * n_frames + f0) * B.n_out();
+      mel_epilogue<false>(B, mag, mag + 2 * bins, o, lane, 64);
+      if (has_b) mel_epilogue<false>(B, mag + bins, mag + 2 * bins + B.n_mels, o + B.n_out(), lane, 64);
     }
     __builtin_amdgcn_wave_barrier();                        // buf is rewritten by the next pair
   }
@@ -963,10 +991,19 @@ __device__ __forceinline__ void generic_tables(float2* tw, float* win, int N, fl
   }
 }
 
-template <int OUT>   // the epilogues of stft1024_kernel
+// |v| for OUT 6, rounded as OUT 4 rounds it: there the compiler squares both parts as a pair and adds them, uncontracted; for OUT 6 alone it
+// would fuse one square into the sum (an ulp apart now and then).  Contraction off, so that the fused mel path equals the bank applied to
+// MagSpec's output bit for bit (tests/test_gpu_melspec.py holds the two together).
+__device__ __forceinline__ float generic_mag(float2 v) {
+#pragma clang fp contract(off)
+  const float xx = v.x * v.x, yy = v.y * v.y;
+  return sqrtf(xx + yy);
+}
+
+template <int OUT, class... Mel>   // the epilogues of stft1024_kernel
 __global__ __launch_bounds__(256) void stft_generic_kernel(const float* __restrict__ x, int64_t x_row_stride, int64_t n_samples, int n_fft,
                                                           int hop, int center, int reflect, int64_t n_frames, int64_t total_pairs,
-                                                          float* __restrict__ out, float* __restrict__ tprev, float momentum) {
+                                                          float* __restrict__ out, float* __restrict__ tprev, float momentum, Mel... mel) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int N = n_fft, half = n_fft >> 1;
   float2* buf0 = reinterpret_cast<float2*>(smem_raw);
@@ -1014,6 +1051,10 @@ __global__ __launch_bounds__(256) void stft_generic_kernel(const float* __restri
           esum[q] += sqrtf(s2[q].x * s2[q].x + s2[q].y * s2[q].y);
           continue;
         }
+        if (OUT == 6) {                                       // the magnitudes of OUT 4 into the buffer the transform left free
+          reinterpret_cast<float*>(src == buf0 ? buf1 : buf0)[q * bins + k] = generic_mag(s2[q]);
+          continue;
+        }
         if (q == 1 && !has_b) break;
         const int64_t e = ea + (int64_t)q * bins + k;
         const float2 v = s2[q];
@@ -1042,6 +1083,15 @@ __global__ __launch_bounds__(256) void stft_generic_kernel(const float* __restri
         o[0] = t.x;
         if (has_b) o[1] = t.y;
       }
+    }
+    if constexpr (OUT == 6) {   // 2 x bins = N + 2 magnitudes in the free buffer; the bands for a DCT (2 x n_mels <= N floats) where the spectrum was
+      const MelBank B = (mel, ...);
+      const float* mag = reinterpret_cast<const float*>(src == buf0 ? buf1 : buf0);
+      float* bands = reinterpret_cast<float*>(src == buf0 ? buf0 : buf1);
+      __syncthreads();
+      float* o = out + (b * n_frames + f0) * B.n_out();
+      mel_epilogue<true>(B, mag, bands, o, tid, nt);
+      if (has_b) mel_epilogue<true>(B, mag + bins, bands + B.n_mels, o + B.n_out(), tid, nt);
     }
     __syncthreads();   // the buffers are rewritten by the next pair
   }
@@ -1221,7 +1271,7 @@ static int launch_istft(const float* spec, const float* mag, int mode, int batch
 }
 
 int launch_stft1024(const float* x, int64_t x_row_stride, int batch, int64_t n_samples, int hop, int center, int reflect, int out_mode,
-                    float* out, float* tprev, float momentum, hipStream_t stream) {
+                    float* out, float* tprev, float momentum, hipStream_t stream, const MelBank* mel) {
   const int64_t n_frames = mmk_stft_n_frames(n_samples, 1024, hop, center);
   const int64_t pairs_per_row = (n_frames + 1) / 2;
   const int64_t total_pairs = (int64_t)batch * pairs_per_row;
@@ -1248,6 +1298,10 @@ int launch_stft1024(const float* x, int64_t x_row_stride, int batch, int64_t n_s
     case 2: MMK_STFT_LAUNCH(2); break;
     case 3: MMK_STFT_LAUNCH(3); break;
     case 5: MMK_STFT_LAUNCH(5); break;
+    case 6:
+      hipLaunchKernelGGL((stft1024_kernel<6, MelBank>), grid, block, 0, stream, T, x, x_row_stride, n_samples, hop, center, reflect, n_frames,
+                         total_pairs, (int)runs_per_row, out, tprev, momentum, *mel);
+      break;
     default: MMK_STFT_LAUNCH(4); break;
   }
 #undef MMK_STFT_LAUNCH
@@ -1256,7 +1310,7 @@ int launch_stft1024(const float* x, int64_t x_row_stride, int batch, int64_t n_s
 }
 
 int launch_stft_generic(const float* x, int64_t x_row_stride, int batch, int64_t n_samples, int n_fft, int hop, int center, int reflect,
-                        int out_mode, float* out, float* tprev, float momentum, hipStream_t stream) {
+                        int out_mode, float* out, float* tprev, float momentum, hipStream_t stream, const MelBank* mel) {
   const int64_t n_frames = mmk_stft_n_frames(n_samples, n_fft, hop, center);
   const int64_t total_pairs = (int64_t)batch * ((n_frames + 1) / 2);
   const size_t lds = (size_t)n_fft * (3 * sizeof(float2) + sizeof(float));
@@ -1270,6 +1324,10 @@ int launch_stft_generic(const float* x, int64_t x_row_stride, int batch, int64_t
     case 2: MMK_STFT_LAUNCH(2); break;
     case 3: MMK_STFT_LAUNCH(3); break;
     case 5: MMK_STFT_LAUNCH(5); break;
+    case 6:
+      hipLaunchKernelGGL((stft_generic_kernel<6, MelBank>), grid, block, lds, stream, x, x_row_stride, n_samples, n_fft, hop, center, reflect, n_frames,
+                         total_pairs, out, tprev, momentum, *mel);
+      break;
     default: MMK_STFT_LAUNCH(4); break;
   }
 #undef MMK_STFT_LAUNCH

@@ -14,6 +14,7 @@
 #include "mmk_common.h"
 #include "fft1024.h"
 #include "spectral_util.h"
+#include "melbank.h"
 
 namespace mmk {
 
@@ -59,6 +60,21 @@ __device__ __forceinline__ cf32 untangle(const cf32* buf, int k, cf32 w) {
   return cf32{e.x + (w.x * o.x - w.y * o.y), e.y + (w.x * o.y + w.y * o.x)};
 }
 
+// |X[k]| for OUT 6, rounded as OUT 4 rounds it.  There the compiler contracts untangle() and the squares into
+//     X.x = fma(.5, z.x + zc.x, fma(w.x, o.x, -(w.y o.y))),  X.y = fma(.5, z.y - zc.y, fma(w.x, o.y, w.y o.x)),  |X| = sqrt(fma(X.x, X.x, X.y X.y))
+// and in OUT 6, where the magnitudes wait in registers, it would pack and contract them another way: one ulp apart now and then.  Written
+// out here with contraction off, so that MelSpec.from_signal is MelSpec()(MagSpec()(x)) bit for bit (tests/test_gpu_melspec.py holds the
+// two together).  (At k = 1024 z and zc are one element, o.y = 0 and Im w = 0: no contraction can show.)
+__device__ __forceinline__ float untangle_mag(const cf32* buf, int k, cf32 w) {
+#pragma clang fp contract(off)
+  const cf32 z = buf[k & (kN - 1)];
+  const cf32 zc = buf[(kN - k) & (kN - 1)];
+  const float ox = 0.5f * (z.y + zc.y), oy = -0.5f * (z.x - zc.x);
+  const float sx = fmaf(0.5f, z.x + zc.x, fmaf(w.x, ox, -(w.y * oy)));
+  const float sy = fmaf(0.5f, z.y - zc.y, fmaf(w.x, oy, w.y * ox));
+  return sqrtf(fmaf(sx, sx, sy * sy));
+}
+
 // conj(Z[n]) from X[n] (a) and X[N - n] (b):  the FFT input of the inverse transform
 __device__ __forceinline__ cf32 tangle_conj(cf32 a, cf32 b, cf32 w) {
   const cf32 e = cf32{0.5f * (a.x + b.x), 0.5f * (a.y - b.y)};
@@ -70,10 +86,12 @@ __device__ __forceinline__ cf32 tangle_conj(cf32 a, cf32 b, cf32 w) {
 // ---- STFT -----------------------------------------------------------------------------------------------------------------
 // OUT 0: (re, im)   OUT 1: (|S|, angle S)   OUT 2: angle S   OUT 4: |S|  (MagSpec)
 // OUT 5: sum_k |S[k]|, one float per frame in out (batch, n_frames): lane partials in bin order, then a butterfly over the wave
-template <int OUT>
+// OUT 6: the mel bands or MFCCs of the |S| of OUT 4 (melbank.h), out (batch, n_frames, n_out); the bank is the one member of `mel`, a pack
+//        that is empty in every other mode: their arguments and code are what they were without it
+template <int OUT, class... Mel>
 __global__ __launch_bounds__(64 * kIstftWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void stft2048_kernel(const SpectralTables T, const float* __restrict__ x, int64_t x_row_stride, int64_t n_samples, int hop, int center, int reflect,
-                     int64_t n_frames, int64_t total_frames, float* __restrict__ out) {
+                     int64_t n_frames, int64_t total_frames, float* __restrict__ out, Mel... mel) {
   __shared__ cf32 tw[kN];
   __shared__ cf32 bufs[kIstftWaves * kFftWaveLds];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -97,10 +115,15 @@ void stft2048_kernel(const SpectralTables T, const float* __restrict__ x, int64_
     fft1024_wave(v, buf, tw, lane);
     const int64_t e0 = fr * kBins2;
     float esum = 0.f;                                       // OUT 5: this lane's share of the frame's sum
+    float mg[OUT == 6 ? 17 : 1];                            // OUT 6: this lane's magnitudes, until every lane has read its Z
 #pragma unroll
     for (int j = 0; j < 17; ++j) {
       const int k = lane + 64 * j;
       if (k < kBins2) {
+        if (OUT == 6) {
+          mg[j] = untangle_mag(buf, k, wk[j]);
+          continue;
+        }
         const cf32 s = untangle(buf, k, wk[j]);
         const int64_t e = e0 + k;
         if (OUT == 5) esum += sqrtf(s.x * s.x + s.y * s.y);
@@ -113,6 +136,16 @@ void stft2048_kernel(const SpectralTables T, const float* __restrict__ x, int64_
     if (OUT == 5) {
       esum = wave_sum(esum);
       if (lane == 0) out[fr] = esum;
+    }
+    if constexpr (OUT == 6) {                               // the frame's 1025 magnitudes over its own Z, the bands for a DCT behind them
+      const MelBank B = (mel, ...);
+      float* mag = reinterpret_cast<float*>(buf);
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int j = 0; j < 17; ++j)
+        if (lane + 64 * j < kBins2) mag[lane + 64 * j] = mg[j];
+      __builtin_amdgcn_wave_barrier();
+      mel_epilogue<false>(B, mag, mag + kBins2, out + fr * B.n_out(), lane, 64);
     }
     __builtin_amdgcn_wave_barrier();                        // buf is rewritten by the next frame
   }
@@ -363,7 +396,7 @@ static void geometry2048(int batch, int64_t n_frames, int* seg_hops, int* segs_p
 }
 
 int launch_stft2048(const float* x, int64_t x_row_stride, int batch, int64_t n_samples, int hop, int center, int reflect, int out_mode,
-                    float* out, hipStream_t stream) {
+                    float* out, hipStream_t stream, const MelBank* mel) {
   const int64_t n_frames = mmk_stft_n_frames(n_samples, kN2, hop, center);
   const int64_t total = (int64_t)batch * n_frames;
   const int64_t wgs = (total + kIstftWaves - 1) / kIstftWaves;
@@ -377,6 +410,10 @@ int launch_stft2048(const float* x, int64_t x_row_stride, int batch, int64_t n_s
     case 1: MMK_STFT_LAUNCH(1); break;
     case 2: MMK_STFT_LAUNCH(2); break;
     case 5: MMK_STFT_LAUNCH(5); break;
+    case 6:
+      hipLaunchKernelGGL((stft2048_kernel<6, MelBank>), grid, block, 0, stream, T, x, x_row_stride, n_samples, hop, center, reflect, n_frames, total, out,
+                         *mel);
+      break;
     default: MMK_STFT_LAUNCH(4); break;
   }
 #undef MMK_STFT_LAUNCH

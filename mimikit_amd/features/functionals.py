@@ -26,6 +26,9 @@ here:
   covariance, a block subspace iteration for the leading eigenvectors and the projection, all in ``csrc/pca.hip``.
 * ``HarmonicSource`` / ``PercussiveSource`` (:736-791), librosa's median-filter harmonic / percussive separation of a magnitude
   spectrogram: both running medians, the soft masks and the product in one launch (``native.hpss``, ``csrc/hpss.hip``).
+* ``MelSpec`` / ``MFCC`` (:650-707), librosa's mel filter bank in banded form and scipy's DCT behind it (``features/mel.py``,
+  ``csrc/melbank.hip``): on a spectrogram (``native.melbank``) or, through ``from_signal``, as an epilogue of the STFT kernels
+  (``native.stft_mel``: one launch from the signal to the mel or MFCC frames, the spectrogram is never written).
 * float64 tensors are computed in fp32 on the device (the kernels are fp32; the reference computes in the input's
   dtype, so float64 mu-law codes may differ from it for inputs within one fp32 ulp of a bin edge).
 """
@@ -43,7 +46,7 @@ from .item_spec import Frame, Sample, Unit, convert
 __all__ = [
     "Continuous", "Discrete", "Functional", "Identity", "Compose", "FileToSignal", "RemoveDC", "Normalize", "Emphasis", "Deemphasis",
     "MuLawCompress", "MuLawExpand", "STFT", "ISTFT", "MagSpec", "GLA", "Resample", "Envelop", "EnvelopBank", "Interpolate", "Derivative",
-    "PCA", "HarmonicSource", "PercussiveSource",
+    "PCA", "HarmonicSource", "PercussiveSource", "MelSpec", "MFCC",
 ]
 
 N_FFT = 2048
@@ -937,3 +940,113 @@ class HarmonicSource(_HPSSSource):
 @dtc.dataclass
 class PercussiveSource(_HPSSSource):
     _which = 1
+
+
+# ---------------------------------------------------------------------------
+# mel spectrogram / MFCC
+# ---------------------------------------------------------------------------
+def _mel_input(inputs, who: str):
+    if not isinstance(inputs, torch.Tensor):
+        raise TypeError(f"{who}: expected a torch.Tensor, got {type(inputs)}")
+    if inputs.dtype != torch.float32:
+        raise TypeError(f"{who} runs in float32 on the HIP path, got {inputs.dtype}")
+    if inputs.dim() not in (2, 3):
+        raise ValueError(f"{who} takes (T, F) or (B, T, F), got shape {tuple(inputs.shape)}")
+
+
+def _mel_signal(x, who: str):
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{who}.from_signal: expected a torch.Tensor, got {type(x)}")
+    if x.dim() not in (1, 2):
+        raise ValueError(f"{who}.from_signal takes (T,) or (B, T), got shape {tuple(x.shape)}")
+
+
+@dtc.dataclass
+class MelSpec(Functional):
+    """reference :650-676: ``librosa.feature.melspectrogram(S=inputs.T, n_mels, fmin, fmax, htk).T`` of (T, F) or (B, T, F) float32
+    magnitudes on the device.  As there, no ``sr`` is passed: the bank is librosa's for 22050 Hz and ``n_fft = 2 (F - 1)``, whatever the
+    audio's rate (``features/mel.py``: a restatement of librosa's published source, Slaney-normalised, held in banded form).
+    ``from_signal`` goes from the signal to the mel frames in one launch."""
+    n_mels: int = 128
+    fmin: float = 0.
+    fmax: Optional[float] = None
+    htk: bool = False
+
+    @property
+    def unit(self) -> Optional[Unit]:
+        return None
+
+    @property
+    def elem_type(self) -> Optional[EventType]:
+        return Continuous(0., float("inf"), self.n_mels)
+
+    def np_func(self, inputs):
+        raise NotImplementedError("the numpy (librosa) MelSpec belongs to dataset extraction; use the torch path on the HIP device")
+
+    def _bank(self, n_bins: int, device):
+        from . import mel
+        return mel.device_bank(n_bins, self.n_mels, self.fmin, self.fmax, self.htk, device)
+
+    def torch_func(self, inputs):
+        from .. import native
+        _mel_input(inputs, "MelSpec")
+        native.require_device(inputs)
+        return native.melbank(inputs, self._bank(inputs.shape[-1], inputs.device))
+
+    def from_signal(self, x, magspec: "MagSpec"):
+        """``self(magspec(x))`` for x (T,) or (B, T) as one launch of ``native.stft_mel``; bit-identical to the two calls with
+        ``pad_mode="constant"``"""
+        from .. import native
+        _mel_signal(x, "MelSpec")
+        native.require_device(x)
+        return native.stft_mel(magspec.stft._fix_length(x), magspec.n_fft, magspec.hop_length, bool(magspec.center), magspec.pad_mode,
+                               self._bank(magspec.n_fft // 2 + 1, x.device))
+
+    @property
+    def inv(self) -> Functional:
+        return Identity()
+
+
+@dtc.dataclass
+class MFCC(Functional):
+    """reference :680-707: ``librosa.feature.mfcc(S=inputs.T, n_mfcc, dct_type, norm, lifter).T`` of (T, n_mels) or (B, T, n_mels) float32
+    on the device: the first ``n_mfcc`` outputs of ``scipy.fft.dct(type, norm)`` along the mel axis, librosa's lifter folded into the
+    matrix.  As there, no logarithm is taken: the DCT of whatever it is given.  ``from_signal`` goes from the signal to the coefficients
+    in one launch; neither the spectrogram nor the mel frames are written."""
+    n_mfcc: int = 20
+    dct_type: int = 2
+    norm: Optional[str] = "ortho"
+    lifter: int = 0
+
+    @property
+    def unit(self) -> Optional[Unit]:
+        return None
+
+    @property
+    def elem_type(self) -> Optional[EventType]:
+        return Continuous(0., float("inf"), self.n_mfcc)
+
+    def np_func(self, inputs):
+        raise NotImplementedError("the numpy (librosa) MFCC belongs to dataset extraction; use the torch path on the HIP device")
+
+    def _dct(self, n_mels: int, device):
+        from . import mel
+        return mel.device_dct(self.n_mfcc, n_mels, self.dct_type, self.norm, self.lifter, device)
+
+    def torch_func(self, inputs):
+        from .. import native
+        _mel_input(inputs, "MFCC")
+        native.require_device(inputs)
+        return native.melbank(inputs, None, self._dct(inputs.shape[-1], inputs.device))
+
+    def from_signal(self, x, magspec: "MagSpec", melspec: MelSpec):
+        """``self(melspec(magspec(x)))`` for x (T,) or (B, T) as one launch of ``native.stft_mel``"""
+        from .. import native
+        _mel_signal(x, "MFCC")
+        native.require_device(x)
+        return native.stft_mel(magspec.stft._fix_length(x), magspec.n_fft, magspec.hop_length, bool(magspec.center), magspec.pad_mode,
+                               melspec._bank(magspec.n_fft // 2 + 1, x.device), self._dct(melspec.n_mels, x.device))
+
+    @property
+    def inv(self) -> Functional:
+        return Identity()

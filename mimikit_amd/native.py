@@ -189,6 +189,8 @@ _SIGNATURES = {
     "mmk_interp1d_f32": (i32, [vp, i64, i32, i64, vp, i64, i64, i32, i32, vp]),
     "mmk_derivative_f32": (i32, [vp, i64, i32, i64, i32, vp, i64, vp]),
     "mmk_hpss_f32": (i32, [vp, i64, i64, i32, i64, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, i64, i64, vp]),
+    "mmk_melbank_f32": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, vp]),
+    "mmk_stft_mel_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, vp]),
     "mmk_istft_n_samples": (i64, [i64, i32, i32]),
     "mmk_istft_workspace_floats": (C.c_size_t, [i32, i64, i32]),
     "mmk_istft_f32": (i32, [vp, i32, i32, i64, i32, i32, vp, vp, vp]),
@@ -961,6 +963,85 @@ def hpss(s: torch.Tensor, kernel_size=31, power: float = 1.0, margin=1.0, harmon
     check(lib().mmk_hpss_f32(ptr(s3), s3.stride(0), s3.stride(1), batch, frames, bins, win_harm, win_perc, power, margin_harm, margin_perc,
                              *(ptr(o) for o in outs), frames * bins, bins, stream_ptr(s.device)), "mmk_hpss_f32")
     return tuple(o.reshape(s.shape) for o in outs if o is not None)
+
+
+# include/mmk.h: MMK_MELBANK_MAX_ROW - the floats of LDS a wave of mmk_melbank_f32 has for a row and its bands (csrc/melbank.hip)
+MELBANK_MAX_ROW = 4096
+
+
+def _bank_args(bank, dct, who: str):
+    """(bank_n_bins, n_mels, band_host, band, weights, n_weights, dct, n_mfcc) of include/mmk.h from a features.mel.DeviceBank (or None) and
+    a transposed DCT matrix (n_mels, n_mfcc) on the device (or None)"""
+    if bank is None and dct is None:
+        raise ValueError(f"{who}: neither a bank nor a DCT matrix")
+    if dct is not None:
+        if dct.dtype != torch.float32 or dct.dim() != 2 or not dct.is_contiguous():
+            raise TypeError(f"{who}: the DCT matrix is a contiguous float32 (n_mels, n_mfcc) tensor")
+        require_device(dct)
+    n_mels = bank.n_mels if bank is not None else dct.shape[0]
+    if dct is not None and dct.shape[0] != n_mels:
+        raise ValueError(f"{who}: a DCT matrix over {dct.shape[0]} bands behind a bank of {n_mels}")
+    n_mfcc = dct.shape[1] if dct is not None else 0
+    if bank is None:
+        return (0, n_mels, None, None, None, 0, ptr(dct), n_mfcc)
+    return (bank.n_bins, n_mels, bank.table_host.ctypes.data, ptr(bank.table), ptr(bank.weights), bank.weights.numel(), ptr(dct), n_mfcc)
+
+
+def melbank(s: torch.Tensor, bank=None, dct: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """s: (..., n_bins) fp32 magnitudes -> (..., n_mels) through ``bank`` (features.mel.device_bank), or (..., n_mfcc) with the DCT matrix
+    ``dct`` (features.mel.device_dct: transposed, (n_mels, n_mfcc)) behind it; ``bank=None`` applies the DCT alone to rows that already are
+    mel bands.  One launch of ``mmk_melbank_f32`` on the current stream."""
+    if not isinstance(s, torch.Tensor):
+        raise TypeError(f"melbank: expected a torch.Tensor, got {type(s)}")
+    if s.dtype != torch.float32:
+        raise TypeError(f"melbank runs in float32 on the HIP path, got {s.dtype}")
+    if s.dim() < 1 or s.shape[-1] < 1:
+        raise ValueError(f"melbank takes (..., n_bins), got shape {tuple(s.shape)}")
+    require_device(s)
+    args = _bank_args(bank, dct, "melbank")
+    n_bins = s.shape[-1]
+    if bank is not None and bank.n_bins != n_bins:
+        raise ValueError(f"melbank: the bank was built for {bank.n_bins} bins, the input has {n_bins}")
+    if bank is None and n_bins != args[1]:
+        raise ValueError(f"melbank: the DCT matrix takes {args[1]} bands, the input has {n_bins}")
+    if n_bins + args[1] > MELBANK_MAX_ROW:
+        raise NotImplementedError(f"melbank: n_bins + n_mels = {n_bins} + {args[1]}, the limit of the HIP path is {MELBANK_MAX_ROW}")
+    n_out = args[7] if dct is not None else args[1]
+    s2 = _rows(s)
+    out = torch.empty((s2.shape[0], n_out), dtype=torch.float32, device=s.device)
+    if s2.shape[0] == 0:
+        return out.reshape(*s.shape[:-1], n_out)
+    check(lib().mmk_melbank_f32(ptr(s2), s2.stride(0), s2.shape[0], n_bins, *args, ptr(out), stream_ptr(s.device)), "mmk_melbank_f32")
+    return out.reshape(*s.shape[:-1], n_out)
+
+
+def stft_mel(x: torch.Tensor, n_fft: int, hop: int, center: bool, pad_mode: str, bank, dct: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x: (..., n_samples) fp32 -> (..., n_frames, n_mels), or (..., n_frames, n_mfcc) with ``dct``: ``melbank(stft magnitudes, bank, dct)``
+    as ONE launch (``mmk_stft_mel_f32``); the spectrogram is never written.  With pad_mode 'constant' the result equals
+    ``melbank(stft_mag(x, ...), bank, dct)`` bit for bit."""
+    require_device(x)
+    if pad_mode not in ("constant", "reflect"):
+        raise NotImplementedError(f"HIP STFT covers pad_mode 'constant' and 'reflect', got '{pad_mode}'")
+    if bank is None:
+        raise ValueError("stft_mel: needs a bank")
+    if x.dtype != torch.float32:
+        x = x.float()
+    args = _bank_args(bank, dct, "stft_mel")
+    if bank.n_bins != n_fft // 2 + 1:
+        raise ValueError(f"stft_mel: the bank was built for {bank.n_bins} bins, n_fft = {n_fft} gives {n_fft // 2 + 1}")
+    if bank.n_mels > n_fft // 2:
+        raise NotImplementedError(f"stft_mel: n_mels = {bank.n_mels}, the limit of the fused path at n_fft = {n_fft} is {n_fft // 2}")
+    lead = x.shape[:-1]
+    x2 = _rows(x)
+    n = x2.shape[-1]
+    n_frames = lib().mmk_stft_n_frames(n, n_fft, hop, int(center))
+    if n_frames <= 0:
+        raise RuntimeError(f"stft_mel: input of {n} samples is shorter than one frame of {n_fft}")
+    n_out = args[7] if dct is not None else args[1]
+    out = torch.empty((x2.shape[0], n_frames, n_out), dtype=torch.float32, device=x.device)
+    check(lib().mmk_stft_mel_f32(ptr(x2), x2.stride(0), x2.shape[0], n, n_fft, hop, int(center), int(pad_mode == "reflect"), *args, ptr(out),
+                                 stream_ptr(x.device)), "mmk_stft_mel_f32")
+    return out.reshape(*lead, n_frames, n_out)
 
 
 def istft(spec: torch.Tensor, n_fft: int, hop: int, polar: bool) -> torch.Tensor:
