@@ -257,6 +257,49 @@ size_t mmk_edge_components_workspace_bytes(int64_t n);
 int mmk_edge_components_i64(const int64_t* src, const int64_t* dst, int64_t n_edges, int64_t n, int64_t* labels, int64_t* n_components,
                             void* workspace, size_t workspace_bytes, mmk_stream_t stream);
 
+/* Cutting corpus frames into segments (mimikit/extract/segment.py:21-174: discontinuity_scores, pick_globally_sorted_maxes).
+ *
+ * mmk_novelty_f32: for `batch` clips of `frames` frames over `bins` bins (clips x_batch_stride floats apart, rows x_row_stride) and n_half
+ * half-widths h_q (a HOST array), with d(r, c) = 1 - <x_r, x_c> rx[r] rx[c] the cosine distance, d(r, r) = 0, d = 1 where a frame is zero,
+ *     raw[b][q][i] = 1 / (4 h_q^2) sum_{a = -h_q .. h_q, a != 0} sum_{b = -h_q .. h_q, b != 0} -sign(a) sign(b) d(i + a, i - 1 + b)
+ * where a term whose row or column lies outside [0, frames) counts 0: the normalised checkerboard of 2 h_q + 1 slid along the diagonal,
+ * centred on (i, i - 1) as the reference's is.  raw: (batch, n_half, frames) contiguous.  inv_norm: (batch, frames) contiguous from
+ * mmk_inv_row_norm_f32, or NULL: the kernel then computes the norms itself, by the same code.  One launch; a workgroup owns
+ * MMK_NOVELTY_TILE output frames, forms the Gram tile of the frames their boards touch on the fp32 matrix pipe and sums the boards from LDS
+ * in fp64 in one fixed order (rounded to fp32 once): neither the distances nor their band are written, and a half-width's bits do not
+ * depend on the other half-widths of the call.  It differs from a numba run of the reference only where that run's out-of-bounds writes
+ * land.  n_half > MMK_NOVELTY_MAX_KERNELS, a half-width > MMK_NOVELTY_MAX_HALF: MMK_ERR_UNSUPPORTED; frames < 2, bins,
+ * batch, n_half or a half-width < 1: MMK_ERR_INVALID.
+ *
+ * mmk_novelty_finish_f32: scores[b][q][i] = raw[b][q][i] - min_i raw[b][q][:] and dg[b][i] = (sum_q scores[b][q][i]) / n_half, the sum in
+ * rising q.  scores (batch, n_half, frames) and dg (batch, frames) contiguous, neither overlapping raw.  Workspace:
+ * mmk_novelty_finish_workspace_floats(batch, n_half, frames) floats (one per 4096 frames of a row).
+ *
+ * mmk_pick_peaks_f32: picked[m] (one byte per index) = 1 where pick_globally_sorted_maxes(x, wait_before, wait_after, min_strength)
+ * accepts index m, else 0.  With lo / hi the global minimum / maximum of x, a candidate is an index with x[m] > x[m-1] and x[m] >= x[m+1]
+ * (the ends padded with themselves), (x[m] - min of x over scipy's window of wait_before + wait_after around m, lo outside the array)
+ * / (hi - lo) >= min_strength (evaluated in fp64), and x[m] above the means of x[max(0, m - wait_before) : m] and of
+ * x[m : min(n, m + wait_after)] (fp64 sums in rising index order).  Candidates are taken by falling x, equal values by rising index (the
+ * reference's argsort is not stable there), and one is accepted unless an accepted one lies in [m - wait_before, m + wait_after).  A
+ * constant x has no candidate.  Three launches, the last one workgroup; no host synchronisation.  Workspace:
+ * mmk_pick_peaks_workspace_bytes(n) = 4 n + 8 bytes.  A wait > MMK_NOVELTY_MAX_WAIT: MMK_ERR_UNSUPPORTED; n < 1, a negative wait, both
+ * waits 0 or a NaN min_strength: MMK_ERR_INVALID.
+ *
+ * All three: 4-byte alignment of the float data is enough, tails are masked here, nothing but the stated outputs and workspace is written,
+ * no atomics: two calls give the same bits.  NaN in the inputs is not handled. */
+#define MMK_NOVELTY_TILE 64
+#define MMK_NOVELTY_MAX_KERNELS 8
+#define MMK_NOVELTY_MAX_HALF 32
+#define MMK_NOVELTY_MAX_WAIT 1024
+int mmk_novelty_f32(const float* x, int64_t x_batch_stride, int64_t x_row_stride, const float* inv_norm, int32_t batch, int64_t frames,
+                    int32_t bins, const int32_t* halves, int32_t n_half, float* raw, mmk_stream_t stream);
+size_t mmk_novelty_finish_workspace_floats(int32_t batch, int32_t n_half, int64_t frames);
+int mmk_novelty_finish_f32(const float* raw, int32_t batch, int32_t n_half, int64_t frames, float* scores, float* dg, float* workspace,
+                           size_t workspace_floats, mmk_stream_t stream);
+size_t mmk_pick_peaks_workspace_bytes(int64_t n);
+int mmk_pick_peaks_f32(const float* x, int64_t n, int32_t wait_before, int32_t wait_after, double min_strength, uint8_t* picked,
+                       void* workspace, size_t workspace_bytes, mmk_stream_t stream);
+
 /* Principal components of corpus frames (mimikit/features/functionals.py:1114-1138 PCA: sklearn's StandardScaler, then sklearn's PCA).
  * x: n frames of d bins, fp32, rows x_row_stride apart; everything else is fp64 on the device and contiguous.
  *

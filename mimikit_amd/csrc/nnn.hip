@@ -45,13 +45,8 @@ __global__ __launch_bounds__(256) void inv_row_norm_kernel(const float* __restri
   const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (g >= total) return;
   const float* p = x + (g / rows) * batch_stride + (g % rows) * row_stride;
-  float a = 0.f;
-  for (int k = lane; k < K; k += 64) {
-    const float v = p[k];
-    a = fmaf(v, v, a);
-  }
-  a = wave_sum(a);
-  if (lane == 0) out[g] = a > 0.f ? 1.0f / sqrtf(a) : 0.f;
+  const float r = wave_inv_row_norm(p, K, lane);
+  if (lane == 0) out[g] = r;
 }
 
 // ---- cosine cost -------------------------------------------------------------------------------------------------------------------

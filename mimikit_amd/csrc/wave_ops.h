@@ -106,6 +106,17 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
+// 1 / |row|_2 of K floats at p, 0 for a row of norm 0: lane l adds the squares of bins l, l + 64, ... in turn, the butterfly joins the lanes.
+// The whole of inv_row_norm_kernel (nnn.hip); novelty.hip calls it for the rows of a tile where the caller passes no norms.
+__device__ __forceinline__ float wave_inv_row_norm(const float* __restrict__ p, int K, int lane) {
+  float a = 0.f;
+  for (int k = lane; k < K; k += 64) {
+    const float v = p[k];
+    a = fmaf(v, v, a);
+  }
+  a = wave_sum(a);
+  return a > 0.f ? 1.0f / sqrtf(a) : 0.f;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));

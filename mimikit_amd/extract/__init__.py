@@ -1,2 +1,3 @@
 from .from_neighbors import *
 from .clusters import *
+from .segment import *

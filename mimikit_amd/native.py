@@ -191,6 +191,11 @@ _SIGNATURES = {
     "mmk_hpss_f32": (i32, [vp, i64, i64, i32, i64, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, i64, i64, vp]),
     "mmk_melbank_f32": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, vp]),
     "mmk_stft_mel_f32": (i32, [vp, i64, i32, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, vp]),
+    "mmk_novelty_f32": (i32, [vp, i64, i64, vp, i32, i64, i32, vp, i32, vp, vp]),
+    "mmk_novelty_finish_workspace_floats": (C.c_size_t, [i32, i32, i64]),
+    "mmk_novelty_finish_f32": (i32, [vp, i32, i32, i64, vp, vp, vp, C.c_size_t, vp]),
+    "mmk_pick_peaks_workspace_bytes": (C.c_size_t, [i64]),
+    "mmk_pick_peaks_f32": (i32, [vp, i64, i32, i32, C.c_double, vp, vp, C.c_size_t, vp]),
     "mmk_istft_n_samples": (i64, [i64, i32, i32]),
     "mmk_istft_workspace_floats": (C.c_size_t, [i32, i64, i32]),
     "mmk_istft_f32": (i32, [vp, i32, i32, i64, i32, i32, vp, vp, vp]),
@@ -1013,6 +1018,85 @@ def melbank(s: torch.Tensor, bank=None, dct: Optional[torch.Tensor] = None) -> t
         return out.reshape(*s.shape[:-1], n_out)
     check(lib().mmk_melbank_f32(ptr(s2), s2.stride(0), s2.shape[0], n_bins, *args, ptr(out), stream_ptr(s.device)), "mmk_melbank_f32")
     return out.reshape(*s.shape[:-1], n_out)
+
+
+# include/mmk.h: MMK_NOVELTY_* - output frames of one workgroup of mmk_novelty_f32, the half-widths one launch sums, the largest of them and the
+# longest wait of mmk_pick_peaks_f32 (csrc/novelty.hip); the tests place their sizes on these
+NOVELTY_TILE = 64
+NOVELTY_MAX_KERNELS = 8
+NOVELTY_MAX_HALF = 32
+NOVELTY_MAX_WAIT = 1024
+
+
+def _novelty_halves(halves, what: str):
+    halves = [int(h) for h in halves]
+    if not halves or min(halves) < 1:
+        raise ValueError(f"{what}: half-widths must be positive integers, got {halves}")
+    if len(halves) > NOVELTY_MAX_KERNELS:
+        raise NotImplementedError(f"{what}: {len(halves)} half-widths, the limit is {NOVELTY_MAX_KERNELS}")
+    if max(halves) > NOVELTY_MAX_HALF:
+        raise NotImplementedError(f"{what}: half-width {max(halves)}, the limit is {NOVELTY_MAX_HALF}")
+    return halves
+
+
+def novelty(x: torch.Tensor, halves: Sequence[int], inv_norm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x (T, D) or (B, T, D) fp32, bins contiguous, frames and clips at any stride; halves: up to NOVELTY_MAX_KERNELS half-widths in
+    [1, NOVELTY_MAX_HALF]; inv_norm (T,) / (B, T) = inv_row_norm(x), computed inside the kernel if not given -> raw (len(halves), T) or
+    (B, len(halves), T) fp32: the normalised checkerboard of 2 h + 1 summed along the diagonal of the cosine self-distance matrix, centred on
+    (i, i - 1), terms outside the matrix counting 0 (``mmk_novelty_f32``, one launch, the matrix is never formed)"""
+    halves = _novelty_halves(halves, "novelty")
+    x = _nnn_frames(x, 2 if isinstance(x, torch.Tensor) and x.dim() == 2 else 3, "novelty")
+    x3 = x.unsqueeze(0) if x.dim() == 2 else x
+    batch, frames, bins = x3.shape
+    if batch < 1 or bins < 1 or frames < 2:
+        raise ValueError(f"novelty: at least two frames of at least one bin per clip, got {tuple(x.shape)}")
+    if inv_norm is not None:
+        require_device(inv_norm)
+        if inv_norm.shape != x.shape[:-1] or inv_norm.dtype != torch.float32 or not inv_norm.is_contiguous():
+            raise ValueError(f"novelty: inv_norm must be {tuple(x.shape[:-1])} contiguous float32 values, got {tuple(inv_norm.shape)} {inv_norm.dtype}")
+    raw = torch.empty((batch, len(halves), frames), dtype=torch.float32, device=x.device)
+    check(lib().mmk_novelty_f32(ptr(x3), x3.stride(0), x3.stride(1), ptr(inv_norm), batch, frames, bins, (i32 * len(halves))(*halves), len(halves),
+                                ptr(raw), stream_ptr(x.device)), "mmk_novelty_f32")
+    return raw[0] if x.dim() == 2 else raw
+
+
+def novelty_finish(raw: torch.Tensor):
+    """raw (n_half, T) or (B, n_half, T) fp32 -> (scores of the same shape, dg (T,) or (B, T)): scores = raw minus its minimum over the frames,
+    dg = the mean of the scores over the half-widths (``mmk_novelty_finish_f32``)"""
+    raw = _nnn_frames(raw, 2 if isinstance(raw, torch.Tensor) and raw.dim() == 2 else 3, "novelty_finish").contiguous()
+    r3 = raw.unsqueeze(0) if raw.dim() == 2 else raw
+    batch, n_half, frames = r3.shape
+    if min(batch, n_half, frames) < 1:
+        raise ValueError(f"novelty_finish: empty input {tuple(raw.shape)}")
+    if n_half > NOVELTY_MAX_KERNELS:
+        raise NotImplementedError(f"novelty_finish: {n_half} half-widths, the limit is {NOVELTY_MAX_KERNELS}")
+    scores = torch.empty_like(r3)
+    dg = torch.empty((batch, frames), dtype=torch.float32, device=raw.device)
+    n_work = lib().mmk_novelty_finish_workspace_floats(batch, n_half, frames)
+    work = torch.empty((n_work,), dtype=torch.float32, device=raw.device)
+    check(lib().mmk_novelty_finish_f32(ptr(r3), batch, n_half, frames, ptr(scores), ptr(dg), ptr(work), n_work, stream_ptr(raw.device)),
+          "mmk_novelty_finish_f32")
+    return (scores[0], dg[0]) if raw.dim() == 2 else (scores, dg)
+
+
+def pick_peaks(x: torch.Tensor, wait_before: int, wait_after: int, min_strength: float = 0.02) -> torch.Tensor:
+    """x (T,) fp32 -> picked (T,) bool on the device: the indices the reference's pick_globally_sorted_maxes accepts (equal values taken by
+    rising index); no host synchronisation (``mmk_pick_peaks_f32``)"""
+    wait_before, wait_after = int(wait_before), int(wait_after)
+    if min(wait_before, wait_after) < 0 or wait_before + wait_after < 1:
+        raise ValueError(f"pick_peaks: waits must be non-negative and not both zero, got {wait_before}, {wait_after}")
+    if max(wait_before, wait_after) > NOVELTY_MAX_WAIT:
+        raise NotImplementedError(f"pick_peaks: waits of {wait_before}, {wait_after}, the limit is {NOVELTY_MAX_WAIT}")
+    x = _nnn_frames(x, 1, "pick_peaks")
+    if x.shape[0] < 1:
+        raise ValueError("pick_peaks: empty input")
+    n = x.shape[0]
+    picked = torch.empty((n,), dtype=torch.uint8, device=x.device)
+    n_work = lib().mmk_pick_peaks_workspace_bytes(n)
+    work = torch.empty((n_work // 4,), dtype=torch.int32, device=x.device)
+    check(lib().mmk_pick_peaks_f32(ptr(x), n, wait_before, wait_after, float(min_strength), ptr(picked), ptr(work), n_work, stream_ptr(x.device)),
+          "mmk_pick_peaks_f32")
+    return picked.bool()
 
 
 def stft_mel(x: torch.Tensor, n_fft: int, hop: int, center: bool, pad_mode: str, bank, dct: Optional[torch.Tensor] = None) -> torch.Tensor:
