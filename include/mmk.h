@@ -14,9 +14,29 @@
  *     `tensor.data_ptr()`); sizes and strides are explicit, in ELEMENTS;
  *   - the library allocates no device memory: plans take a caller-provided
  *     workspace whose size is reported by `*_workspace_bytes`;
- *   - kernels are enqueued on the `stream` argument (a `hipStream_t`, passed as
- *     void*) and the library never synchronises it, except inside
- *     `*_commit` which may wait for its own one-off graph capture;
+ *   - streams.  Every kernel, memset and copy of a call is enqueued on its `stream` argument (a `hipStream_t`, passed as void*; any
+ *     stream, blocking or not) and on no other: nothing goes to the null stream, and a call returns without waiting for `stream`
+ *     - with the exceptions listed here, each of which waits for `stream` (and for nothing else) and so cannot be captured into a
+ *     graph.  tests/stream_cases.py lists every entry point under one of the two rules and tests/test_gpu_streams.py holds it to it
+ *     behind a busy side stream.
+ *       mmk_wavenet_commit, mmk_srnn_commit, mmk_s2s_commit, mmk_tr_commit: may wait - before the workspace is laid out anew
+ *         (replays of a cached graph may still be queued) and after host-built tables were copied;
+ *       mmk_srnn_reset: reads the plan's error word back first;
+ *       mmk_wavenet_sync_status, mmk_srnn_sync_status, mmk_s2s_sync_status: wait, then read the plan's error word (on `stream`)
+ *         and clear it where it is reported;
+ *       mmk_wavenet_inject_sync_error, mmk_srnn_inject_sync_error, mmk_s2s_inject_sync_error: wait for their write of the word;
+ *       mmk_wavenet_profile_steps: waits for its events;
+ *       mmk_edge_components_i64: once per four rounds, to read its changed-flag;
+ *       mmk_pca_eig_f64: every 8 iterations, to read its convergence flag.
+ *     Two more waits depend on what came before the call.  mmk_wavenet_warmup, mmk_wavenet_generate, mmk_srnn_warmup(_multi),
+ *     mmk_srnn_generate(_multi) and mmk_tr_generate replay a cached graph of their step kernels from a block length on (16 steps; SampleRNN: two periods of
+ *     frame_sizes[0]); the graph is keyed by the call's pointers, strides and phase, and a call whose key differs from the cached
+ *     one waits for `stream` before it captures again (shorter blocks and repeated keys do not wait).  And the first spectral call
+ *     of a process on a device (mmk_stft*_f32, mmk_istft_f32, mmk_gla_f32) builds the twiddle and window tables on its `stream` and
+ *     waits for them once; later calls, on any stream, find them ready.
+ *     A plan is driven from ONE stream at a time: its workspace, queues and error word are ordered by that stream alone, and a
+ *     caller who moves a plan to another stream synchronises the old one first.  The stateless functions keep nothing between
+ *     calls but those tables: two of them may run on two streams at once, each with its own workspace;
  *   - no torch / C++ types cross the boundary;
  *   - diagnostics (in-kernel phase stamps, timing experiments that change results) are compiled only into the diagnostic
  *     build of the library (`python -m mimikit_amd.build --diag` -> libmmk_hip_diag.so, -DMMK_DIAG); the product library has
@@ -653,7 +673,7 @@ int mmk_wavenet_mode(const mmk_wavenet_plan* plan);
 /* 1 when the plan's last mode-5 launch streamed the clips through the stages two at a time (csrc/wavenet_spipe_pair.inc: an even number of clips,
  * 54 to 128 of them; the plan switch MMK_WN_SPIPE_PAIR=0 / 1 refuses / asks for it from 24 clips on), 0 otherwise */
 int mmk_wavenet_pair_visits(const mmk_wavenet_plan* plan);
-/* waits for `stream`; MMK_ERR_STATE if a hand-off inside the persistent kernel timed out */
+/* waits for `stream`; MMK_ERR_STATE (and the word is cleared) if a hand-off inside the persistent kernel timed out since the last call */
 int mmk_wavenet_sync_status(mmk_wavenet_plan* plan, mmk_stream_t stream);
 /* Fault injection for the callers' tests: marks the plan as if a hand-off of its last call had timed out, so that the next
  * mmk_wavenet_sync_status fails exactly as it would after a real time-out (and the caller's redo path runs). */

@@ -1079,12 +1079,17 @@ extern "C" int mmk_srnn_inject_sync_error(mmk_srnn_plan* p, mmk_stream_t stream)
 extern "C" int mmk_srnn_sync_status(mmk_srnn_plan* p, mmk_stream_t stream) {
   if (!p) return fail(MMK_ERR_INVALID, "srnn_sync_status: null plan");
   hipStream_t st = (hipStream_t)stream;
-  MMK_HIP(hipStreamSynchronize(st));
-  if (!p->committed) return MMK_OK;
+  if (!p->committed) {
+    MMK_HIP(hipStreamSynchronize(st));
+    return MMK_OK;
+  }
+  // the read and the clear go on `st` like everything else of the plan: the null stream is not ordered against a non-blocking stream,
+  // and a clear on it could land after the caller's next launch on `st`
   int64_t err = 0;
-  MMK_HIP(hipMemcpy(&err, p->tau + 4, sizeof(err), hipMemcpyDeviceToHost));
+  MMK_HIP(hipMemcpyAsync(&err, p->tau + 4, sizeof(err), hipMemcpyDeviceToHost, st));
+  MMK_HIP(hipStreamSynchronize(st));
   if (err != 0) {
-    MMK_HIP(hipMemset(p->tau + 4, 0, sizeof(int64_t)));
+    MMK_HIP(hipMemsetAsync(p->tau + 4, 0, sizeof(int64_t), st));
     return fail(MMK_ERR_STATE, "srnn: a wait inside the tier / bottom kernels timed out (code %lld: 3 tier hand-over, 6 bottom role / 7 tier role of the resident kernel) - "
                 "its workgroups were not all running side by side; the samples of this generation are invalid",
                 (long long)err);

@@ -1408,10 +1408,17 @@ extern "C" int mmk_wavenet_inject_sync_error(mmk_wavenet_plan* p, mmk_stream_t s
 
 extern "C" int mmk_wavenet_sync_status(mmk_wavenet_plan* p, mmk_stream_t stream) {
   if (!p) return fail(MMK_ERR_INVALID, "wavenet_sync_status: null plan");
-  MMK_HIP(hipStreamSynchronize((hipStream_t)stream));
-  if (!p->committed || !p->persistent) return MMK_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (!p->committed || !p->persistent) {
+    MMK_HIP(hipStreamSynchronize(st));
+    return MMK_OK;
+  }
+  // the read and the clear go on `st` like everything else of the plan: the null stream is not ordered against a non-blocking stream.
+  // The word is sticky over launches and cleared where it is reported (once), as the SampleRNN and Seq2Seq plans do
   int32_t flag = 0;
-  MMK_HIP(hipMemcpy(&flag, p->err_flag, sizeof(flag), hipMemcpyDeviceToHost));
+  MMK_HIP(hipMemcpyAsync(&flag, p->err_flag, sizeof(flag), hipMemcpyDeviceToHost, st));
+  MMK_HIP(hipStreamSynchronize(st));
+  if (flag != 0) MMK_HIP(hipMemsetAsync(p->err_flag, 0, sizeof(int32_t), st));
   if (flag == 2)
     return fail(MMK_ERR_STATE, "wavenet: the persistent kernel's workgroups were not spread 8 x %d over the XCDs; rerun with MMK_WN_XCD_LOCAL=0 (agent-scope hand-offs)", p->Gn);
   if (flag != 0)
