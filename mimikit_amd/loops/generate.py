@@ -172,6 +172,7 @@ class GenerateLoopV2:
         self.logger = logger
         self._initial_device = None
         self._was_training = False
+        self._moved = False
         self.device = None
         self.template_vars = {}
 
@@ -194,7 +195,15 @@ class GenerateLoopV2:
         torch.set_grad_enabled(True)
 
     def run(self):
+        """a generator: whoever stops reading it early closes it (``gen.close()``), and the teardown - grad mode on, the network's mode and
+        device as they were found - runs either way (the reference's sits behind the loop and is skipped by a reader that just stops)"""
         self.setup()
+        try:
+            yield from self._batches()
+        finally:
+            self.teardown()
+
+    def _batches(self):
         net = self.network
         for batch in self.dataloader:
             prompt_idx, batch = batch[0], batch[1:]
@@ -226,7 +235,6 @@ class GenerateLoopV2:
             yield final_outputs
             if self.config.callback is not None:
                 self.config.callback(final_outputs)
-        self.teardown()
 
     def process_outputs(self, final_outputs: Tuple[torch.Tensor, ...], prompt_idx, **template_vars):
         wants_audio = self.logger is not None and (self.config.write_waveform or self.config.display_waveform)

@@ -18,20 +18,19 @@ def generate_chunks(config: "GenerateLoopV2.Config", network, seed: torch.Tensor
     return new generate parameters for the next chunk (the reference walks the temperatures randomly, :47-48)."""
     if config.yield_inversed_outputs:
         raise ValueError("generate_chunks feeds every chunk back as the next prompt: set yield_inversed_outputs=False")
-    sr = network.config.io_spec.sr
     n_steps = GenerateLoopV2.get_n_steps(config, network)
     n_prompt = seed.shape[1]
     prompt = seed
     for i in range(n_chunks):
         loader = [[np.ones(1), prompt]]
         loop = GenerateLoopV2(config, network, n_steps, loader, logger=None)
-        out = None
-        for output in loop.run():
-            out = output[0]
-            break
+        gen = loop.run()
+        try:
+            out = next(gen)[0]
+        finally:
+            gen.close()         # (runs the loop's teardown: grad mode, the network's mode and device as they were found)
         new = out[:, n_prompt:]
         yield new
         prompt = out[:, -n_prompt:]
         if update_parameters is not None and config.parameters is not None:
             config.parameters = update_parameters(config.parameters, i)
-    del sr

@@ -15,6 +15,11 @@ event (``run_event`` and ``get_n_steps`` read ``net.config``, which the class do
 is resampled to ``nnn.sr`` and framed by ``nnn.feature``, ``generate_block`` returns the corpus frames that continue it - as many as
 ``GenerateLoopV2.get_n_steps`` counts for a framed target - and ``nnn.feature.inv`` (Griffin-Lim) and ``Resample`` bring them back.  The
 event's temperature is ignored.
+
+Three things differ from the reference on purpose ("The callers' timeline, restated"): a piece longer than the room left is clipped
+(the reference raises a shape error; only a framed event, whose piece is up to one hop longer than ``seconds``, gets there); a prompt that
+holds a class outside the network's input classes raises ``IndexError`` before the loop (the reference's embedding raises, the step kernels
+would not); and after an event grad mode, the network's mode and its device are what the loop's teardown leaves (the reference skips it).
 """
 import dataclasses as dtc
 from typing import Dict, Iterator, Optional, Tuple, Union
@@ -22,9 +27,9 @@ from typing import Dict, Iterator, Optional, Tuple, Union
 import torch
 
 from ..checkpoint import Checkpoint
-from ..features.functionals import Resample
+from ..features.functionals import Discrete, Resample
 from ..features.item_spec import Sample, convert
-from ..loops.generate import GenerateLoopV2
+from ..loops.generate import GenerateLoopV2, _same_device
 from ..networks.arm import ARM
 from ..utils import default_device
 from .nnn import NearestNextNeighbor
@@ -98,7 +103,12 @@ class EnsembleGenerator:
         if self.print_events:
             print({"generator": type(net).__name__, "seconds": event.seconds, "temperature": event.temperature,
                    "start": t / self.base_sr})
-        return self.run_event(inputs, net.to(self.device), n_steps, params)
+        home = net.device
+        try:
+            return self.run_event(inputs, net.to(self.device), n_steps, params)
+        finally:
+            if not _same_device(home, self.device):
+                net.to(home)        # (as the loop's teardown does for a network it moved itself)
 
     def next_event(self) -> Tuple[Event, ARM, int, Dict]:
         event = Event(**next(self.stream))
@@ -118,6 +128,14 @@ class EnsembleGenerator:
         to_net, to_base = Resample(self.base_sr, spec.sr), Resample(spec.sr, self.base_sr)
         at_net_rate = to_net(inputs)
         prompts = [feature.transform(at_net_rate) for feature in spec.inputs]
+        for feature, prompt in zip(spec.inputs, prompts):
+            # a window louder than 1 (after an Emphasis in front of the coder, or by the resampler's overshoot) makes the mu-law formula
+            # return a code past the last class.  The reference's nn.Embedding raises on it; the step kernels stay memory-safe and would
+            # go on from a NaN row, silently - so it is raised here, once per event
+            kind = feature.elem_type
+            if isinstance(kind, Discrete) and prompt.numel() and not (0 <= int(prompt.min()) and int(prompt.max()) < kind.size):
+                raise IndexError(f"index out of range: the event's prompt holds the class {int(prompt.max())} (smallest {int(prompt.min())}), "
+                                 f"the network's input has {kind.size} classes - the window leaves [-1, 1] in front of the coder")
         # a framed input (an STFT) covers fewer samples than it was given: what the loop returns in front of the new audio
         # is the prompt as the TARGET unit counts it
         kept = convert(prompts[0].shape[1], spec.targets[0].unit, Sample(sr=spec.sr), True)
@@ -125,8 +143,12 @@ class EnsembleGenerator:
                                                     yield_inversed_outputs=True),
                               network=net, n_steps=n_steps, logger=None,
                               dataloader=[[torch.ones(1), *prompts]])      # (first entry: the prompt's index, unused without a logger)
-        outputs = next(iter(loop.run()))
-        return to_base(outputs[0][:, kept:])
+        gen = loop.run()
+        try:
+            outputs = next(gen)
+            return to_base(outputs[0][:, kept:])
+        finally:
+            gen.close()         # (the loop puts grad mode and the network's mode back: its teardown is skipped by a reader that just stops)
 
     def run_nnn_event(self, inputs: torch.Tensor, nnn: NearestNextNeighbor, n_frames: int) -> torch.Tensor:
         to_nnn, to_base = Resample(self.base_sr, nnn.sr), Resample(nnn.sr, self.base_sr)

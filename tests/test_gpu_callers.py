@@ -137,12 +137,26 @@ def test_ensemble_generator_chains_networks_across_sample_rates(device):
     seg1 = out[:, 2205:2205 + 441]
     assert float(seg1.abs().max()) > 0
     assert float(out[:, 2205 + 441 + 221 + 5:].abs().max()) == 0.0      # nothing after the two events
-    # oracle composition of event 1
-    x16 = O.resample(prompt, 22050, 16000)
-    codes = O.mulaw_compress(x16)
-    full = O.SampleRNNOracle(sd, **arch).generate(codes, 320)
-    want = O.resample(O.mulaw_expand(full)[:, codes.shape[1]:], 16000, 22050)
-    assert want.shape[1] == 441
+    # oracle composition of event 1.  A resampled sample within fp32 rounding of a mu-law bin edge may flip a code, so the device's codes
+    # are held to the per-element rule (tests/caller_refs.py: the float64 code of the float64 sample, or that sample lies within the
+    # resample kernel's bound of an edge, and then at most one code off) and the oracle generates from THOSE codes: the comparison always runs
+    from mimikit_amd.features.functionals import resample_filter_bank
+    from tests import caller_refs as cr, f64_bounds as fb
+    orig, new, width, table = resample_filter_bank(22050, 16000)
+    x64, bound = fb.resample_ref(prompt.double(), table.double(), orig, new, width)
     got_codes = mmk.MuLawCompress()(mmk.Resample(22050, 16000)(prompt.to(device))).cpu()
-    if torch.equal(got_codes, codes):                       # (a sample within fp32 rounding of a mu-law bin edge may flip a code)
-        assert float((seg1 - want).abs().max()) <= 1e-5
+    wrong, share = cr.mulaw_rule(got_codes, x64, bound, 256, 1.0)
+    assert not bool(wrong.any()) and share <= cr.EDGE_SHARE_CAP, (int(wrong.sum()), share)
+    codes = O.mulaw_compress(O.resample(prompt, 22050, 16000))
+    print(f"[callers] {int((got_codes != codes).sum())} of {codes.numel()} device codes differ from the fp32 oracle's; {share:.4%} of the samples lie near an edge")
+    full = O.SampleRNNOracle(sd, **arch).generate(got_codes, 320)
+    want = O.resample(O.mulaw_expand(full)[:, got_codes.shape[1]:], 16000, 22050)
+    assert want.shape[1] == 441
+    assert float((seg1 - want).abs().max()) <= 1e-5
+    # both events, and the silence behind them, bit for bit: the re-walk of the finished clip along the restated timeline
+    events = [cr.Ev("class", 16000, 0.02), cr.Ev("class", 16000, 0.01), cr.Ev("class", 16000, 1.0)]
+    tl = cr.timeline(2205, 22050, 0.14, events)
+    players = [cr.Player(ev, net.to(device)) for ev, net in zip(events, (srnn, wn, srnn))]
+    again, records = cr.rewalk(out.to(device), 2205, players, tl, seed=0)
+    assert [r is not None for r in records] == [True, True, False] and torch.equal(again.cpu(), out)
+    assert float(out[:, cr.silence_mask(tl)].abs().max()) == 0.0

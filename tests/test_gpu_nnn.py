@@ -208,6 +208,7 @@ def test_ensemble_runs_an_nnn_event(device):
     seconds = 0.1
     eg = mmk.EnsembleGenerator(prompt, max_seconds=0.3, base_sr=base_sr, stream=iter([dict(generator=nnn, seconds=seconds, temperature=0.3),
                                                                                        dict(generator=nnn, seconds=10.0)]), device=device)
+    torch.manual_seed(31)                                  # (Griffin-Lim draws its initial phases from the device generator)
     out = eg.run()
     n0 = prompt.shape[1]
     assert out.shape == (1, int(0.3 * base_sr)) and bool(torch.isfinite(out).all())
@@ -226,6 +227,13 @@ def test_ensemble_runs_an_nnn_event(device):
     region = out[:, n0:n0 + n_new]
     assert float(region.abs().max()) > 0
     assert float(out[:, n0 + n_new:].abs().max()) == 0.0   # the second event does not fit: the tail stays blank
+    # the audio itself, bit for bit: the re-walk of the clip along the restated timeline, phases redrawn under the same seed
+    from tests import caller_refs as cr
+    events = [cr.Ev("nnn", sr, seconds, 256, 64), cr.Ev("nnn", sr, 10.0, 256, 64)]
+    tl = cr.timeline(n0, base_sr, 0.3, events)
+    assert tl.slots[0].fits and not tl.slots[1].fits and (tl.slots[0].at, tl.slots[0].written) == (n0, n_new)
+    again, _ = cr.rewalk(out, n0, [cr.Player(ev, nnn) for ev in events], tl, seed=31)
+    assert torch.equal(again[:, n0:n0 + n_new], region) and torch.equal(again, out)
 
 
 def test_ensemble_mixes_a_network_and_an_nnn_event(device):
@@ -233,9 +241,18 @@ def test_ensemble_mixes_a_network_and_an_nnn_event(device):
     nnn = NearestNextNeighbor(mmk.MagSpec(256, 64), _corpus(), sr=16000, device=device)
     prompt = (torch.rand(2, 2205, generator=torch.Generator().manual_seed(6)) * 2 - 1) * 0.5
     stream = iter([dict(generator=srnn, seconds=0.02), dict(generator=nnn, seconds=0.05), dict(generator=srnn, seconds=1.0)])
+    torch.manual_seed(32)
     out = mmk.EnsembleGenerator(prompt, max_seconds=0.25, base_sr=22050, stream=stream, device=device).run().cpu()
     torch.set_grad_enabled(False)
     assert out.shape == (2, int(0.25 * 22050)) and bool(torch.isfinite(out).all())
     assert torch.equal(out[:, :2205], prompt)
     seg_net, seg_nnn = out[:, 2205:2205 + 441], out[:, 2205 + 441:2205 + 441 + 1000]
     assert float(seg_net.abs().max()) > 0 and float(seg_nnn.abs().max()) > 0
+    # both regions bit for bit, and silence where the third event did not fit
+    from tests import caller_refs as cr
+    events = [cr.Ev("class", 16000, 0.02), cr.Ev("nnn", 16000, 0.05, 256, 64), cr.Ev("class", 16000, 1.0)]
+    tl = cr.timeline(2205, 22050, 0.25, events)
+    assert [(s.at, s.written) for s in tl.slots] == [(2205, 441), (2646, 1059), (3705, 5512 - 3705)]
+    players = [cr.Player(ev, net) for ev, net in zip(events, (srnn.to(device), nnn, srnn))]
+    again, _ = cr.rewalk(out.to(device), 2205, players, tl, seed=32)
+    assert torch.equal(again.cpu(), out) and float(out[:, cr.silence_mask(tl)].abs().max()) == 0.0
