@@ -329,6 +329,8 @@ class Seq2SeqLSTMNetwork(HipPlanned, ARMWithHidden, nn.Module):
         self.dec.hidden = [None] * self._config.dec_n_lstm
 
     def before_generate(self, prompts: Tuple[torch.Tensor, ...], batch_index) -> None:
+        """a step keeps no state between calls, so nothing of the plan is put back here: every step clears the states it starts from and
+        poisons its exchange images itself (tests/test_gpu_plan_lives.py::test_seq2seq_plan_lives holds that across generations)"""
         self.reset_hidden()
         native.require_device(*tuple(prompts))
         self._blocks = []

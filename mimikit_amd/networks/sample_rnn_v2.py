@@ -265,7 +265,9 @@ class SampleRNN(HipPlanned, ARMWithHidden, nn.Module):
         self._resident_seen = 0
 
     def _weights_checked(self, repacked: bool):
-        """a generation starts from h0: packing the weights leaves the hidden states there, otherwise they are put back"""
+        """a generation starts from h0: packing the weights leaves the hidden states there, otherwise they are put back
+        (tests/test_gpu_plan_lives.py::test_sample_rnn_plan_lives holds that, and the resident path's own clears: four generations on one
+        plan, bit for bit against a fresh plan)"""
         if not repacked:
             self._plan.reset()
         self._next_t = None

@@ -206,6 +206,8 @@ class SimpleTransformer(HipPlanned, ARM, nn.Module):
 
     # -- ARM generation protocol ------------------------------------------------------
     def before_generate(self, prompts: Tuple[torch.Tensor, ...], batch_index) -> None:
+        """the weights are checked; the plan's KV rows, step counter and stored graph need no reset: a call rewrites what it reads, and the
+        graph is keyed by the call's pointers and strides (tests/test_gpu_plan_lives.py::test_transformer_plan_lives holds that)"""
         prompts = tuple(prompts)
         native.require_device(*prompts)
         self._ensure_plan(prompts[0].size(0), refresh_weights=True)

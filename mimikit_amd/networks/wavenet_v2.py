@@ -382,7 +382,9 @@ class WaveNet(HipPlanned, ARM, nn.Module):
         return not native.wn_bpipe_by_default(batch) and self._plan.batch_pipelined and b"MMK_WN_BPIPE=1" not in tuning
 
     def _weights_checked(self, repacked: bool):
-        """the queues need no clearing: every slot a step reads is rewritten by the warm-up that precedes it"""
+        """the queues need no clearing: every slot a step reads is rewritten by the warm-up that precedes it
+        (tests/test_gpu_plan_lives.py::test_wavenet_plan_lives holds that: warm-ups from positions 3, 8 and 0 and fewer clips on one plan,
+        bit for bit against a fresh plan)"""
         self._next_t = None
 
     def _plan_tensors(self):

@@ -33,6 +33,11 @@ branch on, on the per-layer launch path or the padded heads of the pipelines) ad
 generators below; each says which device mistake it stands for).  They too are float64 variants, expressed through the state dict, the inputs
 or the oracle's keywords only, and each must leave tol_max.  A network of several targets has one output tensor, one E and one tolerance per
 target; a defect has left the envelope when it leaves tol_max of any one target.
+
+Lives (Life, lives, life_defects): the generations test_gpu_plan_lives.py runs on ONE plan - the case, then its clips behind a prompt 5
+longer with other inputs, then fewer clips behind the shortest prompt, then the case again.  A life is a view of its case with its own clips,
+prompt length, blocks and draw of the inputs; every function here that takes a case takes a life.  Their defects - (e) a prompt, (f) a ragged
+group's rows, (g) SampleRNN tier states of the life BEFORE - stand for what a reused workspace can do, and each must leave tol_max too.
 """
 import functools
 from typing import NamedTuple
@@ -150,45 +155,47 @@ def _multi_io(tag):
 ONE_CLIP, FOUR_CLIPS, LAUNCHES = 1, 2, 3      # mmk_srnn_bottom_kernel (include/mmk.h)
 
 
-def _wn_launches(p, k):
+# ran(plan, k, w=1): k counts the generate blocks (Seq2Seq: steps) the plan has run in its whole life; w the generations among them whose
+# warm-up was whole periods long (SampleRNN: the only ones a resident warm-up launch can take) - one generation, as in test_gpu_networks_f64.py: 1
+def _wn_launches(p, k, w=1):
     return not p.persistent
 
 
-def _wn_persist(p, k):
+def _wn_persist(p, k, w=1):
     return p.persistent and not p.chain and not p.layer_pipelined and not p.stage_pipelined
 
 
-def _wn_chain(p, k):
+def _wn_chain(p, k, w=1):
     return p.chain
 
 
-def _wn_lpipe(p, k):
+def _wn_lpipe(p, k, w=1):
     return p.layer_pipelined
 
 
-def _wn_spipe(p, k):
+def _wn_spipe(p, k, w=1):
     return p.stage_pipelined and not p.batch_pipelined and not p.pair_visits
 
 
-def _wn_spipe_pair(p, k):
+def _wn_spipe_pair(p, k, w=1):
     return p.stage_pipelined and not p.batch_pipelined and p.pair_visits
 
 
-def _wn_bpipe(p, k):
+def _wn_bpipe(p, k, w=1):
     return p.stage_pipelined and p.batch_pipelined
 
 
 def _bottom(kernel):
-    return lambda p, k: p.resident_blocks() == 0 and p.bottom_kernel() == kernel
+    return lambda p, k, w=1: p.resident_blocks() == 0 and p.bottom_kernel() == kernel
 
 
 def _resident(warmups=None):
-    return lambda p, k: p.resident_blocks() == k and (warmups is None or p.resident_warmups() == warmups)
+    return lambda p, k, w=1: p.resident_blocks() == k and (warmups is None or p.resident_warmups() == warmups * w)
 
 
 def _s2s_resident(layers, dec=None):
     """every bi-LSTM layer of every step as one resident launch: `layers` per side, or `layers` in the encoder and `dec` in the decoder"""
-    return lambda p, k: p.resident_launches() == k * (layers + (layers if dec is None else dec))
+    return lambda p, k, w=1: p.resident_launches() == k * (layers + (layers if dec is None else dec))
 
 
 def flags(case, p):
@@ -196,7 +203,7 @@ def flags(case, p):
     if case.kind in ("wavenet", "wavenet_frames"):
         return {n: bool(getattr(p, n)) for n in ("persistent", "chain", "layer_pipelined", "stage_pipelined", "batch_pipelined", "pair_visits")}
     if case.kind == "srnn":
-        return dict(bottom_kernel=p.bottom_kernel(), resident_blocks=p.resident_blocks())
+        return dict(bottom_kernel=p.bottom_kernel(), resident_blocks=p.resident_blocks(), resident_warmups=p.resident_warmups())
     return dict(resident_launches=p.resident_launches())
 
 
@@ -205,7 +212,7 @@ def streams(x):
     return tuple(x) if isinstance(x, (tuple, list)) else (x,)
 
 
-def _s2s_per_frame(p, k):
+def _s2s_per_frame(p, k, w=1):
     return p.resident_launches() == 0
 
 
@@ -265,9 +272,23 @@ class Case:
             return 2 * arch["frame_sizes"][0] + 3
         return self.hop
 
-    def inputs(self):
-        """the prompt and the conditioning inputs of the case (fp32 / int64, on the host)"""
-        g = torch.Generator().manual_seed(1000 + self.seed + self.clips)
+    draw = 0          # which draw of the inputs (a Life: its own)
+
+    @property
+    def shortest_prompt(self):
+        """the shortest prompt the network takes: the receptive field (the WaveNet warm-up then starts at position 0), frame_sizes[0], or
+        the `hop` frames a Seq2Seq step reads.  The oracle and the networks accept it for every case: no life needed another length."""
+        arch = self.arch
+        if self.kind in ("wavenet", "wavenet_frames"):
+            return O.wavenet_rf(arch["kernels"], arch["dilations"])
+        return arch["frame_sizes"][0] if self.kind == "srnn" else self.hop
+
+    def inputs(self, life=None):
+        """the prompt and the conditioning inputs of the case - or of `life`, a Life of it - (fp32 / int64, on the host)"""
+        if life is not None:
+            assert life.case is self
+            return life.inputs()
+        g = torch.Generator().manual_seed(1000 + self.seed + self.clips + 7919 * self.draw)
         P = self.P
         if self.kind == "wavenet_frames":
             return torch.rand(self.clips, P, 33, generator=g), ()
@@ -277,6 +298,63 @@ class Case:
             return tuple(torch.randint(0, q, (self.clips, P if k < self.targets else P + self.n), generator=g) for k, q in enumerate(self.q)), ()
         prompt = torch.randint(0, self.q[0], (self.clips, P), generator=g)
         return prompt, tuple(torch.rand(self.clips, P + self.n, 12, generator=g) for _ in range(self.cond))
+
+
+def spipe_pair_form(clips, forced=True):
+    """csrc/wavenet_spipe.h, wn_spipe_pair_form, restated for a forced MMK_WN_SPIPE_PAIR=1: the ring takes two clips per visit for an even
+    count of 24 .. 128 clips - of the CALL, not of the plan: a plan made for 24 clips serves 11 of them one clip per visit"""
+    return forced and clips % 2 == 0 and 24 <= clips <= 128
+
+
+class Life(Case):
+    """One generation among several that a case's network runs on ONE plan (test_gpu_plan_lives.py): a view of the case with its own clips,
+    prompt length P, blocks and draw of the inputs.  The network, the state dict, the oracle's keywords, `env` and `ran` are the case's - but
+    for the one flag that follows the call's batch instead of the plan's (spipe_pair_form).  inputs(), reference(), free_run(), envelope()
+    and defects() take a life wherever they take a case."""
+
+    def __init__(self, case, index, clips, P, parts, draw):
+        vars(self).update({k: v for k, v in vars(case).items() if k != "host"})
+        self.case, self.index, self.clips, self.parts, self.draw, self._P = case, index, clips, tuple(parts), draw, P
+        if case.ran is _wn_spipe_pair and not spipe_pair_form(clips):
+            self.ran = _wn_spipe
+
+    host = property(lambda self: self.case.host)
+    P = property(lambda self: self._P)
+
+    @property
+    def whole_period_warmup(self):
+        """SampleRNN: the warm-up runs the tiers over [fs0, P - P % fs0): at least one whole period, which a resident warm-up launch can take"""
+        fs0 = self.arch["frame_sizes"][0]
+        return self.P - self.P % fs0 - fs0 >= fs0
+
+    def reached(self):
+        """the indices into rows() of the steps a teacher-forced reference still computes from the prompt: the window of step j holds prompt
+        positions while j < rf; a Seq2Seq step reads the `hop` frames before it; a SampleRNN tier state carries the prompt without end"""
+        if self.kind == "srnn":
+            return list(range(len(self.rows())))
+        return [i for i, r in enumerate(self.rows()) if r < self.shortest_prompt]
+
+
+def life_parts(case):
+    """the blocks of lives 2 and 3: the first five (15 steps); in SampleRNN resident mode the first two, which are two resident launches; two
+    steps of `hop` frames for Seq2Seq - the oracle's cost per life stays near that of the case itself"""
+    if case.kind in ("s2s", "s2s_classes"):
+        return case.parts[:2]
+    return case.parts[:2] if case.parts in (RES_PARTS_16, RES_PARTS_32) else case.parts[:5]
+
+
+def lives(case):
+    """the four lives of a case on one plan:
+      1  the case itself
+      2  the case's clips, a prompt 5 longer (it starts below where life 1 ended: the tags and ring slots of life 1 lie ahead of it, on
+         other ring phases; the WaveNet warm-up starts at position 8, the SampleRNN warm-up offset is (P + 5) % fs0; Seq2Seq has no prompt
+         beyond `hop`: only the content changes), a prefix of the blocks, other inputs
+      3  max(1, clips // 2 - 1) clips - ragged against the groups of 2, 4 and 16 the kernels work in -, the shortest prompt, other inputs
+      4  life 1 again, bit for bit"""
+    B, P, short = case.clips, case.P, life_parts(case)
+    longer = P if case.kind in ("s2s", "s2s_classes") else P + 5
+    return [Life(case, 1, B, P, case.parts, 0), Life(case, 2, B, longer, short, 1),
+            Life(case, 3, max(1, B // 2 - 1), case.shortest_prompt, short, 2), Life(case, 4, B, P, case.parts, 0)]
 
 
 WN_PARTS = (1, 2, 3, 4, 5, 6, 7, 8, 9)                        # 45 steps, nine rows per clip, block ends on every small ring phase
@@ -377,7 +455,7 @@ def reference(case, sd, hist, conds=(), arch=None):
     arch = case.arch if arch is None else arch
     sd = O.fold_weight_norm(sd)                    # (in the dtype of `sd`; the Seq2Seq decoder with residuals is weight-normed)
     if case.kind in ("wavenet", "wavenet_frames"):
-        rf = P - 3
+        rf = O.wavenet_rf(arch["kernels"], arch["dilations"])
         lo, hi = P - rf, P + n - 1                 # ONE forward over the n windows: output j belongs to the window that starts at lo + j
         kw = dict(arch, embedding=False) if case.kind == "wavenet_frames" else arch
         inputs = tuple(x[:, lo:hi] for x in (*streams(hist), *conds))
@@ -550,6 +628,42 @@ def defects(case, history, conds, R64):
         yield from option(case, sd64, history, conds)
 
 
+def life_defects(life, history, conds, R64, prev_history, prev_R64, prev=None):
+    """(name, the float64 outputs with that one defect, the indices into rows() it is checked on) for the defects of a plan's later lives.
+    `prev_history` / `prev_R64`: the history and the float64 outputs (per target) of the life before, `prev` that life (for (g)):
+      (e) clip 0's prompt is the previous life's, position by position (the rings are addressed by absolute position): a queue, a ring or
+          a state the warm-up did not rewrite - on the rows the prompt still reaches (Life.reached)
+      (f) the last clip's rows are the previous life's rows of the same clip index and the same steps: a ragged group that was skipped
+      (g) SampleRNN, life 2: the tiers start from the previous life's final hidden states instead of h0 (the oracle keeps its tier states
+          in `hidden` and puts them back through reset_hidden(): with that method stubbed on the one instance it runs on from where the
+          generation before ended - nothing of the oracle is rewritten)"""
+    sd64 = O.fold_weight_norm(to64(life.sd))
+    P, n = life.P, life.n
+    first, prev_first = streams(history)[0], streams(prev_history)[0]
+    stale = first.clone()
+    stale[0, :P] = prev_first[0, :P]
+    assert not torch.equal(stale, first)
+    stale = (stale, *history[1:]) if life.multi else stale
+    yield "(e) clip 0's prompt is the previous life's", reference(life, sd64, stale, conds), life.reached()
+    every = list(range(len(life.rows())))
+    skipped = []
+    for r, pr in zip(per_target(R64), per_target(prev_R64)):
+        c = r.clone()
+        c[-1] = pr[life.clips - 1, :n]
+        skipped.append(c)
+    yield "(f) the last clip's rows are the previous life's", skipped if life.multi else skipped[0], every
+    if life.kind == "srnn" and prev is not None and prev.clips == life.clips:
+        oracle = O.SampleRNNOracle(sd64, **life.arch)
+        oracle.reset_hidden = lambda: None
+        if life.multi:
+            oracle.generate(tuple(x[:, :prev.P] for x in prev_history), prev.n, forced=tuple(prev_history))
+            out = oracle.generate(tuple(x[:, :P] for x in history), n, keep_logits=True, forced=tuple(history))[1]
+        else:
+            oracle.generate(prev_history[:, :prev.P], prev.n, forced=prev_history)
+            out = oracle.generate(history[:, :P], n, keep_logits=True, forced=history)[1]
+        yield "(g) the tiers start from the previous life's final hidden states", out, every
+
+
 # ---- option defects: generators of (name, the float64 outputs with the option subtly off) over (case, folded float64 state dict, history, conds) --
 def _layer_key(case, sd, leaf):
     """the key of the middle layer's dilated convolution (gated or not) that ends in `leaf`"""
@@ -718,7 +832,7 @@ def _wn_option_defects(kw):
 
 
 def _wn_stage(batched):
-    return lambda p, k: p.stage_pipelined and p.batch_pipelined == batched
+    return lambda p, k, w=1: p.stage_pipelined and p.batch_pipelined == batched
 
 
 _BP = {"MMK_WN_SPIPE": "1", "MMK_WN_BPIPE": "1"}

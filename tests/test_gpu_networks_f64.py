@@ -138,59 +138,10 @@ import torch
 
 import mimikit_amd as mmk
 from tests import net_refs as R
+from tests.plan_driver import generate as _generate, switch as _switch
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
-
-SWITCHES = ("MMK_WN_XCD_LOCAL", "MMK_WN_PERSISTENT", "MMK_WN_GROUPS", "MMK_WN_SMALL", "MMK_WN_PREFILL", "MMK_WN_CHAIN", "MMK_WN_LPIPE", "MMK_WN_SPIPE",
-            "MMK_WN_BPIPE", "MMK_WN_PIPE", "MMK_WN_SPIPE_PAIR", "MMK_SRNN_FUSED", "MMK_SRNN_FUSED_UP", "MMK_SRNN_RESIDENT", "MMK_SRNN_RESIDENT_WARMUP",
-            "MMK_SRNN_COMPOSED", "MMK_S2S_FUSED", "MMK_S2S_SEQ", "MMK_S2S_COMPOSED", "MMK_GEMM_KSPLIT")
-
-
-def _switch(monkeypatch, case):
-    for k in SWITCHES:
-        monkeypatch.delitem(mmk.native.PLAN_TUNING, k, raising=False)
-    for k, v in case.env.items():
-        monkeypatch.setitem(mmk.native.PLAN_TUNING, k, v)
-
-
-def _generate(case, device, what):
-    """the case's blocks on the device -> (history on the host, the outputs the device hands back: (clips, compared steps, columns))"""
-    net = case.make()[0].to(device)
-    prompt, conds = case.inputs()
-    B, P, n, hop = case.clips, case.P, case.n, case.hop or 1
-    conds_d = tuple(c.to(device) for c in conds)
-    # one tensor per class stream (or the one of frames): the prompt and blanks - a stream no target feeds is given for the whole length
-    data = tuple(torch.cat([p, torch.zeros(B, P + n - p.size(1), *p.shape[2:], dtype=p.dtype)], 1).to(device) for p in R.streams(prompt))
-    if case.kind in ("srnn", "s2s", "s2s_classes"):
-        net.before_generate(tuple(x[:, :P] for x in data), None)
-        if case.kind == "srnn" and "MMK_SRNN_RESIDENT_WARMUP" in case.env:
-            assert case.ran(net._plan, 0), (what, "the warm-up took another path", net._plan.resident_warmups())
-    rows, t = [[] for _ in range(case.targets)], P
-    for k, nb in enumerate(case.parts, 1):
-        if case.kind == "s2s" and conds_d:
-            # several frame inputs: the network adds them up and has no block path (generate_block declines), so step by step as the loop does
-            assert nb == 1 and net.generate_block((*data, *conds_d), t, hop) is None
-            data[0][:, t:t + hop] = net.generate_step(tuple(x[:, t - hop:t] for x in (*data, *conds_d)), t=t)
-        else:
-            assert net.generate_block((*data, *conds_d), t, nb * hop)
-        t += nb * hop
-        plan = net._plan
-        assert case.ran(plan, k), (what, f"block {k}: the plan took another kernel", R.flags(case, plan))
-        waits = plan.persistent if case.kind in ("wavenet", "wavenet_frames") else plan.resident_blocks() if case.kind == "srnn" else plan.resident_launches()
-        if waits:
-            plan.sync_status()                     # (the workgroups of these kernels wait for each other: a timed-out wait is an error here)
-        if case.kind == "s2s_classes":
-            rows[0].append(plan.last_logits(B).cpu())
-        elif case.classes:
-            for target in range(case.targets):
-                rows[target].append(plan.last_logits(B, target).cpu())
-    net.after_generate(data, None)
-    hist = tuple(x.cpu() for x in data)
-    if not case.classes:
-        return hist[0], hist[0][:, P:]
-    dev = [torch.cat(r, 1) if case.kind == "s2s_classes" else torch.stack(r, 1) for r in rows]
-    return (hist, dev) if case.multi else (hist[0], dev[0])
 
 
 def _against_float64(case, device, monkeypatch, what):

@@ -2,7 +2,10 @@
 free-running history, the float64 run is the same function as the fp32 one, both fp32 runs lie inside the envelope, the oracle's own picks
 pass check_picks on every step, and each of the four defects - and every option defect of an option case - leaves the envelope (a network
 of several targets: per target, each with its own envelope).  And the kernels' activation formulas (csrc/mmk_common.h) against float64.
-The 55 option cases add about 30 s to this module on the host, at most 1 s each for either test."""
+The 55 option cases add about 30 s to this module on the host, at most 1 s each for either test.
+The same for lives 2 and 3 of every case (net_refs.lives: the later generations of test_gpu_plan_lives.py): the fp32 oracle inside the
+life's own envelope, the life defects (e), (f) and (g) outside it, and the arithmetic of the lives.  The SampleRNN oracle can be started from
+the tier states a generation left (defect (g)): its reset_hidden is stubbed on the one instance, nothing of it is rewritten."""
 import functools
 
 import pytest
@@ -23,12 +26,28 @@ def _run(index):
     return case, hist, conds, R.envelope(hist, case, conds)
 
 
+@functools.lru_cache(maxsize=None)
+def _life(index, which):
+    """life `which` (1 .. 3) of the case on the fp32 oracle's own free-running history of that life; life 1 is the case itself"""
+    if which == 1:
+        return _run(index)
+    life = R.lives(R.ALL_CASES[index][1])[which - 1]
+    prompt, conds = life.inputs()
+    hist = R.free_run(life, prompt, conds)
+    return life, hist, conds, R.envelope(hist, life, conds)
+
+
 @pytest.mark.parametrize("index", range(len(R.ALL_CASES)), ids=IDS)
 def test_fp32_oracle_lies_inside_its_own_envelope(index):
-    case, hist, conds, envs = _run(index)
+    """the case, and lives 2 and 3 of it (net_refs.lives: the generations test_gpu_plan_lives.py runs on a plan that has generated before)"""
+    for which in (1, 2, 3):
+        _inside_its_own_envelope(IDS[index] + ("" if which == 1 else f" life {which}"), *_life(index, which))
+
+
+def _inside_its_own_envelope(tag, case, hist, conds, envs):
     rows = case.rows()
     for k, env in enumerate(R.per_target(envs)):
-        what = f"{IDS[index]} target {k}" if case.multi else IDS[index]
+        what = f"{tag} target {k}" if case.multi else tag
         R64, E = env.R64[:, rows], env.E[:, rows]
         assert env.R64.dtype == torch.float64 and env.R64.shape[:2] == (case.clips, case.n)
         scale = float(env.R64.abs().max())
@@ -67,6 +86,79 @@ def test_every_defect_leaves_the_envelope(index):
         R.check_near_miss(out, R64, tol_max, f"{IDS[index]} {name}")
         names.append(name)
     assert len(names) >= 4 + len(case.options)
+
+
+@pytest.mark.parametrize("index", range(len(R.ALL_CASES)), ids=IDS)
+def test_every_life_defect_leaves_the_envelope(index):
+    """lives 2 and 3: (e) a prompt of the life before, (f) a ragged group's rows of the life before and, for SampleRNN's life 2, (g) tier
+    states carried over - each against the tol_max of the life's compared rows, the tolerance the device is held to"""
+    for which in (2, 3):
+        life, hist, conds, envs = _life(index, which)
+        prev, prev_hist, _, prev_envs = _life(index, which - 1)
+        rows = life.rows()
+        envs = R.per_target(envs)
+        tol_max = [R.tolerance(env.E[:, rows])[0] for env in envs]
+        full, prev_full = [env.R64 for env in envs], [env.R64 for env in R.per_target(prev_envs)]
+        names = ""
+        for name, out, where in R.life_defects(life, hist, conds, full if life.multi else full[0], prev_hist, prev_full if life.multi else prev_full[0], prev):
+            assert where, (IDS[index], which, name, "no compared row is reached by the prompt")
+            at = [rows[i] for i in where]
+            out, R64 = [o[:, at] for o in R.per_target(out)], [r[:, at] for r in full]
+            print(f"[net_refs] {IDS[index]} life {which} {name}: moves {len(at)} of {len(rows)} compared rows by up to "
+                  f"{[f'{float((o - r).abs().max()):.3e}' for o, r in zip(out, R64)]}, tol_max {[f'{t:.3e}' for t in tol_max]}")
+            R.check_near_miss(out, R64, tol_max, f"{IDS[index]} life {which} {name}")
+            names += name[1]
+        assert names == ("efg" if life.kind == "srnn" and which == 2 else "ef")
+
+
+# the clips of life 3, B -> max(1, B // 2 - 1): ragged against the groups of 2, 4 and 16 the kernels work in, or a single clip
+LIFE_3_CLIPS = {5: 1, 8: 3, 13: 5, 20: 9, 24: 11, 21: 9, 33: 15, 40: 19, 17: 7, 128: 63, 16: 7, 3: 1, 9: 3, 11: 4}
+
+
+def test_life_arithmetic():
+    """what net_refs.lives promises test_gpu_plan_lives.py: lives 1 and 4 are the case bit for bit, life 3's clips, life 2 starts below
+    life 1's end on another ring phase, the warm-up starts, and the resident blocks of the later lives"""
+    seen = set()
+    for _, case in R.ALL_CASES:
+        one, two, three, four = R.lives(case)
+        for life in (one, four):
+            assert (life.clips, life.P, life.parts, life.n, life.rows()) == (case.clips, case.P, case.parts, case.n, case.rows())
+        if case.id in ("chain-cond", "multi-srnn_mean_3x3", "two_inputs", "frames-g4"):
+            for a, b in zip((*R.streams(case.inputs()[0]), *case.inputs()[1]), (*R.streams(four.inputs()[0]), *four.inputs()[1])):
+                assert torch.equal(a, b)
+            assert not torch.equal(R.streams(case.inputs()[0])[0], R.streams(two.inputs()[0])[0][:, :case.P])
+            assert all(torch.equal(a, b) for a, b in zip(R.streams(case.inputs(two)[0]), R.streams(two.inputs()[0])))
+        assert three.clips == LIFE_3_CLIPS[case.clips] and two.clips == case.clips
+        seen.add(case.clips)
+        assert two.parts == three.parts == case.parts[:len(two.parts)] and two.sd is case.sd and three.arch is case.arch
+        if case.kind in ("s2s", "s2s_classes"):
+            assert two.P == three.P == case.hop and two.parts == (1, 1)
+            continue
+        assert two.P == case.P + 5 and two.P + two.n < case.P + case.n          # (life 1's last tags and slots lie ahead of all of life 2)
+        assert three.P == case.shortest_prompt == case.P - 3 - (case.arch["frame_sizes"][0] if case.kind == "srnn" else 0)
+        if case.kind != "srnn":
+            assert two.P - case.shortest_prompt == 8 and sum(two.parts) == 15      # (the warm-up starts at position 8, life 3's at 0)
+            continue
+        fs0 = case.arch["frame_sizes"][0]
+        assert (one.P % fs0, two.P % fs0, three.P % fs0) == (3 % fs0, 8 % fs0, 0)          # (the warm-up's offset: 3, 8 and 0 at frame sizes 16 and 32)
+        assert one.whole_period_warmup and two.whole_period_warmup and not three.whole_period_warmup
+        if case.parts not in (R.RES_PARTS_16, R.RES_PARTS_32):
+            assert sum(two.parts) == 15
+            continue
+        # resident mode (csrc/srnn_plan.hip, run_steps): a head of (fs0 - t % fs0) % fs0 steps with the kernels in turns, then ONE resident launch
+        # if at least a period is left.  Every block of lives 2 and 3 is at least two periods long and leaves the launch more than a period; behind
+        # life 2's head of 8 (24) steps the first block holds two WHOLE periods and more (life 1's, behind a head of 13 (29), holds less than two)
+        assert len(two.parts) == 2
+        for life in (two, three):
+            t = life.P
+            for k, nb in enumerate(life.parts):
+                head = (fs0 - t % fs0) % fs0
+                assert nb >= 2 * fs0 and nb - head > fs0, (case.id, life.index, k, nb, head)
+                if k == 0:
+                    assert head == {2: fs0 - 8, 3: 0}[life.index] and nb - head >= 2 * fs0
+                t += nb
+    assert seen == set(LIFE_3_CLIPS)
+    assert R.spipe_pair_form(24) and not R.spipe_pair_form(11) and not R.spipe_pair_form(22) and not R.spipe_pair_form(130)
 
 
 def test_seq2seq_dropped_reverse_bias_is_seen_now():

@@ -82,6 +82,52 @@ def test_every_applicable_defect_leaves_the_envelope(tag):
     assert ("i" in letters) == bool(case.net_kw.get("with_layer_norm"))
 
 
+@functools.lru_cache(maxsize=None)
+def _life(tag, which):
+    """life `which` (1 .. 3) of the case (transformer_refs.lives) on the fp32 modules' own free-running history of that life"""
+    if which == 1:
+        return _run(tag)
+    life = R.lives(R.BY_TAG[tag])[which - 1]
+    hist = R.free_run(life)
+    return life, hist, R.envelope(hist, life)
+
+
+@pytest.mark.parametrize("tag", TAGS)
+def test_later_lives_lie_inside_the_envelope_and_their_defects_leave_it(tag):
+    """lives 2 and 3 of test_gpu_plan_lives.py, for the references alone: both fp32 runs inside the life's envelope, the fp32 picks pass, and
+    a prompt or a ragged group's rows of the life before leave tol_max"""
+    for which in (2, 3):
+        life, hist, env = _life(tag, which)
+        _, prev_hist, prev_env = _life(tag, which - 1)
+        assert env.R64.shape[:2] == (life.clips, life.n) and hist.shape[1] == life.prompt + life.n
+        tol_max, tol_rms = R.tolerance(env.E)
+        for name, run in (("R32", env.R32), ("R32k", env.R32k)):
+            print(f"[transformer_refs] {tag} life {which} {name}: ratios {R.ratios(run, env.R64, env.E)}")
+            R.check_outputs(run, env.R64, tol_max, tol_rms, f"{tag} life {which} {name}")
+        if life.classes:
+            R.check_picks(hist[:, life.prompt:], env.R64, tol_max, f"{tag} life {which} the fp32 modules' own picks")
+        letters = ""
+        for name, out, steps in R.life_defects(life, hist, env.R64, prev_hist, prev_env.R64):
+            assert steps
+            print(f"[transformer_refs] {tag} life {which} {name}: moves {len(steps)} of {life.n} steps by "
+                  f"{float((out[:, steps] - env.R64[:, steps]).abs().max()) / tol_max:.3g} tol_max")
+            R.check_near_miss(out[:, steps], env.R64[:, steps], tol_max, f"{tag} life {which} {name}")
+            letters += name[1]
+        assert letters == "ef"
+
+
+def test_life_arithmetic():
+    for case in R.CASES:
+        one, two, three, four = R.lives(case)
+        for life in (one, four):
+            assert (life.clips, life.prompt, life.parts, life.tag) == (case.clips, case.prompt, case.parts, case.tag)
+            assert torch.equal(life.inputs(), case.inputs())
+        assert (two.clips, two.prompt, two.parts) == (case.clips, case.rf + 8, case.parts)
+        assert (three.clips, three.prompt, three.parts) == ({130: 64, 4: 1, 3: 1, 2: 1}[case.clips], case.rf, case.parts)
+        assert two.inputs().shape[1] == two.prompt and not torch.equal(two.inputs()[:, :case.prompt], case.inputs())
+        assert two.ends() == case.ends() and R.nets(two.tag) is R.nets(case.tag)
+
+
 def test_a_leaking_mask_moves_nothing_in_a_one_layer_network():
     """the rule of defect (e): the outputs depend on the last row's query only, which sees every key"""
     case, hist, env = _run("one_layer_rf9")

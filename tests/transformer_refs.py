@@ -126,6 +126,42 @@ CASES = [
     Case("default", dict(), dict(kind="mulaw", n_mlp_layers=1, mlp_dim=128), 2, (16, 3), 97, "the network people run: D 256, 8 heads, FF 1024, 8 layers, rf 64"),
 ]
 BY_TAG = {c.tag: c for c in CASES}
+
+
+class Life(Case):
+    """One generation among several that a case's network runs on ONE plan (net_refs.lives, test_gpu_plan_lives.py): the case with its own
+    clips, prompt length, blocks and draw of the prompt; the tag - and with it the networks of nets() - is the case's."""
+
+    @property
+    def prompt(self):
+        return self._prompt
+
+    def inputs(self, seed=None):
+        return Case.inputs(self, self.seed + self.clips + 7919 * self.draw if seed is None else seed)
+
+    def reached(self):
+        """the steps whose window still holds prompt positions"""
+        return list(range(min(self.n, self.rf)))
+
+
+def _life(case, index, clips, prompt, parts, draw):
+    life = Life(*Case._replace(case, clips=clips, parts=tuple(parts)))
+    life.index, life._prompt, life.draw = index, prompt, draw
+    return life
+
+
+def of_clips(life, n):
+    """the life as the envelope of `n` selected clips of its history takes it"""
+    return _life(life, life.index, n, life.prompt, life.parts, life.draw)
+
+
+def lives(case):
+    """the four lives of net_refs.lives: the case; its clips behind a prompt 5 longer with another prompt; max(1, clips // 2 - 1) clips (130 ->
+    64, 4 -> 1, 3 -> 1, 2 -> 1) behind the shortest prompt, rf (generate_block takes it: the first window starts at position 0); the case again.
+    The blocks of lives 2 and 3 are the case's first five, which is all of them here (at most three)"""
+    B, P = case.clips, case.prompt
+    return [_life(case, 1, B, P, case.parts, 0), _life(case, 2, B, P + 5, case.parts[:5], 1),
+            _life(case, 3, max(1, B // 2 - 1), case.rf, case.parts[:5], 2), _life(case, 4, B, P, case.parts, 0)]
 CACHE_HIT_CASES = ("one_layer_rf9", "clips130_rf2")
 SAMPLED_CASE = "clips130_rf2"
 
@@ -426,6 +462,19 @@ def defects(case, history, R64):
         yield "(h) cross-attention keys / values of layers >= 1 from the layer's input", reference64(case, history, defect="kv_from_input")
     if case.net_kw.get("with_layer_norm"):
         yield "(i) the final LayerNorm skipped", reference64(case, history, defect="no_final_norm")
+
+
+def life_defects(life, history, R64, prev_history, prev_R64):
+    """(name, the float64 outputs with that one defect, the steps it is checked on) for defects (e) and (f) of net_refs.life_defects: clip
+    0's prompt is the previous life's, position by position (the steps whose window still holds prompt positions); the last clip's rows are
+    the previous life's rows of the same clip index and the same steps (every step)"""
+    stale = history.clone()
+    stale[0, :life.prompt] = prev_history[0, :life.prompt]
+    assert not torch.equal(stale, history)
+    yield "(e) clip 0's prompt is the previous life's", reference64(life, stale), life.reached()
+    skipped = R64.clone()
+    skipped[-1] = prev_R64[life.clips - 1, :life.n]
+    yield "(f) the last clip's rows are the previous life's", skipped, list(range(life.n))
 
 
 def applicable(case):
