@@ -1,4 +1,5 @@
-"""Labelling the frames of a corpus on the MI355X: the three deterministic estimators of the reference's ``mimikit/extract/clusters.py``.
+"""Labelling the frames of a corpus on the MI355X: the three deterministic estimators of the reference's ``mimikit/extract/clusters.py``
+and ``KMeans``, whose random draws can all be made before the first launch.
 
 ``HCluster`` (clusters.py:157-205) merges every frame with its nearest other frame by cosine distance, takes the connected components of
 that graph as clusters, replaces each cluster by the unweighted mean of ITS ROWS OF THE LEVEL BEFORE (not of the original frames) and
@@ -44,19 +45,58 @@ Differences from the reference:
   * a single core: the reference raises (its 2-nearest-cores query finds one sample); here every frame joins it: one cluster;
   * metric "manhattan" is not on the HIP path, and max(n, k) is limited to ``native.NN_TOPK_MAX`` - ``n_neighbors=None`` asks for sqrt(N)
     neighbours and raises on a corpus of more than (NN_TOPK_MAX + 1)^2 - 1 frames.
-``KMeans``, ``SpectralClustering`` and ``GCluster`` are not carried over: random initialisation, sklearn's solvers or an Adam loop
-leave no reference result to pin.  Device float32 tensors only: a CPU tensor raises, as everywhere in this package.
+``SpectralClustering`` and ``GCluster`` are not carried over: sklearn's eigen-solver with its random start, or an Adam loop, leave no
+reference result to pin.  Device float32 tensors only: a CPU tensor raises, as everywhere in this package.
+
+``KMeans`` (clusters.py:233-262, the clusterizer app's "kmeans") is ``sklearn.cluster.KMeans(n_clusters, n_init, max_iter,
+random_state=random_seed)`` - init "k-means++", algorithm "lloyd", tol 1e-4 - as sklearn 1.7 runs it on dense float32 frames with unit
+weights.  Its random numbers are ``numpy.random.RandomState`` draws whose number does not depend on the data, so all of them are made on
+the host before the first launch, and the rest is deterministic (csrc/kmeans.hip, include/mmk_kmeans.h):
+
+  1. tol = 1e-4 x the mean over the columns of the population variance of x.  The column mean mu is taken in float64
+     (``native.pca_colstats``) and rounded to float32; every kernel works on x' = fl32(x - mu), subtracted while loading - the centred
+     corpus is never written - and ``cluster_centers_`` gets mu added back at the end.
+  2. draws: rs = RandomState(random_seed), one generator for all n_init runs; per run first = rs.choice(N, p=full(N, 1 / N)), then
+     n_clusters - 1 times rs.uniform(size=T) with T = 2 + int(log(n_clusters)).
+  3. seeding: closest[r] = |x'_r - x'_first|^2, pot = sum(closest); for every further centre the candidates are
+     clip(searchsorted(cumsum(closest), u pot, side="left"), N - 1), candidate t gives m_t = min(closest, |x' - x'_cand_t|^2) and
+     pot_t = sum(m_t), the FIRST t with the smallest pot_t wins: closest = m_t, pot = pot_t, the centre is row cand_t
+     (``native.kmeans_pp_step``).  Distances, closest, the pots and the scan are float64 on the device (the difference of two floats is
+     exact there, the squares are added in one fixed order); ``torch.cumsum`` / ``torch.searchsorted`` are plumbing on N numbers; u pot is
+     multiplied on the device: seeding reads nothing back.
+  4. Lloyd (``lloyd``), at most max_iter times: every frame goes to the FIRST centre with the largest <x'_r, c_j> - |c_j|^2 / 2
+     (``native.kmeans_assign``: fp32 MFMA sums in one fixed order); the new centres are the means of their members, summed in float64 in
+     one fixed order and rounded to float32 once (``native.kmeans_label_sums``; the division is torch on K x D numbers).  Empty clusters:
+     the n_e frames farthest from their own old centre - by |x'_r - c_old[label_r]|^2 computed directly, in descending order, ties to
+     the lower index - become the centres of the n_e empty clusters in rising cluster number and leave their old clusters' sums and
+     counts (their labels stay).  For one empty cluster this is sklearn's rule; for two or more sklearn's order comes out of
+     ``argpartition`` and is no contract.  Stop with "strict convergence" when the labels equal the previous iteration's; otherwise stop
+     when sum_j |c_new_j - c_old_j|^2 <= tol, and in that case, and when max_iter runs out, assign once more against the final centres.
+     inertia = sum_r |x'_r - c_label_r|^2, computed directly in float64.  n_iter as sklearn counts it.
+  5. the run kept: the first, then any later run with a strictly smaller inertia whose labelling is not the same clustering up to renaming
+     (sklearn's ``_is_same_clustering``: every label of the one maps to a single label of the other).
+
+Synchronisations: at most two small host reads per Lloyd iteration - one of (the number of changed labels, the number of empty
+clusters), one of the shift against tol, only when labels changed - plus, per run, its inertia and, for a run that could replace the kept
+one, the same-clustering test; an iteration that has empty clusters reads their numbers (``nonzero``) as well.  Nothing of size N x K is
+allocated anywhere.
+
+Differences from sklearn: sklearn centres with numpy's float32 column mean, measures the seeding distances by
+|x|^2 + |y|^2 - 2 <x, y> in float32 and sums the members in float32; where a frame's best and second-best centre, or a draw and a boundary of
+the scan, are closer than those roundings the two may part ways.  ``n_clusters`` is limited to ``native.KMEANS_MAX_K``, D to
+``native.PCA_MAX_D`` (the column statistics); no sample_weight, no other init, no Elkan, no predict / transform.
 """
 import dataclasses as dtc
 import math
 from typing import Optional
 
+import numpy as np
 import torch
 
 from .. import native
 from ..features.functionals import Functional, Identity
 
-__all__ = ["QCluster", "HCluster", "ArgMax"]
+__all__ = ["QCluster", "HCluster", "ArgMax", "KMeans"]
 
 
 def _check_frames(x, what: str) -> torch.Tensor:
@@ -71,7 +111,7 @@ def _check_frames(x, what: str) -> torch.Tensor:
 
 
 def _no_numpy(name: str):
-    raise NotImplementedError(f"{name} runs on device tensors only (csrc/neighbors.hip, csrc/hcluster.hip, csrc/qcluster.hip): pass a float32 tensor on the HIP "
+    raise NotImplementedError(f"{name} runs on device tensors only (csrc/neighbors.hip, csrc/hcluster.hip, csrc/qcluster.hip, csrc/kmeans.hip): pass a float32 tensor on the HIP "
                               "device; this package has no CPU path")
 
 
@@ -224,6 +264,143 @@ class ArgMax(Functional):
 
     def np_func(self, inputs):
         _no_numpy("ArgMax")
+
+    def torch_func(self, inputs):
+        return self.fit(inputs).labels_
+
+    @property
+    def inv(self) -> Functional:
+        return Identity()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- KMeans
+def _column_stats(x: torch.Tensor):
+    """(mu (D,) float32, the mean over the columns of the population variance of x as a float): the column means in float64 rounded once"""
+    mean, scale = native.pca_colstats(x)
+    var = torch.where(x.amax(0) == x.amin(0), torch.zeros_like(scale), scale * scale)      # (pca_colstats gives a constant column scale 1)
+    return mean.float(), float(var.mean())
+
+
+def _lloyd(x, mu, centres, max_iter: int, tol: float):
+    """one run from `centres` (K, D) float32 in the coordinates of x' = fl32(x - mu) -> (labels (N,) int32, inertia () float64 on the device,
+    centres in those coordinates, n_iter)"""
+    n, k = x.shape[0], centres.shape[0]
+    dev = x.device
+    labels = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    changed = torch.zeros((), dtype=torch.int64, device=dev)
+    strict, n_iter = False, 0
+    for i in range(int(max_iter)):
+        changed.zero_()
+        native.kmeans_assign(x, mu, centres, labels, changed)
+        sums, counts = native.kmeans_label_sums(x, mu, labels, k)
+        empty = counts == 0
+        n_changed, n_empty = torch.stack([changed, empty.sum()]).tolist()                   # the iteration's first host read
+        if n_empty:
+            d2 = native.kmeans_label_sums(x, mu, labels, k, centres=centres, row_d2=True)[3]
+            far = torch.sort(d2, descending=True, stable=True)[1][:n_empty]                 # farthest first, equal distances by rising index
+            rows = (x[far] - mu).double()
+            was = labels[far].long()
+            sums.index_add_(0, was, -rows)
+            counts.index_add_(0, was, torch.full_like(was, -1))
+            into = empty.nonzero()[:, 0]                                                    # rising cluster number
+            sums[into] = rows
+            counts[into] = 1
+        new = (sums / counts.clamp(min=1).to(torch.float64)[:, None]).float()
+        old, centres, n_iter = centres, new, i + 1
+        if n_changed == 0:
+            strict = True
+            break
+        if float(((new.double() - old.double()) ** 2).sum()) <= tol:                        # the second, only when labels changed
+            break
+    if not strict:
+        native.kmeans_assign(x, mu, centres, labels)
+    inertia = native.kmeans_label_sums(x, mu, labels, k, centres=centres)[2]
+    return labels, inertia, centres, n_iter
+
+
+def lloyd(x: torch.Tensor, init: torch.Tensor, max_iter: int = 100, tol: Optional[float] = None):
+    """One Lloyd run from the given centres: x (N, D) float32 on the device, init (K, D) float32 in the input's coordinates, tol the
+    absolute bound on the centres' squared shift (None: 1e-4 x the mean column variance, as ``KMeans`` sets it) -> (labels (N,) int64,
+    inertia (float), centres (K, D) float32 in the input's coordinates, n_iter) - step 4 of the module docstring, what ``KMeans.fit`` runs
+    once per seeding"""
+    x = _check_frames(x, "lloyd")
+    init = _check_frames(init, "lloyd")
+    if init.shape[1] != x.shape[1] or init.shape[0] > x.shape[0]:
+        raise ValueError(f"lloyd: x {tuple(x.shape)}, init {tuple(init.shape)}: the same bins, and no more centres than frames")
+    if init.shape[0] > native.KMEANS_MAX_K:
+        raise NotImplementedError(f"lloyd: {init.shape[0]} centres, the limit of the HIP path is {native.KMEANS_MAX_K} (native.KMEANS_MAX_K)")
+    mu, var = _column_stats(x)
+    labels, inertia, centres, n_iter = _lloyd(x, mu, init - mu, max_iter, 1e-4 * var if tol is None else float(tol))
+    return labels.long(), float(inertia), centres + mu, n_iter
+
+
+def _same_clustering(a: torch.Tensor, b: torch.Tensor, k: int) -> bool:
+    """sklearn's _is_same_clustering: every label of `a` is paired with one single label of `b`"""
+    a, b = a.long(), b.long()
+    return int(torch.unique(a * k + b).numel()) == int(torch.unique(a).numel())
+
+
+@dtc.dataclass
+class KMeans(Functional):
+    n_clusters: int = 16
+    n_init: int = 2
+    max_iter: int = 100
+    random_seed: int = 42
+
+    def __post_init__(self):
+        self.labels_: Optional[torch.Tensor] = None
+        self.cluster_centers_: Optional[torch.Tensor] = None
+        self.inertia_: Optional[float] = None
+        self.n_iter_: Optional[int] = None
+        self.seed_rows_: Optional[torch.Tensor] = None
+
+    def fit(self, x: torch.Tensor) -> "KMeans":
+        """x (N >= n_clusters, D) float32 on the device -> ``labels_`` (N,) int64 and ``cluster_centers_`` (K, D) float32 on the device,
+        ``inertia_`` (float), ``n_iter_`` (int) - as sklearn's KMeans sets them - and ``seed_rows_`` (n_init, K) int64, the frames every
+        seeding chose.  Synchronises as the module docstring says"""
+        self.__post_init__()
+        x = _check_frames(x, "KMeans")
+        n, dev = x.shape[0], x.device
+        k, n_init, max_iter = int(self.n_clusters), int(self.n_init), int(self.max_iter)
+        if k < 1 or n_init < 1 or max_iter < 1:
+            raise ValueError(f"KMeans: n_clusters = {k}, n_init = {n_init}, max_iter = {max_iter} (all at least 1)")
+        if k > native.KMEANS_MAX_K:
+            raise NotImplementedError(f"KMeans: n_clusters = {k}, the limit of the HIP path is {native.KMEANS_MAX_K} (native.KMEANS_MAX_K)")
+        if n < k:
+            raise ValueError(f"KMeans: n_clusters = {k} needs at least {k} frames, got N = {n}")
+        # every draw, on the host, before the first launch
+        rs = np.random.RandomState(int(self.random_seed))
+        trials = 2 + int(math.log(k))
+        firsts, uniforms = np.zeros((n_init,), dtype=np.int64), np.zeros((n_init, max(k - 1, 1), trials), dtype=np.float64)
+        for run in range(n_init):
+            firsts[run] = rs.choice(n, p=np.full(n, 1 / n))
+            for c in range(k - 1):
+                uniforms[run, c] = rs.uniform(size=trials)
+        firsts, uniforms = torch.from_numpy(firsts).to(dev), torch.from_numpy(uniforms).to(dev)
+        mu, var = _column_stats(x)
+        tol = 1e-4 * var
+        seed_rows = torch.empty((n_init, k), dtype=torch.int64, device=dev)
+        closest = torch.empty((n,), dtype=torch.float64, device=dev)
+        pot = torch.empty((), dtype=torch.float64, device=dev)
+        work = torch.empty((native.lib().mmk_kmeans_pp_step_workspace_bytes() // 8,), dtype=torch.float64, device=dev)
+        best = None
+        for run in range(n_init):
+            closest.fill_(float("inf"))
+            native.kmeans_pp_step(x, mu, firsts[run:run + 1], closest, pot, seed_rows[run, 0], work)
+            for c in range(1, k):
+                cand = torch.searchsorted(torch.cumsum(closest, 0), uniforms[run, c - 1] * pot).clamp_(max=n - 1)
+                native.kmeans_pp_step(x, mu, cand, closest, pot, seed_rows[run, c], work)
+            labels, inertia, centres, n_iter = _lloyd(x, mu, x[seed_rows[run]] - mu, max_iter, tol)
+            inertia = float(inertia)
+            if best is None or (inertia < best[1] and not _same_clustering(labels, best[0], k)):
+                best = (labels, inertia, centres, n_iter)
+        self.labels_, self.inertia_, self.n_iter_ = best[0].long(), best[1], best[3]
+        self.cluster_centers_ = best[2] + mu
+        self.seed_rows_ = seed_rows
+        return self
+
+    def np_func(self, inputs):
+        _no_numpy("KMeans")
 
     def torch_func(self, inputs):
         return self.fit(inputs).labels_

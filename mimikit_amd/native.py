@@ -269,6 +269,17 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
+# include/mmk_kmeans.h: the k-means entry points, a header and a table of their own beside include/mmk.h (the ABI version does not change)
+_KMEANS_SIGNATURES = {
+    "mmk_kmeans_assign_f32": (i32, [vp, i64, vp, i64, i32, vp, i64, vp, i32, vp, vp, vp, vp]),
+    "mmk_kmeans_label_sums_workspace_bytes": (C.c_size_t, [i64, i32, i32]),
+    "mmk_kmeans_label_sums_f64": (i32, [vp, i64, vp, i64, i32, vp, i32, vp, vp, vp, i64, vp, vp, vp, C.c_size_t, vp]),
+    "mmk_kmeans_pp_step_workspace_bytes": (C.c_size_t, []),
+    "mmk_kmeans_pp_step_f64": (i32, [vp, i64, vp, i64, i32, vp, i32, vp, vp, vp, vp, C.c_size_t, vp]),
+}
+
+KMEANS_SYMBOLS = tuple(_KMEANS_SIGNATURES)
+
 _lib = None
 
 
@@ -283,7 +294,7 @@ def load_library(path: Optional[str] = None):
             f"{path} is missing: build it with `python -m mimikit_amd.build` (hipcc, --offload-arch=gfx950). "
             "There is no CPU fallback for the generate path.")
     lib = C.CDLL(path)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in {**_SIGNATURES, **_KMEANS_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -694,6 +705,107 @@ def edge_components(src: torch.Tensor, dst: torch.Tensor, n: int):
     check(lib().mmk_edge_components_i64(ptr(src) if n_edges else None, ptr(dst) if n_edges else None, n_edges, n, ptr(labels), ptr(count),
                                         ptr(work), n_work, stream_ptr(src.device)), "mmk_edge_components_i64")
     return labels, count
+
+
+# include/mmk_kmeans.h: MMK_KMEANS_* - the centres of one assignment (the widest centre tile of csrc/kmeans.hip), the candidates of one
+# seeding step, the slabs of the float64 sums
+KMEANS_MAX_K = 256
+KMEANS_PP_MAX_TRIALS = 8
+KMEANS_MAX_SLABS = 1024
+
+
+def _kmeans_offset(offset: Optional[torch.Tensor], d: int, what: str) -> Optional[torch.Tensor]:
+    if offset is None:
+        return None
+    if not isinstance(offset, torch.Tensor) or offset.dtype != torch.float32 or tuple(offset.shape) != (d,):
+        raise TypeError(f"{what}: offset must be a float32 tensor of shape ({d},)")
+    require_device(offset)
+    return offset.contiguous()
+
+
+def kmeans_assign(x: torch.Tensor, offset: Optional[torch.Tensor], centres: torch.Tensor, labels: torch.Tensor, changed: Optional[torch.Tensor] = None,
+                  key: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x (N, D) fp32, offset (D,) fp32 or None, centres (K <= KMEANS_MAX_K, D) fp32 in the coordinates of x' = fl32(x - offset), labels (N,)
+    int32 IN/OUT -> labels: the first centre with the largest <x'_r, c_j> - |c_j|^2 / 2, the nearest one.  ``changed`` (() int64) is
+    incremented for every row whose label differs from the one found in ``labels``; ``key`` (N,) fp32 receives the largest key.  One
+    launch behind mmk_half_neg_sqnorm_f32 of the centres; nothing of size N x K is allocated"""
+    x = _nnn_frames(x, 2, "kmeans_assign")
+    centres = _nnn_frames(centres, 2, "kmeans_assign")
+    n, d = x.shape
+    k = centres.shape[0]
+    if min(n, d, k) < 1 or centres.shape[1] != d:
+        raise ValueError(f"kmeans_assign: x {tuple(x.shape)}, centres {tuple(centres.shape)}")
+    if k > KMEANS_MAX_K:
+        raise NotImplementedError(f"kmeans_assign: {k} centres, the limit of the HIP path is {KMEANS_MAX_K} (native.KMEANS_MAX_K)")
+    offset = _kmeans_offset(offset, d, "kmeans_assign")
+    for name, t, dtype, shape in (("labels", labels, torch.int32, (n,)), ("changed", changed, torch.int64, ()), ("key", key, torch.float32, (n,))):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise TypeError(f"kmeans_assign: {name} must be a contiguous {dtype} tensor of shape {shape}")
+    require_device(labels, changed, key)
+    dev = x.device
+    shift = torch.empty((k,), dtype=torch.float32, device=dev)
+    check(lib().mmk_half_neg_sqnorm_f32(ptr(centres), centres.stride(0), k, d, ptr(shift), stream_ptr(dev)), "mmk_half_neg_sqnorm_f32")
+    check(lib().mmk_kmeans_assign_f32(ptr(x), x.stride(0), ptr(offset), n, d, ptr(centres), centres.stride(0), ptr(shift), k, ptr(labels), ptr(key),
+                                      ptr(changed), stream_ptr(dev)), "mmk_kmeans_assign_f32")
+    return labels
+
+
+def kmeans_label_sums(x: torch.Tensor, offset: Optional[torch.Tensor], labels: torch.Tensor, k: int, centres: Optional[torch.Tensor] = None,
+                      row_d2: bool = False):
+    """x (N, D) fp32, labels (N,) int32 in [0, k) -> (sums (k, D) fp64, counts (k,) int64): the float64 sum of x' = fl32(x - offset) over every
+    label's rows, in one fixed order, the rows read once and in order.  With ``centres`` (k, D) fp32 also (inertia () fp64, row_d2 (N,) fp64 or
+    None): |x'_r - c_label_r|^2 computed directly in float64, and their sum"""
+    x = _nnn_frames(x, 2, "kmeans_label_sums")
+    n, d = x.shape
+    k = int(k)
+    if min(n, d, k) < 1:
+        raise ValueError(f"kmeans_label_sums: x {tuple(x.shape)}, k = {k}")
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,) or not labels.is_contiguous():
+        raise TypeError(f"kmeans_label_sums: labels must be a contiguous int32 tensor of shape ({n},)")
+    require_device(labels)
+    offset = _kmeans_offset(offset, d, "kmeans_label_sums")
+    dev = x.device
+    sums = torch.empty((k, d), dtype=torch.float64, device=dev)
+    counts = torch.empty((k,), dtype=torch.int64, device=dev)
+    inertia = d2 = None
+    c_stride = 0
+    if centres is not None:
+        centres = _nnn_frames(centres, 2, "kmeans_label_sums")
+        if tuple(centres.shape) != (k, d):
+            raise ValueError(f"kmeans_label_sums: centres {tuple(centres.shape)}, expected {(k, d)}")
+        c_stride = centres.stride(0)
+        inertia = torch.empty((), dtype=torch.float64, device=dev)
+        d2 = torch.empty((n,), dtype=torch.float64, device=dev) if row_d2 else None
+    n_work = lib().mmk_kmeans_label_sums_workspace_bytes(n, d, k)
+    work = torch.empty((n_work // 8,), dtype=torch.float64, device=dev)
+    check(lib().mmk_kmeans_label_sums_f64(ptr(x), x.stride(0), ptr(offset), n, d, ptr(labels), k, ptr(sums), ptr(counts), ptr(centres), c_stride,
+                                          ptr(d2), ptr(inertia), ptr(work), n_work, stream_ptr(dev)), "mmk_kmeans_label_sums_f64")
+    return (sums, counts) if centres is None else (sums, counts, inertia, d2)
+
+
+def kmeans_pp_step(x: torch.Tensor, offset: Optional[torch.Tensor], cand: torch.Tensor, closest: torch.Tensor, pot: torch.Tensor,
+                   chosen: torch.Tensor, work: Optional[torch.Tensor] = None):
+    """one step of k-means++ seeding: cand (t <= KMEANS_PP_MAX_TRIALS,) int64 candidate rows, closest (N,) fp64 IN/OUT, pot () fp64 and chosen
+    () int64 OUT - the first candidate whose min(closest, |x' - x'_cand|^2) has the smallest sum.  Nothing is read back"""
+    x = _nnn_frames(x, 2, "kmeans_pp_step")
+    n, d = x.shape
+    offset = _kmeans_offset(offset, d, "kmeans_pp_step")
+    for name, t, dtype, shape in (("cand", cand, torch.int64, None), ("closest", closest, torch.float64, (n,)), ("pot", pot, torch.float64, ()),
+                                  ("chosen", chosen, torch.int64, ())):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or (shape is not None and tuple(t.shape) != shape) or t.dim() > 1 or not t.is_contiguous():
+            raise TypeError(f"kmeans_pp_step: {name} must be a contiguous {dtype} tensor" + (f" of shape {shape}" if shape is not None else ""))
+    require_device(cand, closest, pot, chosen)
+    t = cand.shape[0]
+    if t < 1:
+        raise ValueError("kmeans_pp_step: no candidate")
+    if t > KMEANS_PP_MAX_TRIALS:
+        raise NotImplementedError(f"kmeans_pp_step: {t} candidates, the limit is {KMEANS_PP_MAX_TRIALS} (native.KMEANS_PP_MAX_TRIALS)")
+    n_work = lib().mmk_kmeans_pp_step_workspace_bytes()
+    if work is None:
+        work = torch.empty((n_work // 8,), dtype=torch.float64, device=x.device)
+    check(lib().mmk_kmeans_pp_step_f64(ptr(x), x.stride(0), ptr(offset), n, d, ptr(cand), t, ptr(closest), ptr(pot), ptr(chosen), ptr(work),
+                                       work.numel() * 8, stream_ptr(x.device)), "mmk_kmeans_pp_step_f64")
+    return chosen
 
 
 # include/mmk.h: MMK_PCA_* - the widest frames and the most components of the PCA kernels (csrc/pca.hip), the stop rule of the eigen step
