@@ -5,17 +5,13 @@
 //   kmeans_assign_kernel<KT>  key[r, j] = <x'_r, c_j> + shift[j] for k <= KT = 32, 64, 128, 256 centres.  The opposite shape of
 //                         nn_search.h: there many corpus frames are walked in 128-wide tiles per span with a merge launch behind, here
 //                         the "corpus" is a handful of centres that fit ONE tile.  A workgroup of four waves owns 128 rows, a wave 32 of
-//                         them against all KT centres: KT / 32 products of v_mfma_f32_32x32x2_f32 with A = centres and B = rows, so that D
-//                         has the row on the lane (l & 31) and 16 centres in the registers (centre (q & 3) + 8 (q >> 2) + 4 (l >> 5) of the
-//                         product's 32) - a row's candidates are met inside the lane in rising centre order, and "strictly greater" keeps
-//                         the first.  The two half-waves hold the same rows against other centres and are joined by one shuffle
-//                         (greater key, then lower index).  Rows and centres go through LDS in chunks of 32 bins exactly as in
-//                         nn_search.h (dword loads with consecutive lanes on consecutive bins: coalesced whatever the stride and the
-//                         alignment; unconditional loads at clamped addresses, the mask picks zero afterwards; the next chunk's loads in
-//                         flight while this chunk's products run; pitch 36; one 16-byte LDS read per operand and group of 8 bins) - the
-//                         same permutation of the bins for every row and centre: ONE order of the sum wherever they sit.  kNarrow, for
-//                         d <= 16: a load covers 16 bins, not 32 (no lane loads a clamped duplicate), and the two groups of 8 bins that
-//                         hold data are multiplied, not four; what is left out are products with zero.  The centres
+//                         them against all KT centres: KT / 32 products with A = centres and B = rows, the row on the lane and 16 centres
+//                         in the registers - a row's candidates are met inside the lane in rising centre order, and "strictly greater"
+//                         keeps the first.  The two half-waves hold the same rows against other centres and are joined by one shuffle
+//                         (greater key, then lower index).  Rows and centres are staged and multiplied by the pieces of frame_walk.h:
+//                         ONE order of the sum wherever they sit, and the search's order.  kNarrow, for d <= 16: a load covers 16 bins,
+//                         not 32 (no lane loads a clamped duplicate), and the two groups of 8 bins that hold data are multiplied, not
+//                         four; what is left out are products with zero.  The centres
 //                         are re-staged per chunk by every workgroup (K D floats from L2 against 128 D floats of rows from HBM: 1/8 more
 //                         LDS traffic at K = 16) rather than kept resident, which would cap K D at the LDS and give one workgroup per CU.
 //                         (A workgroup that walks several row blocks with the next block's loads in flight was tried and was no faster.)
@@ -50,7 +46,7 @@ constexpr int kKmSumsLds = 60000;         // bytes of LDS one wave of the sums k
 // the wave's 32 rows against all centres: the lane's candidates in rising centre order, the other half-wave's best by one shuffle, the label
 // compared and overwritten by the lane that owns the row
 template <int KT>
-__device__ __forceinline__ void assign_epilogue(nn_f32x16 (&acc)[KT / 32], const float* shs, int32_t K, int64_t rbase, int64_t n, int wave, int lane,
+__device__ __forceinline__ void assign_epilogue(fw_f32x16 (&acc)[KT / 32], const float* shs, int32_t K, int64_t rbase, int64_t n, int wave, int lane,
                                                 int32_t* __restrict__ labels, float* __restrict__ key, unsigned long long* __restrict__ changed) {
   constexpr int NP = KT / 32;
   const int fr = lane & 31, fh = lane >> 5;
@@ -60,7 +56,7 @@ __device__ __forceinline__ void assign_epilogue(nn_f32x16 (&acc)[KT / 32], const
   for (int p = 0; p < NP; ++p)
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      const int j = p * 32 + (q & 3) + 8 * (q >> 2) + 4 * fh;
+      const int j = fw_acc_row(p * 32, q, fh);
       const float c = __fadd_rn(acc[p][q], shs[j]);
       if (j < K && c > best) {
         best = c;
@@ -94,15 +90,15 @@ __global__ __launch_bounds__(256, KT <= 128 ? 2 : 1) void kmeans_assign_kernel(c
   constexpr int LC = kNarrow ? 16 : 32;             // bins a load covers: lanes on consecutive bins
   constexpr int RS = 256 / LC;                      // rows between a thread's loads
   constexpr int CL = KT / RS, XL = kKmRows / RS;    // centre and row dwords a thread loads per chunk
-  __shared__ __attribute__((aligned(16))) float cs[KT * kNnPitch];
-  __shared__ __attribute__((aligned(16))) float xs[kKmRows * kNnPitch];
+  __shared__ __attribute__((aligned(16))) float cs[KT * kFwPitch];
+  __shared__ __attribute__((aligned(16))) float xs[kKmRows * kFwPitch];
   __shared__ float shs[KT];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int col = tid & (LC - 1), row0 = tid / LC;  // loads: bin `col` of rows row0, row0 + RS, ...
   const int fr = lane & 31, fh = lane >> 5;         // MFMA fragments: row / centre fr, bin half fh
 
   if (tid < KT) shs[tid] = tid < K ? shift[tid] : 0.f;
-  nn_f32x16 acc[NP];
+  fw_f32x16 acc[NP];
 #pragma unroll
   for (int p = 0; p < NP; ++p)
 #pragma unroll
@@ -111,47 +107,33 @@ __global__ __launch_bounds__(256, KT <= 128 ? 2 : 1) void kmeans_assign_kernel(c
   const int64_t rbase = (int64_t)blockIdx.x * kKmRows;
   float rg[CL + XL];
   auto gload = [&](int k0) {
-    const int k = k0 + col;
-    const int kc = k < D ? k : D - 1;
-    const float mu = offset ? offset[kc] : 0.f;
-#pragma unroll
-    for (int i = 0; i < CL; ++i) {
-      const int j = i * RS + row0;
-      rg[i] = centres[(int64_t)(j < K ? j : K - 1) * c_row_stride + kc];
-    }
-#pragma unroll
-    for (int i = 0; i < XL; ++i) {
-      const int64_t r = rbase + i * RS + row0;
-      rg[CL + i] = __fsub_rn(x[(r < n ? r : n - 1) * x_row_stride + kc], mu);
-    }
+    const float mu = offset ? offset[fw_bin(k0 + col, D)] : 0.f;
+    fw_load<CL, RS, 0>(rg, centres, c_row_stride, 0, K, row0, col, k0, D);
+    fw_load<XL, RS, CL>(rg, x, x_row_stride, rbase, n, row0, col, k0, D, [mu](float v) { return __fsub_rn(v, mu); });
   };
   gload(0);
-  for (int k0 = 0; k0 < D; k0 += kNnKC) {
+  for (int k0 = 0; k0 < D; k0 += kFwKC) {
     const bool kin = k0 + col < D;
 #pragma unroll
-    for (int i = 0; i < CL; ++i) cs[(i * RS + row0) * kNnPitch + col] = (kin && i * RS + row0 < K) ? rg[i] : 0.f;
+    for (int i = 0; i < CL; ++i) cs[(i * RS + row0) * kFwPitch + col] = (kin && i * RS + row0 < K) ? rg[i] : 0.f;
 #pragma unroll
-    for (int i = 0; i < XL; ++i) xs[(i * RS + row0) * kNnPitch + col] = (kin && rbase + i * RS + row0 < n) ? rg[CL + i] : 0.f;
+    for (int i = 0; i < XL; ++i) xs[(i * RS + row0) * kFwPitch + col] = (kin && rbase + i * RS + row0 < n) ? rg[CL + i] : 0.f;
     __syncthreads();
-    if (k0 + kNnKC < D) gload(k0 + kNnKC);
+    if (k0 + kFwKC < D) gload(k0 + kFwKC);
 #pragma unroll
     for (int g = 0; g < LC; g += 8) {
-      const nn_f32x4 bv = *reinterpret_cast<const nn_f32x4*>(&xs[(wave * 32 + fr) * kNnPitch + g + 4 * fh]);
+      const fw_f32x4 bv = fw_frag(xs, wave * 32 + fr, g, fh);
       if constexpr (KT <= 128) {                    // independent products interleaved
-        nn_f32x4 av[NP];
+        fw_f32x4 av[NP];
 #pragma unroll
-        for (int p = 0; p < NP; ++p) av[p] = *reinterpret_cast<const nn_f32x4*>(&cs[(p * 32 + fr) * kNnPitch + g + 4 * fh]);
+        for (int p = 0; p < NP; ++p) av[p] = fw_frag(cs, p * 32 + fr, g, fh);
 #pragma unroll
         for (int e = 0; e < 4; ++e)
 #pragma unroll
-          for (int p = 0; p < NP; ++p) acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[p][e], bv[e], acc[p], 0, 0, 0);
+          for (int p = 0; p < NP; ++p) fw_mfma(acc[p], av[p], bv, e);
       } else {                                      // product by product: four centre registers live, not 4 NP; the sum's order is the same
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
-          const nn_f32x4 av = *reinterpret_cast<const nn_f32x4*>(&cs[(p * 32 + fr) * kNnPitch + g + 4 * fh]);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], bv[e], acc[p], 0, 0, 0);
-        }
+        for (int p = 0; p < NP; ++p) fw_mma(acc[p], fw_frag(cs, p * 32 + fr, g, fh), bv);
       }
     }
     __syncthreads();

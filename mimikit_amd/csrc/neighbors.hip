@@ -1,7 +1,7 @@
 // Scoring generated clips against the training corpus (mimikit/extract/from_neighbors.py:13-19, :44-55 and demos/checkpoint_k_bests.py:36-46):
 // every generated frame's nearest corpus frame by angular distance, and the cumulative entropy of the series of those neighbours.
 //
-//   mmk_nn_cosine_f32     nn_cosine_kernel, the tile walk of nn_search.h with a list of one and the cosine key, kept as its own kernel (see
+//   mmk_nn_cosine_f32     nn_cosine_kernel, the tiles of nn_search.h with a list of one and the cosine key, kept as its own kernel (see
 //                         there): the row arg-max of c[r, j] = clamp(<x_r, y_j> rx[r] ry[j], -1, 1), greater value, then lower index;
 //                         nn_merge_kernel<1> of nn_search.h joins the spans and writes index (int64) and cos_best.
 //   mmk_nn_cosine_self_f32   nn_search_kernel<1, true, NnCosineKey> of nn_search.h, the corpus = the queries and frame r left out of row r:
@@ -19,16 +19,17 @@
 
 namespace mmk {
 
-// The plain arg-max keeps the kernel it had before nn_search.h.  It is the walk of nn_search_kernel<1, false, NnCosineKey>, statement for
-// statement, and gives its bits (scripts/nn_search_parity.py); but as that instance it measured 0.2 % slower on scripts/neighbors_bench.py
-// than this kernel, outside the range of three runs, with the same instructions in the loop over the bins and in the tile's epilogue
-// (DESIGN.md section 5.6.3 has the figures).  Until the cause is known this entry point does not move; a change to the walk is made in both.
+// The plain arg-max keeps the kernel it had before nn_search.h.  It walks the tiles of nn_search_kernel<1, false, NnCosineKey> with the
+// same pieces of frame_walk.h and gives its bits (scripts/walk_parity.py); but as that instance it measured 0.2 % slower on
+// scripts/neighbors_bench.py than this kernel, outside the range of three runs, with the same instructions in the loop over the bins and in
+// the tile's epilogue (DESIGN.md section 5.6.3 has the figures).  Until the cause is known this entry point does not move.  Its own: the
+// arg-max in two registers per row and the join arrays.
 __global__ __launch_bounds__(kNnThreads, 2) void nn_cosine_kernel(const float* __restrict__ x, int64_t x_row_stride, const float* __restrict__ rx,
                                                                int64_t rows, const float* __restrict__ y, int64_t y_row_stride,
                                                                const float* __restrict__ ry, int64_t M, int32_t K, int32_t n_blocks,
                                                                int32_t n_spans, float* __restrict__ ws_val, int32_t* __restrict__ ws_idx) {
-  __shared__ __attribute__((aligned(16))) float ys[kNnCols * kNnPitch];
-  __shared__ __attribute__((aligned(16))) float xs[kNnRows * kNnPitch];
+  __shared__ __attribute__((aligned(16))) float ys[kNnCols * kFwPitch];
+  __shared__ __attribute__((aligned(16))) float xs[kNnRows * kFwPitch];
   __shared__ float rys[2][kNnCols];
   __shared__ float red_val[2][kNnRows];
   __shared__ int red_idx[2][kNnRows];
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(kNnThreads, 2) void nn_cosine_kernel(const float* _
       const int64_t j = jt + tid;
       rys[parity][tid] = j < jend ? ry[j] : 0.f;
     }
-    nn_f32x16 acc[2][2];
+    fw_f32x16 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -73,43 +74,33 @@ __global__ __launch_bounds__(kNnThreads, 2) void nn_cosine_kernel(const float* _
 
     float rg[kNnLoads];
     auto gload = [&](int k0) {
-      const int k = k0 + col;
-      const int kc = k < K ? k : K - 1;
-#pragma unroll
-      for (int i = 0; i < kNnCols / 8; ++i) {
-        const int64_t j = jt + i * 8 + row0;
-        rg[i] = y[(j < M ? j : M - 1) * y_row_stride + kc];
-      }
-#pragma unroll
-      for (int i = 0; i < kNnRows / 8; ++i) {
-        const int64_t r = rbase + i * 8 + row0;
-        rg[kNnCols / 8 + i] = x[(r < rows ? r : rows - 1) * x_row_stride + kc];
-      }
+      fw_load<kNnCols / 8, 8, 0>(rg, y, y_row_stride, jt, M, row0, col, k0, K);
+      fw_load<kNnRows / 8, 8, kNnCols / 8>(rg, x, x_row_stride, rbase, rows, row0, col, k0, K);
     };
     gload(0);
-    for (int k0 = 0; k0 < K; k0 += kNnKC) {
+    for (int k0 = 0; k0 < K; k0 += kFwKC) {
       const bool kin = k0 + col < K;
 #pragma unroll
-      for (int i = 0; i < kNnCols / 8; ++i) ys[(i * 8 + row0) * kNnPitch + col] = (kin && jt + i * 8 + row0 < jend) ? rg[i] : 0.f;
+      for (int i = 0; i < kNnCols / 8; ++i) ys[(i * 8 + row0) * kFwPitch + col] = (kin && jt + i * 8 + row0 < jend) ? rg[i] : 0.f;
 #pragma unroll
       for (int i = 0; i < kNnRows / 8; ++i)
-        xs[(i * 8 + row0) * kNnPitch + col] = (kin && rbase + i * 8 + row0 < rows) ? rg[kNnCols / 8 + i] : 0.f;
+        xs[(i * 8 + row0) * kFwPitch + col] = (kin && rbase + i * 8 + row0 < rows) ? rg[kNnCols / 8 + i] : 0.f;
       __syncthreads();
-      if (k0 + kNnKC < K) gload(k0 + kNnKC);
+      if (k0 + kFwKC < K) gload(k0 + kFwKC);
 #pragma unroll
-      for (int g = 0; g < kNnKC; g += 8) {
-        nn_f32x4 av[2], bv[2];
+      for (int g = 0; g < kFwKC; g += 8) {
+        fw_f32x4 av[2], bv[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-          av[t] = *reinterpret_cast<const nn_f32x4*>(&ys[(wm * 64 + t * 32 + fr) * kNnPitch + g + 4 * fh]);
-          bv[t] = *reinterpret_cast<const nn_f32x4*>(&xs[(wn * 64 + t * 32 + fr) * kNnPitch + g + 4 * fh]);
+          av[t] = fw_frag(ys, wm * 64 + t * 32 + fr, g, fh);
+          bv[t] = fw_frag(xs, wn * 64 + t * 32 + fr, g, fh);
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e)
 #pragma unroll
           for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
-            for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[tm][e], bv[tn][e], acc[tm][tn], 0, 0, 0);
+            for (int tn = 0; tn < 2; ++tn) fw_mfma(acc[tm][tn], av[tm], bv[tn], e);
       }
       __syncthreads();
     }
@@ -119,7 +110,7 @@ __global__ __launch_bounds__(kNnThreads, 2) void nn_cosine_kernel(const float* _
     for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
-        const int jl = wm * 64 + tm * 32 + (q & 3) + 8 * (q >> 2) + 4 * fh;
+        const int jl = fw_acc_row(wm * 64 + tm * 32, q, fh);
         const int64_t j = jt + jl;
         const float ryj = rys[parity][jl];
 #pragma unroll

@@ -1,23 +1,15 @@
 // The best corpus frames of every query frame: a GEMM whose epilogue keeps the TC best keys of every row and which never writes the matrix.
-// ONE tile walk for the self-excluding nearest-frame search (neighbors.hip: mmk_nn_cosine_self_f32 - TC = 1, the cosine key) and the
-// k-best search (qcluster.hip: mmk_nn_topk_f32 - TC = 1, 4, 8, 16, the affine key).  The plain nearest-frame search (mmk_nn_cosine_f32)
-// keeps nn_cosine_kernel of neighbors.hip, this walk written out for TC = 1 and the cosine key, for the reason given there; it uses the
-// constants, nn_better and nn_merge_kernel<1> of this header.
+// ONE kernel for the self-excluding nearest-frame search (neighbors.hip: mmk_nn_cosine_self_f32 - TC = 1, the cosine key) and the k-best
+// search (qcluster.hip: mmk_nn_topk_f32 - TC = 1, 4, 8, 16, the affine key).  The plain nearest-frame search (mmk_nn_cosine_f32) keeps
+// nn_cosine_kernel of neighbors.hip, a kernel of its own for the reason given there; it uses the constants, nn_better and
+// nn_merge_kernel<1> of this header.  How the bins are walked - staging, fragments, products, the accumulator's rows - is frame_walk.h.
 //
 //   nn_search_kernel<TC, kSelf, Key>   key[r, j] = Key::key(<x_r, y_j>, ...) for `rows` query frames against m corpus frames over k bins.
 //                         A workgroup of four waves owns kNnRows = 128 query rows and one SPAN of MMK_NN_SPAN corpus frames, which it
-//                         walks in tiles of kNnCols = 128 frames; a wave owns a 64 x 64 corner of the tile as 2 x 2 products of
-//                         v_mfma_f32_32x32x2_f32 with A = corpus frames and B = query rows, so that D has the query row on the lane
-//                         (l & 31) and 16 corpus frames in the registers (frame (q & 3) + 8 (q >> 2) + 4 (l >> 5) of the product's 32): a
-//                         tile's candidates are met inside the lane, in rising frame order.  Both operands go through LDS in chunks of
-//                         kNnKC = 32 bins: rows are loaded dword by dword with consecutive lanes on consecutive bins (coalesced whatever
-//                         the row stride and the base alignment; every load is unconditional at a clamped, valid address and the mask
-//                         picks zero afterwards - nothing is padded by the caller), the next chunk's loads are in flight while this
-//                         chunk's products run.  Lane (r = l & 31, h = l >> 5) reads bins 8 g + 4 h .. + 3 of its row as one 16-byte LDS
-//                         read and feeds MFMA e of group g with bin 8 g + 4 h + e - the same permutation of the bins on both operands and
-//                         for every row and column, so ONE order of the sum over k wherever a frame sits in a tile: two identical corpus
-//                         frames have bit-identical keys, under either key and any TC.  The row pitch of 36 floats keeps the 16-lane
-//                         groups of that read on 64 different banks.
+//                         walks in tiles of kNnCols = 128 frames; a wave owns a 64 x 64 corner of the tile as 2 x 2 products with
+//                         A = corpus frames and B = query rows: the query row on the lane and 16 corpus frames in the registers, so a
+//                         tile's candidates are met inside the lane, in rising frame order.  Two identical corpus frames have
+//                         bit-identical keys, under either key and any TC (frame_walk.h: one order of the sum).
 //                         A lane keeps, for each of its two query rows, a list of TC (key, index) pairs in registers, sorted by falling key,
 //                         across the whole span.  It meets its frames in rising index order, so "strictly greater than the list's last
 //                         key" is the whole guard: one compare per candidate once the list has filled with good keys, and an insertion (the
@@ -39,26 +31,21 @@
 // No atomics, no workgroup waits for another; every sum has one order, so two calls give the same bits.  NaN in the inputs is not handled
 // (> drops it silently; a key of -inf never enters a list).
 #pragma once
-#include "mmk_common.h"
+#include "frame_walk.h"
 
 namespace mmk {
-
-typedef float nn_f32x4 __attribute__((ext_vector_type(4)));
-typedef float nn_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kNnSpan = MMK_NN_SPAN;
 constexpr int kNnThreads = 256;
 constexpr int kNnRows = 128;      // query rows of a workgroup, 64 per wave pair
 constexpr int kNnCols = 128;      // corpus frames of a tile, 64 per wave pair
-constexpr int kNnKC = 32;         // bins per LDS chunk
-constexpr int kNnPitch = 36;      // floats between LDS rows: 16-byte aligned, and the 16 lanes of one read group fall into 64 different banks
 constexpr int kNnGroup = 16;      // query blocks that are in flight together
 constexpr int kNnLoads = (kNnRows + kNnCols) / 8;      // dwords a thread loads per chunk
 constexpr int kNnEmpty = 0x7fffffff;
 static_assert(kNnSpan % kNnCols == 0, "a span is a whole number of tiles");
 static_assert(kNnRows == 128 && kNnCols == 128 && kNnThreads == 256, "four waves, each a 64 x 64 corner of 2 x 2 MFMA products");
 static_assert(MMK_NN_TOPK_MAX == 16, "the list capacities end at 16");
-static_assert(2 * MMK_NN_TOPK_MAX * kNnRows <= kNnCols * kNnPitch, "the two waves' lists of a span fit the LDS of one operand");
+static_assert(2 * MMK_NN_TOPK_MAX * kNnRows <= kNnCols * kFwPitch, "the two waves' lists of a span fit the LDS of one operand");
 
 // What the epilogue makes of a sum, and the per-frame vectors it needs: a kernel argument, so an instance carries its own key's data and no
 // other.  `row` is the query row's factor (in a register across the span), `cs` and - where kShift - `sh` are the corpus frame's scale[j] and
@@ -103,8 +90,8 @@ __global__ __launch_bounds__(kNnThreads, 2) void nn_search_kernel(const float* _
                                                                 int64_t rows, const float* __restrict__ y, int64_t y_row_stride,
                                                                 const Key kp, int64_t M, int32_t K, int32_t T, int32_t n_blocks, int32_t n_spans,
                                                                 float* __restrict__ ws_key, int32_t* __restrict__ ws_idx) {
-  __shared__ __attribute__((aligned(16))) float ys[kNnCols * kNnPitch];
-  __shared__ __attribute__((aligned(16))) float xs[kNnRows * kNnPitch];
+  __shared__ __attribute__((aligned(16))) float ys[kNnCols * kFwPitch];
+  __shared__ __attribute__((aligned(16))) float xs[kNnRows * kFwPitch];
   __shared__ float css[2][kNnCols];                 // the tile's frames' scale and shift, two tiles deep;
   __shared__ float shs[2][kNnCols];                 // (an instance whose key has no shift never names shs, and it takes no LDS)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -146,7 +133,7 @@ __global__ __launch_bounds__(kNnThreads, 2) void nn_search_kernel(const float* _
       css[parity][tid] = j < jend ? kp.scale[j] : 0.f;
       if constexpr (Key::kShift) shs[parity][tid] = j < jend ? kp.shift[j] : 0.f;
     }
-    nn_f32x16 acc[2][2];
+    fw_f32x16 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -156,43 +143,33 @@ __global__ __launch_bounds__(kNnThreads, 2) void nn_search_kernel(const float* _
 
     float rg[kNnLoads];
     auto gload = [&](int k0) {
-      const int k = k0 + col;
-      const int kc = k < K ? k : K - 1;
-#pragma unroll
-      for (int i = 0; i < kNnCols / 8; ++i) {
-        const int64_t j = jt + i * 8 + row0;
-        rg[i] = y[(j < M ? j : M - 1) * y_row_stride + kc];
-      }
-#pragma unroll
-      for (int i = 0; i < kNnRows / 8; ++i) {
-        const int64_t r = rbase + i * 8 + row0;
-        rg[kNnCols / 8 + i] = x[(r < rows ? r : rows - 1) * x_row_stride + kc];
-      }
+      fw_load<kNnCols / 8, 8, 0>(rg, y, y_row_stride, jt, M, row0, col, k0, K);
+      fw_load<kNnRows / 8, 8, kNnCols / 8>(rg, x, x_row_stride, rbase, rows, row0, col, k0, K);
     };
     gload(0);
-    for (int k0 = 0; k0 < K; k0 += kNnKC) {
+    for (int k0 = 0; k0 < K; k0 += kFwKC) {
       const bool kin = k0 + col < K;
 #pragma unroll
-      for (int i = 0; i < kNnCols / 8; ++i) ys[(i * 8 + row0) * kNnPitch + col] = (kin && jt + i * 8 + row0 < jend) ? rg[i] : 0.f;
+      for (int i = 0; i < kNnCols / 8; ++i) ys[(i * 8 + row0) * kFwPitch + col] = (kin && jt + i * 8 + row0 < jend) ? rg[i] : 0.f;
 #pragma unroll
       for (int i = 0; i < kNnRows / 8; ++i)
-        xs[(i * 8 + row0) * kNnPitch + col] = (kin && rbase + i * 8 + row0 < rows) ? rg[kNnCols / 8 + i] : 0.f;
+        xs[(i * 8 + row0) * kFwPitch + col] = (kin && rbase + i * 8 + row0 < rows) ? rg[kNnCols / 8 + i] : 0.f;
       __syncthreads();
-      if (k0 + kNnKC < K) gload(k0 + kNnKC);
+      if (k0 + kFwKC < K) gload(k0 + kFwKC);
 #pragma unroll
-      for (int g = 0; g < kNnKC; g += 8) {
-        nn_f32x4 av[2], bv[2];
+      for (int g = 0; g < kFwKC; g += 8) {
+        fw_f32x4 av[2], bv[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-          av[t] = *reinterpret_cast<const nn_f32x4*>(&ys[(wm * 64 + t * 32 + fr) * kNnPitch + g + 4 * fh]);
-          bv[t] = *reinterpret_cast<const nn_f32x4*>(&xs[(wn * 64 + t * 32 + fr) * kNnPitch + g + 4 * fh]);
+          av[t] = fw_frag(ys, wm * 64 + t * 32 + fr, g, fh);
+          bv[t] = fw_frag(xs, wn * 64 + t * 32 + fr, g, fh);
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e)
 #pragma unroll
           for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
-            for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[tm][e], bv[tn][e], acc[tm][tn], 0, 0, 0);
+            for (int tn = 0; tn < 2; ++tn) fw_mfma(acc[tm][tn], av[tm], bv[tn], e);
       }
       __syncthreads();
     }
@@ -208,7 +185,7 @@ __global__ __launch_bounds__(kNnThreads, 2) void nn_search_kernel(const float* _
     for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
-        const int jl = wm * 64 + tm * 32 + (q & 3) + 8 * (q >> 2) + 4 * fh;
+        const int jl = fw_acc_row(wm * 64 + tm * 32, q, fh);
         const int64_t j = jt + jl;
         const float cs = css[parity][jl];
         float sh = 0.f;

@@ -5,11 +5,10 @@
 //                         d(r, c) = 1 - <x_r, x_c> rx[r] rx[c], d(r, r) = 0 and 0 where r or c lies outside [0, frames).  A workgroup of four
 //                         waves owns a run of MMK_NOVELTY_TILE = 64 output frames and the R = 64 + 2 h_max + 1 frames their boards touch
 //                         (local row p = frame i0 - 1 - h_max + p), h_max the largest half-width of the CALL; NB = ceil(R / 32) = 3, 4 or 5
-//                         blocks of 32 rows.  The rows go through LDS in chunks of 32 bins as in nn_search.h (dword loads, consecutive
-//                         lanes on consecutive bins, unconditional at clamped addresses, the mask picks zero afterwards; the next chunk's
-//                         loads in flight while this chunk's products run), and the lower triangle of the NB x NB blocks of their Gram
-//                         matrix is formed with v_mfma_f32_32x32x2_f32, block w + 4 s on wave w, with the same permutation of the bins on
-//                         both operands: ONE order of the sum over the bins for every pair of frames, wherever it sits in a tile.
+//                         blocks of 32 rows.  The rows are staged by the pieces of frame_walk.h (clamped on both sides: a tile's first
+//                         rows lie before frame 0), and the lower triangle of the NB x NB blocks of their Gram matrix is formed with its
+//                         products, block w + 4 s on wave w: ONE order of the sum over the bins for every pair of frames, wherever it
+//                         sits in a tile.
 //                         The Gram tile becomes distances in the same LDS, by diagonal: D[r - c][r] for 0 <= r - c <= 2 h_max + 1 (the
 //                         matrix is symmetric; a pitch of 32 NB + 1 keeps the lanes of the stores, which differ in c, and those of the
 //                         reads, which differ in r, in different banks).  Then wave w owns one quadrant of the board (sign of a, sign of b)
@@ -26,18 +25,13 @@
 //                         every higher-ranked candidate there is rejected.  The fixed point is the sequential walk's result, whatever the
 //                         order in which the threads read each other's decisions.
 // No atomics, no workgroup waits for another; every sum has one order, so two calls give the same bits.  NaN in the inputs is not handled.
-#include "mmk_common.h"
+#include "frame_walk.h"
 #include "wave_ops.h"
 
 namespace mmk {
 
-typedef float nv_f32x4 __attribute__((ext_vector_type(4)));
-typedef float nv_f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kNvTile = MMK_NOVELTY_TILE;
 constexpr int kNvThreads = 256;
-constexpr int kNvKC = 32;           // bins per LDS chunk
-constexpr int kNvPitch = 36;        // floats between staged rows (nn_search.h: kNnPitch)
 constexpr int kNvMaxKernels = MMK_NOVELTY_MAX_KERNELS;
 constexpr int kNvMaxHalf = MMK_NOVELTY_MAX_HALF;
 constexpr int kNvMinChunk = 4096;   // frames of one partial minimum
@@ -55,7 +49,7 @@ constexpr int nv_min(int a, int b) { return a < b ? a : b; }
 constexpr int nv_half_cap(int nb) { return nv_min((nb * 32 - kNvTile - 1) / 2, kNvMaxHalf); }
 constexpr int nv_deltas(int nb) { return 2 * nv_half_cap(nb) + 2; }
 constexpr int nv_lds_floats(int nb) {
-  return nv_max(nv_max(nv_deltas(nb) * (nb * 32 + 1), nb * 32 * kNvPitch), 2 * kNvMaxKernels * 4 * kNvTile);
+  return nv_max(nv_max(nv_deltas(nb) * (nb * 32 + 1), nb * 32 * kFwPitch), 2 * kNvMaxKernels * 4 * kNvTile);
 }
 
 template <int NB>
@@ -99,7 +93,7 @@ __global__ __launch_bounds__(kNvThreads) void novelty_kernel(const float* __rest
 
   int br[kSlots], bc[kSlots];
   bool on[kSlots];
-  nv_f32x16 acc[kSlots];
+  fw_f32x16 acc[kSlots];
 #pragma unroll
   for (int s = 0; s < kSlots; ++s) {
     const int idx = wave + 4 * s;
@@ -113,38 +107,23 @@ __global__ __launch_bounds__(kNvThreads) void novelty_kernel(const float* __rest
   }
 
   float rg[kLoads];
-  auto gload = [&](int k0) {
-    const int k = k0 + col;
-    const int kc = k < K ? k : K - 1;
-#pragma unroll
-    for (int i = 0; i < kLoads; ++i) {
-      int64_t g = g0 + i * 8 + row0;
-      g = g < 0 ? 0 : (g < T ? g : T - 1);
-      rg[i] = xb[g * row_stride + kc];
-    }
-  };
+  auto gload = [&](int k0) { fw_load<kLoads, 8, 0, true>(rg, xb, row_stride, g0, T, row0, col, k0, K); };
   gload(0);
-  for (int k0 = 0; k0 < K; k0 += kNvKC) {
+  for (int k0 = 0; k0 < K; k0 += kFwKC) {
     const bool kin = k0 + col < K;
 #pragma unroll
     for (int i = 0; i < kLoads; ++i) {
       const int p = i * 8 + row0;
       const int64_t g = g0 + p;
-      stage[p * kNvPitch + col] = (kin && p < R && g >= 0 && g < T) ? rg[i] : 0.f;
+      stage[p * kFwPitch + col] = (kin && p < R && g >= 0 && g < T) ? rg[i] : 0.f;
     }
     __syncthreads();
-    if (k0 + kNvKC < K) gload(k0 + kNvKC);
+    if (k0 + kFwKC < K) gload(k0 + kFwKC);
 #pragma unroll
-    for (int gb = 0; gb < kNvKC; gb += 8) {
+    for (int gb = 0; gb < kFwKC; gb += 8) {
 #pragma unroll
-      for (int s = 0; s < kSlots; ++s) {
-        if (on[s]) {
-          const nv_f32x4 av = *reinterpret_cast<const nv_f32x4*>(&stage[(br[s] * 32 + fr) * kNvPitch + gb + 4 * fh]);
-          const nv_f32x4 bv = *reinterpret_cast<const nv_f32x4*>(&stage[(bc[s] * 32 + fr) * kNvPitch + gb + 4 * fh]);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], bv[e], acc[s], 0, 0, 0);
-        }
-      }
+      for (int s = 0; s < kSlots; ++s)
+        if (on[s]) fw_mma(acc[s], fw_frag(stage, br[s] * 32 + fr, gb, fh), fw_frag(stage, bc[s] * 32 + fr, gb, fh));
     }
     __syncthreads();
   }
@@ -159,7 +138,7 @@ __global__ __launch_bounds__(kNvThreads) void novelty_kernel(const float* __rest
       const float rc = inv_s[cl];
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
-        const int rl = br[s] * 32 + (q & 3) + 8 * (q >> 2) + 4 * fh;
+        const int rl = fw_acc_row(br[s] * 32, q, fh);
         const int delta = rl - cl;
         if (delta >= 0 && delta <= dmax) {
           const int64_t gr = g0 + rl;

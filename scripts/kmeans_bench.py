@@ -1,7 +1,7 @@
 """One Lloyd iteration of KMeans on one MI355X: assign every frame to its nearest centre, then sum every label's
 frames.
 
-    python scripts/kmeans_bench.py --parent-lib PATH/libmmk_hip.so [--shapes 1048576x16x16,262144x128x16,131072x1025x16,131072x1025x256]
+    python scripts/kmeans_bench.py [--parent-lib PATH/libmmk_hip.so] [--shapes 1048576x16x16,262144x128x16,131072x1025x16,131072x1025x256]
                                    [--repeats 15] [--warmup 3] [--fit-shape 262144x128]
 
 N frames of D bins around K seeded centres, centred by their float32 column mean as KMeans.fit does.  One JSON line per shape N x D x K,
@@ -11,7 +11,8 @@ after `warmup` untimed calls):
   sums            mmk_kmeans_label_sums_f64 (sums and counts)
   step            the two, one after the other: one Lloyd iteration of this tree
   chain_assign, chain_sums, chain
-                  the same iteration chained from the entry points the library had before, through the library given by --parent-lib (the
+                  (with --parent-lib only; without it the line holds this tree's times and the copy alone, which is what a comparison
+                  of two builds of THIS kernel through MMK_DIAG_LIB needs) the same iteration chained from the entry points the library had before, through the library given by --parent-lib (the
                   PARENT commit's build, never this tree's): mmk_half_neg_sqnorm_f32 -> mmk_nn_topk_f32 (t = 1) for the labels, then a
                   stable torch.sort of the labels -> bincount / cumsum -> mmk_segment_mean_f32 (the means, fp32).  It works on a corpus
                   that was centred beforehand (the parent has no offset argument), which is not timed
@@ -86,7 +87,7 @@ def main():
     ap.add_argument("--shapes", default="1048576x16x16,262144x128x16,131072x1025x16,131072x1025x256")
     ap.add_argument("--repeats", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--parent-lib", required=True)
+    ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--fit-shape", default="")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kmeans_bench.jsonl"))
     args = ap.parse_args()
@@ -94,7 +95,7 @@ def main():
         raise SystemExit("kmeans_bench needs the MI355X: there is no CPU path to time")
     device = torch.device("cuda", 0)
     torch.set_grad_enabled(False)
-    parent = parent_library(args.parent_lib)
+    parent = parent_library(args.parent_lib) if args.parent_lib else None
     lib, stream = native.lib(), native.stream_ptr(device)
     lines = []
     for shape in args.shapes.split(","):
@@ -124,7 +125,7 @@ def main():
         ones = torch.ones((max(n, k),), dtype=torch.float32, device=device)
         index = torch.empty((n, 1), dtype=torch.int64, device=device)
         key = torch.empty((n, 1), dtype=torch.float32, device=device)
-        n_topk = parent.mmk_nn_topk_workspace_bytes(n, k, 1)
+        n_topk = parent.mmk_nn_topk_workspace_bytes(n, k, 1) if parent else 0
         topk_work = torch.empty((n_topk // 4,), dtype=torch.float32, device=device)
         means = torch.empty((k, d), dtype=torch.float32, device=device)
         offsets = torch.zeros((k + 1,), dtype=torch.int64, device=device)
@@ -143,18 +144,19 @@ def main():
         line["assign"] = stats_ms(assign, device, args.warmup, args.repeats)
         line["sums"] = stats_ms(label_sums, device, args.warmup, args.repeats)
         line["step"] = stats_ms(lambda: (assign(), label_sums()), device, args.warmup, args.repeats)
-        line["chain_assign"] = stats_ms(chain_assign, device, args.warmup, args.repeats)
-        assert torch.equal(index[:, 0].int(), labels), "the chain's labels and the new kernel's differ"
-        assert int(torch.bincount(index[:, 0], minlength=k).min()) > 0, "the chain's segment_mean takes no empty segment: pick other centres"
-        line["chain_sums"] = stats_ms(chain_sums, device, args.warmup, args.repeats)
-        line["chain"] = stats_ms(lambda: (chain_assign(), chain_sums()), device, args.warmup, args.repeats)
-        worst = float(((sums / counts[:, None]).float() - means).abs().max())
+        if parent:
+            line["chain_assign"] = stats_ms(chain_assign, device, args.warmup, args.repeats)
+            assert torch.equal(index[:, 0].int(), labels), "the chain's labels and the new kernel's differ"
+            assert int(torch.bincount(index[:, 0], minlength=k).min()) > 0, "the chain's segment_mean takes no empty segment: pick other centres"
+            line["chain_sums"] = stats_ms(chain_sums, device, args.warmup, args.repeats)
+            line["chain"] = stats_ms(lambda: (chain_assign(), chain_sums()), device, args.warmup, args.repeats)
+            line.update({"step_over_chain": round(line["step"][0] / line["chain"][0], 3), "parent_digest": parent.mmk_build_digest().decode(),
+                         "means_max_abs_diff": float(((sums / counts[:, None]).float() - means).abs().max())})
         dst = torch.empty_like(x)
         line["copy"] = stats_ms(lambda: dst.copy_(x), device, args.warmup, args.repeats)
         line.update({"corpus_bytes": 4 * n * d, "copy_gbps": round(2 * 4 * n * d / (line["copy"][0] * 1e-3) / 1e9, 1),
-                     "assign_over_half_copy": round(line["assign"][0] / (line["copy"][0] / 2), 2), "step_over_chain": round(line["step"][0] / line["chain"][0], 3),
-                     "means_max_abs_diff": worst, "parent_digest": parent.mmk_build_digest().decode(), "device": torch.cuda.get_device_name(0),
-                     "library_digest": build.library_digest(), "date": time.strftime("%Y-%m-%d")})
+                     "assign_over_half_copy": round(line["assign"][0] / (line["copy"][0] / 2), 2), "device": torch.cuda.get_device_name(0),
+                     "library_digest": lib.mmk_build_digest().decode(), "date": time.strftime("%Y-%m-%d")})
         lines.append(line)
         del dst, xc, x, topk_work, work
     if args.fit_shape:
