@@ -29,6 +29,8 @@ here:
 * ``MelSpec`` / ``MFCC`` (:650-707), librosa's mel filter bank in banded form and scipy's DCT behind it (``features/mel.py``,
   ``csrc/melbank.hip``): on a spectrogram (``native.melbank``) or, through ``from_signal``, as an epilogue of the STFT kernels
   (``native.stft_mel``: one launch from the signal to the mel or MFCC frames, the spectrogram is never written).
+* ``NearestNeighborFilter`` (:1083-1111), librosa's mutual k-nearest-neighbour median (or mean, max, min) of the frames: the k-best
+  search of ``csrc/neighbors.hip`` and one gather-and-aggregate launch behind it (``native.nn_aggregate``, ``csrc/nn_filter.hip``).
 * float64 tensors are computed in fp32 on the device (the kernels are fp32; the reference computes in the input's
   dtype, so float64 mu-law codes may differ from it for inputs within one fp32 ulp of a bin edge).
 """
@@ -46,7 +48,7 @@ from .item_spec import Frame, Sample, Unit, convert
 __all__ = [
     "Continuous", "Discrete", "Functional", "Identity", "Compose", "FileToSignal", "RemoveDC", "Normalize", "Emphasis", "Deemphasis",
     "MuLawCompress", "MuLawExpand", "STFT", "ISTFT", "MagSpec", "GLA", "Resample", "Envelop", "EnvelopBank", "Interpolate", "Derivative",
-    "PCA", "HarmonicSource", "PercussiveSource", "MelSpec", "MFCC",
+    "PCA", "HarmonicSource", "PercussiveSource", "MelSpec", "MFCC", "NearestNeighborFilter",
 ]
 
 N_FFT = 2048
@@ -940,6 +942,85 @@ class HarmonicSource(_HPSSSource):
 @dtc.dataclass
 class PercussiveSource(_HPSSSource):
     _which = 1
+
+
+# ---------------------------------------------------------------------------
+# nearest-neighbour filter
+# ---------------------------------------------------------------------------
+@dtc.dataclass
+class NearestNeighborFilter(Functional):
+    """reference :1083-1111: ``librosa.decompose.nn_filter(inputs, aggregate=getattr(np, aggregate), metric=metric, sym=True, sparse=True,
+    k=n_neighbors, axis=0)`` of (T, F) or (B, T, F) float32 frames on the device.  librosa is not installed where this was written: what
+    follows restates the published ``librosa.segment.recurrence_matrix`` (width 1, connectivity mode, ``sym=True``) and ``nn_filter`` from
+    memory.  Every frame is replaced, bin by bin, by the aggregate of the frames that are among its k nearest other frames AND have it among
+    theirs; a frame without such a neighbour keeps its values.  Two launches: ``native.nn_topk(x, x, min(n_neighbors, T - 1), metric,
+    self_exclude=True)`` and ``native.nn_aggregate`` (``csrc/nn_filter.hip``), behind nn_topk's norm / shift helpers; nothing is read back
+    and the (T, k, F) block of neighbour frames is never written.  ``aggregate`` is one of ``native.NN_AGGREGATES``; a batch is filtered
+    clip by clip, neighbours never cross clips.
+
+    Differences from librosa:
+      * librosa asks sklearn for min(T - 1, k + 2) neighbours and then keeps "the k closest" by an argsort of the stored values, which in
+        connectivity mode are all 1: which k of the k + 2 survive is whatever numpy's unstable sort does with equal keys.  Here the
+        documented meaning is implemented: the k nearest.  Where T - 1 <= k nothing is trimmed and the two readings agree;
+      * "mean" adds the neighbours in float64, in rising order of nearness, and rounds once (numpy: a float32 running sum); median, max
+        and min return numpy's bits on float32;
+      * the search orders by float32 keys (``native.nn_topk``): two frames closer to each other in distance than those roundings may swap
+        places across the k | k + 1 boundary;
+      * librosa refuses (from memory) fewer than about five frames at width 1; here two frames are enough;
+      * metrics "cosine" and "euclidean"; at most ``native.NN_TOPK_MAX`` neighbours."""
+    n_neighbors: int = 16
+    metric: str = "cosine"
+    aggregate: str = "median"
+
+    @property
+    def unit(self) -> Optional[Unit]:
+        return None
+
+    @property
+    def elem_type(self) -> Optional[EventType]:
+        return None
+
+    def np_func(self, inputs):
+        raise NotImplementedError("the numpy (librosa) nn_filter belongs to dataset extraction; use the torch path on the HIP device")
+
+    def torch_func(self, inputs):
+        from .. import native
+        if not isinstance(inputs, torch.Tensor):
+            raise TypeError(f"NearestNeighborFilter: expected a torch.Tensor, got {type(inputs)}")
+        if inputs.dtype != torch.float32:
+            raise TypeError(f"NearestNeighborFilter runs in float32 on the HIP path, got {inputs.dtype}")
+        if inputs.dim() not in (2, 3):
+            raise ValueError(f"NearestNeighborFilter takes (T, F) or (B, T, F), got shape {tuple(inputs.shape)}")
+        k = int(self.n_neighbors)
+        if k < 1:
+            raise ValueError(f"NearestNeighborFilter: n_neighbors = {k} < 1")
+        if k > native.NN_TOPK_MAX:
+            raise NotImplementedError(f"NearestNeighborFilter: n_neighbors = {k}, the limit of the HIP path is {native.NN_TOPK_MAX} "
+                                      "(native.NN_TOPK_MAX)")
+        if self.metric not in native.NN_TOPK_METRICS:
+            raise NotImplementedError(f"NearestNeighborFilter: metric={self.metric!r} is not on the HIP path "
+                                      f"({', '.join(native.NN_TOPK_METRICS)})")
+        if self.aggregate not in native.NN_AGGREGATES:
+            raise ValueError(f"NearestNeighborFilter: aggregate={self.aggregate!r} is none of {', '.join(native.NN_AGGREGATES)}")
+        frames, bins = inputs.shape[-2:]
+        if frames < 2 or bins < 1:
+            raise ValueError(f"NearestNeighborFilter: {frames} frames of {bins} bins, at least two frames are needed")
+        native.require_device(inputs)
+        if inputs.dim() == 3:
+            if inputs.shape[0] < 1:
+                raise ValueError(f"NearestNeighborFilter: empty batch {tuple(inputs.shape)}")
+            return torch.stack([self._clip(clip) for clip in inputs])
+        return self._clip(inputs)
+
+    def _clip(self, x: torch.Tensor) -> torch.Tensor:
+        from .. import native
+        x = x if x.stride(-1) == 1 or x.shape[-1] == 1 else x.contiguous()       # (nn_topk's self_exclude wants the very rows it is given)
+        index, _ = native.nn_topk(x, x, min(int(self.n_neighbors), x.shape[0] - 1), self.metric, self_exclude=True)
+        return native.nn_aggregate(x, index, self.aggregate, mutual=True)
+
+    @property
+    def inv(self) -> Functional:
+        return Identity()
 
 
 # ---------------------------------------------------------------------------

@@ -280,6 +280,13 @@ _KMEANS_SIGNATURES = {
 
 KMEANS_SYMBOLS = tuple(_KMEANS_SIGNATURES)
 
+# include/mmk_nn_filter.h: the nearest-neighbour filter's entry point, a header and a table of its own like the k-means ones
+_NN_FILTER_SIGNATURES = {
+    "mmk_nn_aggregate_f32": (i32, [vp, i64, i64, i32, vp, i32, i32, i32, vp, i64, vp, vp]),
+}
+
+NN_FILTER_SYMBOLS = tuple(_NN_FILTER_SIGNATURES)
+
 _lib = None
 
 
@@ -294,7 +301,7 @@ def load_library(path: Optional[str] = None):
             f"{path} is missing: build it with `python -m mimikit_amd.build` (hipcc, --offload-arch=gfx950). "
             "There is no CPU fallback for the generate path.")
     lib = C.CDLL(path)
-    for name, (res, args) in {**_SIGNATURES, **_KMEANS_SIGNATURES}.items():
+    for name, (res, args) in {**_SIGNATURES, **_KMEANS_SIGNATURES, **_NN_FILTER_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -705,6 +712,42 @@ def edge_components(src: torch.Tensor, dst: torch.Tensor, n: int):
     check(lib().mmk_edge_components_i64(ptr(src) if n_edges else None, ptr(dst) if n_edges else None, n_edges, n, ptr(labels), ptr(count),
                                         ptr(work), n_work, stream_ptr(src.device)), "mmk_edge_components_i64")
     return labels, count
+
+
+# include/mmk_nn_filter.h: MMK_NN_AGG_* in the order of their codes
+NN_AGGREGATES = ("median", "mean", "max", "min")
+
+
+def nn_aggregate(x: torch.Tensor, index: torch.Tensor, op: str = "median", mutual: bool = True, return_count: bool = False):
+    """x (n, k) fp32, index (n, t <= NN_TOPK_MAX) int64 as nn_topk returns it -> (n, k) fp32: every row replaced by the `op` (NN_AGGREGATES)
+    of the rows its list names, bin by bin; a slot outside [0, n) (nn_topk's -1) or equal to its own row number is empty, and a row
+    without a neighbour keeps its values.  With ``mutual`` row j counts for row i only if row j's list holds i.  median / max / min
+    return numpy's bits on float32 (an even count: fl32(fl32(a + b) / 2)), mean is the float64 sum in slot order rounded once.
+    ``return_count``: also the (n,) int32 number of neighbours of every row.  One launch; nothing of size n x t x k is allocated"""
+    x = _nnn_frames(x, 2, "nn_aggregate")
+    if not isinstance(index, torch.Tensor):
+        raise TypeError(f"nn_aggregate: expected a torch.Tensor for index, got {type(index)}")
+    if index.dtype != torch.int64:
+        raise TypeError(f"nn_aggregate takes the int64 index of nn_topk, got {index.dtype}")
+    if index.dim() != 2:
+        raise ValueError(f"nn_aggregate: expected an (n, t) index, got shape {tuple(index.shape)}")
+    require_device(index)
+    if op not in NN_AGGREGATES:
+        raise ValueError(f"nn_aggregate: op={op!r} is none of {', '.join(NN_AGGREGATES)}")
+    n, k = x.shape
+    t = index.shape[1]
+    if min(n, k) < 1 or index.shape[0] != n:
+        raise ValueError(f"nn_aggregate: x {tuple(x.shape)}, index {tuple(index.shape)}")
+    if t < 1:
+        raise ValueError(f"nn_aggregate: t = {t} < 1")
+    if t > NN_TOPK_MAX:
+        raise NotImplementedError(f"nn_aggregate: t = {t} neighbours per row, the limit is {NN_TOPK_MAX} (NN_TOPK_MAX)")
+    index = index.contiguous()
+    out = torch.empty((n, k), dtype=torch.float32, device=x.device)
+    count = torch.empty((n,), dtype=torch.int32, device=x.device) if return_count else None
+    check(lib().mmk_nn_aggregate_f32(ptr(x), x.stride(0), n, k, ptr(index), t, 1 if mutual else 0, NN_AGGREGATES.index(op), ptr(out), out.stride(0),
+                                     ptr(count), stream_ptr(x.device)), "mmk_nn_aggregate_f32")
+    return (out, count) if return_count else out
 
 
 # include/mmk_kmeans.h: MMK_KMEANS_* - the centres of one assignment (the widest centre tile of csrc/kmeans.hip), the candidates of one
