@@ -31,6 +31,8 @@ here:
   (``native.stft_mel``: one launch from the signal to the mel or MFCC frames, the spectrogram is never written).
 * ``NearestNeighborFilter`` (:1083-1111), librosa's mutual k-nearest-neighbour median (or mean, max, min) of the frames: the k-best
   search of ``csrc/neighbors.hip`` and one gather-and-aggregate launch behind it (``native.nn_aggregate``, ``csrc/nn_filter.hip``).
+* ``NMF`` (:1141-1170), sklearn's non-negative matrix factorisation with its defaults: the NNDSVDA start from the PCA kernels' Gram
+  matrix and eigenpairs, and the cyclic coordinate-descent solver with its stop rule on the device (``csrc/nmf.hip``).
 * float64 tensors are computed in fp32 on the device (the kernels are fp32; the reference computes in the input's
   dtype, so float64 mu-law codes may differ from it for inputs within one fp32 ulp of a bin edge).
 """
@@ -48,7 +50,7 @@ from .item_spec import Frame, Sample, Unit, convert
 __all__ = [
     "Continuous", "Discrete", "Functional", "Identity", "Compose", "FileToSignal", "RemoveDC", "Normalize", "Emphasis", "Deemphasis",
     "MuLawCompress", "MuLawExpand", "STFT", "ISTFT", "MagSpec", "GLA", "Resample", "Envelop", "EnvelopBank", "Interpolate", "Derivative",
-    "PCA", "HarmonicSource", "PercussiveSource", "MelSpec", "MFCC", "NearestNeighborFilter",
+    "PCA", "HarmonicSource", "PercussiveSource", "MelSpec", "MFCC", "NearestNeighborFilter", "NMF",
 ]
 
 N_FFT = 2048
@@ -889,6 +891,106 @@ class PCA(Functional):
 
     def torch_func(self, inputs):
         return self.fit(inputs).transform(inputs)
+
+    @property
+    def inv(self) -> Functional:
+        return Identity()
+
+
+@dtc.dataclass
+class NMF(Functional):
+    """reference :1141-1170: ``sklearn.decomposition.NMF(n_components, tol=tol, max_iter=max_iter).fit_transform(x)`` for (N, D) non-negative
+    float32 frames on the device, computed in float64 and returned as W (N, n_components) float32 (``csrc/nmf.hip``, ``include/mmk_nmf.h``):
+
+        native.nmf_start   sklearn's NNDSVDA start from the k leading eigenpairs of X^T X (``native.pca_cov``'s kernel with mean 0 and
+                           scale 1, ``native.pca_eig``'s subspace iteration).  NNDSVD does not see the sign of a singular pair, so any
+                           accurate top-k decomposition gives sklearn's start - where the frames have a spectral gap
+        native.nmf_solve   the cyclic coordinate descent (no shuffle, no regularisation, Frobenius loss) with sklearn's stop rule
+                           ``violation / violation_init <= tol`` held on the device; waits for the stream every 8 iterations
+
+    ``torch_func`` / ``__call__`` are ``fit_transform``, NOT ``fit(x).transform(x)``: as in sklearn, ``transform`` solves for W again from
+    zeros with ``components_`` fixed.  ``fit`` stores ``components_`` (n_components, D) float64 on the device and ``n_iter_`` (int).
+    ``random_seed`` is kept for the YAML form and unused: sklearn's seed enters its randomised SVD only, whose result the start does not
+    depend on beyond rounding (DESIGN.md 5.6.12 - frames without a spectral gap, such as white noise, are not pinned by sklearn itself).
+
+    ValueError: a negative entry; n_components outside [1, min(N, D)] (sklearn starts at random there); n_components beyond the
+    numerical rank of the frames (all-zero frames included: the reference's start is arbitrary there).  NotImplementedError: D >
+    ``native.NMF_MAX_D``, n_components > ``native.NMF_MAX_COMPONENTS``.  Reaching ``max_iter`` with ``tol > 0`` warns, and then
+    ``n_iter_ == max_iter``, as in sklearn.  Not built: the ``mu`` solver, other ``beta_loss``, regularisation, ``shuffle``, other
+    ``init`` modes, ``reconstruction_err_``, NaN / inf handling."""
+    n_components: int = 16
+    tol: float = 1e-4
+    max_iter: int = 200
+    random_seed: int = 42
+
+    def __post_init__(self):
+        self.components_: Optional[torch.Tensor] = None
+        self.n_iter_: Optional[int] = None
+
+    @property
+    def unit(self) -> Optional[Unit]:
+        return None
+
+    @property
+    def elem_type(self) -> Optional[EventType]:
+        return None
+
+    def _check(self, x, what: str) -> torch.Tensor:
+        x = PCA._frames(x, what)
+        if int(self.max_iter) < 1 or not float(self.tol) >= 0.0:
+            raise ValueError(f"{what}: max_iter = {self.max_iter} must be at least 1 and tol = {self.tol} 0 or above")
+        return x
+
+    def _warn(self, n_iter: int, what: str):
+        if n_iter == int(self.max_iter) and float(self.tol) > 0:
+            import warnings
+            warnings.warn(f"{what}: maximum number of iterations {self.max_iter} reached. Increase it to improve convergence.", RuntimeWarning)
+
+    def fit_transform(self, x: torch.Tensor) -> torch.Tensor:
+        from .. import native
+        x = self._check(x, "NMF")
+        n, d = x.shape
+        k = int(self.n_components)
+        if not 1 <= k <= min(n, d):
+            raise ValueError(f"NMF: n_components = {k} must lie in [1, min(N, D) = {min(n, d)}] (beyond it the reference starts at random)")
+        if d > native.NMF_MAX_D:
+            raise NotImplementedError(f"NMF: D = {d} bins, the limit of the HIP path is {native.NMF_MAX_D} (native.NMF_MAX_D)")
+        if k > native.NMF_MAX_COMPONENTS:
+            raise NotImplementedError(f"NMF: n_components = {k}, the limit of the HIP path is {native.NMF_MAX_COMPONENTS} "
+                                      "(native.NMF_MAX_COMPONENTS)")
+        if n < 2:
+            raise ValueError(f"NMF: N = {n} frames, at least 2 are needed")
+        native.require_device(x)
+        w, ht, _, _, _ = native.nmf_start(x, k)
+        self.n_iter_ = native.nmf_solve(x, w, ht, True, self.tol, self.max_iter)
+        self.components_ = ht.t().contiguous()
+        self._warn(self.n_iter_, "NMF")
+        return w.to(torch.float32)
+
+    def fit(self, x: torch.Tensor) -> "NMF":
+        self.fit_transform(x)
+        return self
+
+    def transform(self, y: torch.Tensor) -> torch.Tensor:
+        from .. import native
+        if self.components_ is None:
+            raise RuntimeError("NMF.transform before NMF.fit")
+        y = self._check(y, "NMF.transform")
+        k, d = self.components_.shape
+        if y.shape[0] < 1 or y.shape[1] != d:
+            raise ValueError(f"NMF.transform: y must be (M >= 1, D = {d}), got shape {tuple(y.shape)}")
+        native.require_device(y)
+        w = torch.zeros((y.shape[0], k), dtype=torch.float64, device=y.device)
+        n_iter = native.nmf_solve(y, w, self.components_.t().contiguous(), False, self.tol, self.max_iter, check_nonneg=True)
+        self._warn(n_iter, "NMF.transform")
+        return w.to(torch.float32)
+
+    def np_func(self, inputs):
+        raise NotImplementedError("NMF runs on device tensors only (csrc/nmf.hip): pass a float32 tensor on the HIP device; this package has "
+                                  "no CPU path")
+
+    def torch_func(self, inputs):
+        return self.fit_transform(inputs)
 
     @property
     def inv(self) -> Functional:

@@ -287,6 +287,19 @@ _NN_FILTER_SIGNATURES = {
 
 NN_FILTER_SYMBOLS = tuple(_NN_FILTER_SIGNATURES)
 
+# include/mmk_nmf.h: the NMF entry points, a header and a table of their own like the two above
+_NMF_SIGNATURES = {
+    "mmk_nmf_start_workspace_bytes": (C.c_size_t, [i64, i32, i32]),
+    "mmk_nmf_start_f64": (i32, [vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    "mmk_nmf_half_workspace_bytes": (C.c_size_t, [i64, i32, i32]),
+    "mmk_nmf_w_half_f64": (i32, [vp, i64, i64, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]),
+    "mmk_nmf_h_half_f64": (i32, [vp, i64, i64, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]),
+    "mmk_nmf_solve_workspace_bytes": (C.c_size_t, [i64, i32, i32]),
+    "mmk_nmf_solve_f64": (i32, [vp, i64, i64, i32, i32, vp, vp, i32, C.c_double, i32, i32, i32, vp, vp, C.c_size_t, vp]),
+}
+
+NMF_SYMBOLS = tuple(_NMF_SIGNATURES)
+
 _lib = None
 
 
@@ -301,7 +314,7 @@ def load_library(path: Optional[str] = None):
             f"{path} is missing: build it with `python -m mimikit_amd.build` (hipcc, --offload-arch=gfx950). "
             "There is no CPU fallback for the generate path.")
     lib = C.CDLL(path)
-    for name, (res, args) in {**_SIGNATURES, **_KMEANS_SIGNATURES, **_NN_FILTER_SIGNATURES}.items():
+    for name, (res, args) in {**_SIGNATURES, **_KMEANS_SIGNATURES, **_NN_FILTER_SIGNATURES, **_NMF_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -940,6 +953,106 @@ def pca_project(y: torch.Tensor, mean: torch.Tensor, scale: torch.Tensor, compon
     check(lib().mmk_pca_project_f32(ptr(y), y.stride(0), m, d, ptr(mean), ptr(scale), ptr(components), k, ptr(out), out.stride(0),
                                     stream_ptr(y.device)), "mmk_pca_project_f32")
     return out
+
+
+# include/mmk_nmf.h: MMK_NMF_* - the PCA limits (the Gram matrix and its eigenpairs come from the PCA kernels), the host's read interval of
+# the convergence flag, the cut of sklearn's start and the margin of the rank test
+NMF_MAX_D = PCA_MAX_D
+NMF_MAX_COMPONENTS = PCA_MAX_COMPONENTS
+NMF_POLL = 8
+NMF_EPS = 1e-6
+NMF_RANK_MARGIN = 64.0
+
+
+def _nmf_shape(x: torch.Tensor, k: int, what: str, start: bool = False):
+    """the start needs n_components <= min(N, D) (sklearn's condition for NNDSVDA); the sweeps take any 1 <= n_components <= the limit"""
+    x = _nnn_frames(x, 2, what)
+    n, d = x.shape
+    if n < 1 or d < 1:
+        raise ValueError(f"{what}: empty input {tuple(x.shape)}")
+    if k < 1 or (start and k > min(n, d)):
+        raise ValueError(f"{what}: n_components = {k} must lie in [1, min(N, D) = {min(n, d)}]" if start else
+                         f"{what}: n_components = {k} must be at least 1")
+    if d > NMF_MAX_D:
+        raise NotImplementedError(f"{what}: D = {d} bins, the limit of the HIP path is {NMF_MAX_D} (native.NMF_MAX_D)")
+    if k > NMF_MAX_COMPONENTS:
+        raise NotImplementedError(f"{what}: n_components = {k}, the limit of the HIP path is {NMF_MAX_COMPONENTS} "
+                                  "(native.NMF_MAX_COMPONENTS)")
+    return x, n, d
+
+
+def _nmf_factor(t: torch.Tensor, shape, what: str) -> torch.Tensor:
+    """a factor that a call updates in place: float64, contiguous (a copy would take the update with it)"""
+    if isinstance(t, torch.Tensor) and not t.is_contiguous():
+        raise ValueError(f"{what} is updated in place and must be contiguous, got strides {tuple(t.stride())}")
+    return _f64_vector(t, shape, what)
+
+
+def _nmf_work(n_bytes: int, device) -> torch.Tensor:
+    return torch.empty((max(n_bytes // 8, 1),), dtype=torch.float64, device=device)
+
+
+def nmf_start(x: torch.Tensor, n_components: int):
+    """x (N >= 2, D) fp32 >= 0 -> (w (N, k), ht (D, k), s (k,), v (k, D)) fp64 on the device and part (k,) int32: sklearn's NNDSVDA start
+    from the k leading eigenpairs of X^T X (mmk_nmf.h).  Waits for the stream.  ValueError for a negative entry and for n_components
+    beyond the numerical rank of the frames"""
+    k = int(n_components)
+    x, n, d = _nmf_shape(x, k, "nmf_start", start=True)
+    if n < 2:
+        raise ValueError(f"nmf_start: N = {n} frames, at least 2 are needed")
+    w = torch.empty((n, k), dtype=torch.float64, device=x.device)
+    ht = torch.empty((d, k), dtype=torch.float64, device=x.device)
+    s = torch.empty((k,), dtype=torch.float64, device=x.device)
+    v = torch.empty((k, d), dtype=torch.float64, device=x.device)
+    part = torch.empty((k,), dtype=torch.int32, device=x.device)
+    n_work = lib().mmk_nmf_start_workspace_bytes(n, d, k)
+    work = _nmf_work(n_work, x.device)
+    check(lib().mmk_nmf_start_f64(ptr(x), x.stride(0), n, d, k, ptr(w), ptr(ht), ptr(s), ptr(v), ptr(part), ptr(work), n_work, stream_ptr(x.device)),
+          "mmk_nmf_start_f64")
+    return w, ht, s, v, part
+
+
+def _nmf_half(which: str, x: torch.Tensor, w: torch.Tensor, ht: torch.Tensor) -> torch.Tensor:
+    k = w.shape[1] if isinstance(w, torch.Tensor) and w.dim() == 2 else -1
+    x, n, d = _nmf_shape(x, k, f"nmf_{which}_half")
+    w, ht = _nmf_factor(w, (n, k), f"nmf_{which}_half: w"), _nmf_factor(ht, (d, k), f"nmf_{which}_half: ht")
+    violation = torch.empty((1,), dtype=torch.float64, device=x.device)
+    n_work = lib().mmk_nmf_half_workspace_bytes(n, d, k)
+    work = _nmf_work(n_work, x.device)
+    if which == "w":
+        rc = lib().mmk_nmf_w_half_f64(ptr(x), x.stride(0), n, d, k, ptr(ht), ptr(w), ptr(violation), ptr(work), n_work, stream_ptr(x.device))
+    else:
+        rc = lib().mmk_nmf_h_half_f64(ptr(x), x.stride(0), n, d, k, ptr(w), ptr(ht), ptr(violation), ptr(work), n_work, stream_ptr(x.device))
+    check(rc, f"mmk_nmf_{which}_half_f64")
+    return violation
+
+
+def nmf_w_half(x: torch.Tensor, w: torch.Tensor, ht: torch.Tensor) -> torch.Tensor:
+    """one W half-sweep of sklearn's coordinate descent, w (N, k) fp64 contiguous IN PLACE from ht (D, k); returns the violation (1,)"""
+    return _nmf_half("w", x, w, ht)
+
+
+def nmf_h_half(x: torch.Tensor, w: torch.Tensor, ht: torch.Tensor) -> torch.Tensor:
+    """one H half-sweep, ht (D, k) fp64 contiguous IN PLACE from w (N, k); returns the violation (1,)"""
+    return _nmf_half("h", x, w, ht)
+
+
+def nmf_solve(x: torch.Tensor, w: torch.Tensor, ht: torch.Tensor, update_h: bool = True, tol: float = 1e-4, max_iter: int = 200, poll: int = 0,
+              check_nonneg: bool = False) -> int:
+    """sklearn's _fit_coordinate_descent from (w, ht), both fp64 contiguous and updated IN PLACE (ht only with update_h); returns n_iter.
+    The call waits for the stream every ``poll`` iterations (0: NMF_POLL) to read its convergence flag; the result does not depend on it"""
+    k = w.shape[1] if isinstance(w, torch.Tensor) and w.dim() == 2 else -1
+    x, n, d = _nmf_shape(x, k, "nmf_solve")
+    w, ht = _nmf_factor(w, (n, k), "nmf_solve: w"), _nmf_factor(ht, (d, k), "nmf_solve: ht")
+    tol, max_iter, poll = float(tol), int(max_iter), int(poll)
+    if max_iter < 1 or poll < 0 or not tol >= 0.0:
+        raise ValueError(f"nmf_solve: max_iter = {max_iter} must be at least 1, poll = {poll} and tol = {tol} 0 or above")
+    n_iter = i32(0)
+    n_work = lib().mmk_nmf_solve_workspace_bytes(n, d, k)
+    work = _nmf_work(n_work, x.device)
+    check(lib().mmk_nmf_solve_f64(ptr(x), x.stride(0), n, d, k, ptr(w), ptr(ht), 1 if update_h else 0, tol, max_iter, poll, 1 if check_nonneg else 0,
+                                  C.byref(n_iter), ptr(work), n_work, stream_ptr(x.device)), "mmk_nmf_solve_f64")
+    return int(n_iter.value)
 
 
 def _rows(x: torch.Tensor) -> torch.Tensor:
