@@ -1,3 +1,4 @@
 from .from_neighbors import *
 from .clusters import *
 from .segment import *
+from .samplify import *

@@ -624,7 +624,9 @@ class Interpolate(Functional):
     """reference :867-916.  On a device tensor the last axis is resampled by ``native.interp1d``: ``mode="linear"`` at the positions of
     ``torch.nn.functional.interpolate(mode="linear")`` (align_corners=False), with the reference's ``.squeeze()`` of the result;
     ``mode="previous"`` at scipy's positions ``np.linspace(0, n - 1, N)`` - the reference sends every non-linear mode through scipy on
-    the host and moves the result back, here it stays on the device.  Other modes and other axes raise NotImplementedError."""
+    the host and moves the result back, here it stays on the device; ``mode="quadratic"`` is scipy's interpolating spline at the same
+    positions (``native.spline2_coef`` / ``native.spline2_eval``: not-a-knot ends, float64 inside, at least 3 points).  Other modes and
+    other axes raise NotImplementedError."""
     axis: int = -1
     mode: str = "linear"
     length: Optional[int] = None
@@ -662,13 +664,15 @@ class Interpolate(Functional):
 
     def torch_func(self, inputs):
         from .. import native
-        if self.mode not in native.INTERP_MODES:
-            raise NotImplementedError(f"Interpolate(mode='{self.mode}') is not on the HIP path: 'linear' or 'previous'")
+        if self.mode not in native.INTERP_MODES and self.mode != "quadratic":
+            raise NotImplementedError(f"Interpolate(mode='{self.mode}') is not on the HIP path: 'linear', 'previous' or 'quadratic'")
         if not isinstance(inputs, torch.Tensor) or inputs.dim() == 0 or self.axis not in (-1, inputs.dim() - 1):
             raise NotImplementedError(f"Interpolate(axis={self.axis}) is not on the HIP path: the last axis only")
         n_out = self._get_target_length(inputs)
         if self.mode == "linear":
             return native.interp1d(inputs, n_out, "linear", align=False).squeeze()
+        if self.mode == "quadratic":
+            return native.spline2_eval(native.spline2_coef(inputs), n_out)
         return native.interp1d(inputs, n_out, "previous", align=True)
 
 

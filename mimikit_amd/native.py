@@ -300,6 +300,19 @@ _NMF_SIGNATURES = {
 
 NMF_SYMBOLS = tuple(_NMF_SIGNATURES)
 
+# include/mmk_samplify.h: the quadratic spline and the onset-cut entry points of Samplifyer, a header and a table of their own like the three above
+_SAMPLIFY_SIGNATURES = {
+    "mmk_spline2_coef_f64": (i32, [vp, i64, i32, i64, vp, i64, vp]),
+    "mmk_spline2_eval_f32": (i32, [vp, i64, i32, i64, vp, i64, i64, vp]),
+    "mmk_periods_workspace_bytes": (C.c_size_t, [i64]),
+    "mmk_periods_count_i64": (i32, [vp, i64, vp, i64, vp, vp, C.c_size_t, vp]),
+    "mmk_periods_fill_i64": (i32, [vp, i64, vp, i64, vp, C.c_size_t, i64, i64, vp, vp, vp, vp]),
+    "mmk_samplify_scores_f32": (i32, [vp, i64, i64, vp, vp, i64, C.c_float, vp, vp, vp, vp, vp]),
+    "mmk_samplify_cuts_i64": (i32, [vp, i64, vp, vp, vp, i32, vp, vp, i64, vp, vp, vp, vp]),
+}
+
+SAMPLIFY_SYMBOLS = tuple(_SAMPLIFY_SIGNATURES)
+
 _lib = None
 
 
@@ -314,7 +327,7 @@ def load_library(path: Optional[str] = None):
             f"{path} is missing: build it with `python -m mimikit_amd.build` (hipcc, --offload-arch=gfx950). "
             "There is no CPU fallback for the generate path.")
     lib = C.CDLL(path)
-    for name, (res, args) in {**_SIGNATURES, **_KMEANS_SIGNATURES, **_NN_FILTER_SIGNATURES, **_NMF_SIGNATURES}.items():
+    for name, (res, args) in {**_SIGNATURES, **_KMEANS_SIGNATURES, **_NN_FILTER_SIGNATURES, **_NMF_SIGNATURES, **_SAMPLIFY_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -1176,6 +1189,149 @@ def derivative(x: torch.Tensor, max_lag: int) -> torch.Tensor:
     check(lib().mmk_derivative_f32(ptr(x2), x2.stride(0), batch, n, max_lag, ptr(out), out.stride(0), stream_ptr(x.device)),
           "mmk_derivative_f32")
     return out.reshape(x.shape)
+
+
+# include/mmk_samplify.h: MMK_SPLINE2_* / MMK_PERIODS_TILE / MMK_SAMPLIFY_* - the knots one workgroup of the coefficient kernel owns and the
+# halo a coefficient is solved from, the outputs per step of the evaluation, the samples one workgroup of the period kernels owns, the levels,
+# the half window and the lanes per cut of the cut kernel (csrc/samplify.hip); the tests place their sizes on these
+SPLINE2_TILE = 256
+SPLINE2_HALO = 32
+SPLINE2_EVAL_TILE = 256
+PERIODS_TILE = 1024
+SAMPLIFY_MAX_LEVELS = 6
+SAMPLIFY_MAX_WINDOW = 2000
+SAMPLIFY_GROUP = 256
+
+
+def spline2_coef(x: torch.Tensor) -> torch.Tensor:
+    """x: (..., n) fp32, rows at any stride -> (..., n) float64: the B-spline coefficients of scipy's interp1d(np.arange(n), x, kind="quadratic")
+    (make_interp_spline(k=2), not-a-knot ends) of every row; n >= 3"""
+    x2 = _float32_rows(x, "spline2_coef")
+    batch, n = x2.shape
+    if n < 3:
+        raise ValueError(f"spline2_coef: a quadratic spline needs n >= 3 knots, got {n}")
+    out = torch.empty((batch, n), dtype=torch.float64, device=x.device)
+    if batch == 0:
+        return out.reshape(x.shape)
+    check(lib().mmk_spline2_coef_f64(ptr(x2), x2.stride(0), batch, n, ptr(out), out.stride(0), stream_ptr(x.device)), "mmk_spline2_coef_f64")
+    return out.reshape(x.shape)
+
+
+def _spline_coef(coef: torch.Tensor, what: str, rows: bool = False) -> torch.Tensor:
+    if not isinstance(coef, torch.Tensor):
+        raise TypeError(f"{what}: expected a torch.Tensor, got {type(coef)}")
+    if coef.dtype != torch.float64:
+        raise TypeError(f"{what} takes the float64 coefficients of spline2_coef, got {coef.dtype}")
+    require_device(coef)
+    if not rows and coef.dim() != 1:
+        raise ValueError(f"{what}: expected one row of coefficients, got shape {tuple(coef.shape)}")
+    if coef.dim() == 0 or coef.shape[-1] < 3:
+        raise ValueError(f"{what}: a quadratic spline needs n >= 3 knots, got shape {tuple(coef.shape)}")
+    return coef if rows else coef.contiguous()
+
+
+def spline2_eval(coef: torch.Tensor, n_out: int) -> torch.Tensor:
+    """coef: (..., n) float64 as spline2_coef returns it -> (..., n_out) fp32: the spline at np.linspace(0, n - 1, n_out) (the positions of
+    interp1d with align=True), evaluated in float64 and rounded once"""
+    coef = _spline_coef(coef, "spline2_eval", rows=True)
+    n_out = int(n_out)
+    if n_out < 1:
+        raise ValueError(f"spline2_eval: needs n_out >= 1 points, got {n_out}")
+    c2 = _rows(coef)
+    batch, n = c2.shape
+    out = torch.empty((batch, n_out), dtype=torch.float32, device=coef.device)
+    if batch == 0:
+        return out.reshape(*coef.shape[:-1], n_out)
+    check(lib().mmk_spline2_eval_f32(ptr(c2), c2.stride(0), batch, n, ptr(out), out.stride(0), n_out, stream_ptr(coef.device)), "mmk_spline2_eval_f32")
+    return out.reshape(*coef.shape[:-1], n_out)
+
+
+def periods(coef: Optional[torch.Tensor], n_samples: int, row: Optional[torch.Tensor] = None):
+    """coef: (n,) float64, the spline of a gradient, or (coef None) row: (n_samples,) fp32, the gradient itself -> (att, dec, peaks) int64,
+    rising: attack_decay of the reference on the spline's n_samples float32 values, which are never written, or on the row as it is.
+    ONE host synchronisation: the two counts the lists are sized by."""
+    if (coef is None) == (row is None):
+        raise ValueError("periods: exactly one of coef and row must be given")
+    if coef is not None:
+        src = coef = _spline_coef(coef, "periods")
+        n, n_samples = coef.shape[0], int(n_samples)
+    else:
+        row = _float32_rows(row, "periods")
+        if row.shape[0] != 1:
+            raise ValueError(f"periods: row must be one (T,) curve, got {row.shape[0]} rows")
+        src = row = row[0]
+        n, n_samples = 0, row.shape[0]
+    if n_samples < 1:
+        raise ValueError(f"periods: n_samples = {n_samples} < 1")
+    dev = src.device
+    n_work = lib().mmk_periods_workspace_bytes(n_samples)
+    work = torch.empty((n_work // 8,), dtype=torch.int64, device=dev)
+    counts = torch.empty((2,), dtype=torch.int64, device=dev)
+    check(lib().mmk_periods_count_i64(ptr(coef), n, ptr(row), n_samples, ptr(counts), ptr(work), n_work, stream_ptr(dev)), "mmk_periods_count_i64")
+    n_att, n_peak = (int(v) for v in counts.tolist())
+    att, dec = torch.empty((n_att,), dtype=torch.int64, device=dev), torch.empty((n_att,), dtype=torch.int64, device=dev)
+    peaks = torch.empty((n_peak,), dtype=torch.int64, device=dev)
+    check(lib().mmk_periods_fill_i64(ptr(coef), n, ptr(row), n_samples, ptr(work), n_work, n_att, n_peak, ptr(att) if n_att else None,
+                                     ptr(dec) if n_att else None, ptr(peaks) if n_peak else None, stream_ptr(dev)), "mmk_periods_fill_i64")
+    return att, dec, peaks
+
+
+def _index_list(t: torch.Tensor, what: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: expected a torch.Tensor, got {type(t)}")
+    if t.dtype != torch.int64 or t.dim() != 1:
+        raise TypeError(f"{what} takes (count,) int64 indices, got {t.dtype} of shape {tuple(t.shape)}")
+    require_device(t)
+    return t.contiguous()
+
+
+def samplify_scores(env_coef: torch.Tensor, n_samples: int, att: torch.Tensor, dec: torch.Tensor, sensitivity: float = 0.0):
+    """-> (scores, env_att, env_dec) fp32 and keep (bool) per attack: the envelope spline at the attack and at its peak, their float32
+    difference, and whether it is above fl32(sensitivity)"""
+    env_coef = _spline_coef(env_coef, "samplify_scores")
+    att, dec = _index_list(att, "samplify_scores"), _index_list(dec, "samplify_scores")
+    if att.shape != dec.shape:
+        raise ValueError(f"samplify_scores: {att.shape[0]} attacks and {dec.shape[0]} peaks")
+    count, dev = att.shape[0], env_coef.device
+    scores, ea, ed = (torch.empty((count,), dtype=torch.float32, device=dev) for _ in range(3))
+    keep = torch.empty((count,), dtype=torch.uint8, device=dev)
+    if count:
+        check(lib().mmk_samplify_scores_f32(ptr(env_coef), env_coef.shape[0], int(n_samples), ptr(att), ptr(dec), count, float(sensitivity), ptr(scores),
+                                            ptr(ea), ptr(ed), ptr(keep), stream_ptr(dev)), "mmk_samplify_scores_f32")
+    return scores, ea, ed, keep.bool()
+
+
+def samplify_cuts(y: torch.Tensor, env_coefs: Sequence[torch.Tensor], grad_coefs: Sequence[torch.Tensor], coarse_cuts: torch.Tensor,
+                  coarse_peaks: torch.Tensor):
+    """y (T,) fp32, the levels' envelope and gradient coefficients (level 0 the coarse one), the kept attacks and their peaks ->
+    (sides, lr_scores, cuts): which side of each coarse cut the finest envelope falls below the coarse one (0 left, 1 right), the (count, 2)
+    left / right scores that decide it, and the refined cuts snapped to a zero crossing of y (include/mmk_samplify.h)"""
+    y = _float32_rows(y, "samplify_cuts")
+    if y.shape[0] != 1:
+        raise ValueError(f"samplify_cuts: y must be one (T,) signal, got {y.shape[0]} rows")
+    y = y[0]
+    levels = len(env_coefs)
+    if levels < 1 or len(grad_coefs) != levels:
+        raise ValueError(f"samplify_cuts: {levels} envelope and {len(grad_coefs)} gradient levels")
+    if levels > SAMPLIFY_MAX_LEVELS:
+        raise NotImplementedError(f"samplify_cuts: {levels} levels, the limit is {SAMPLIFY_MAX_LEVELS} (SAMPLIFY_MAX_LEVELS)")
+    env_coefs = [_spline_coef(c, "samplify_cuts") for c in env_coefs]
+    grad_coefs = [_spline_coef(c, "samplify_cuts") for c in grad_coefs]
+    if any(e.shape != g.shape for e, g in zip(env_coefs, grad_coefs)):
+        raise ValueError("samplify_cuts: a level's envelope and gradient have different numbers of knots")
+    cc, cp = _index_list(coarse_cuts, "samplify_cuts"), _index_list(coarse_peaks, "samplify_cuts")
+    if cc.shape != cp.shape:
+        raise ValueError(f"samplify_cuts: {cc.shape[0]} cuts and {cp.shape[0]} peaks")
+    count, dev = cc.shape[0], y.device
+    sides, cuts = torch.empty((count,), dtype=torch.int64, device=dev), torch.empty((count,), dtype=torch.int64, device=dev)
+    lr = torch.empty((count, 2), dtype=torch.float32, device=dev)
+    if count:
+        e_ptrs = (vp * levels)(*[c.data_ptr() for c in env_coefs])
+        g_ptrs = (vp * levels)(*[c.data_ptr() for c in grad_coefs])
+        knots = (i64 * levels)(*[c.shape[0] for c in env_coefs])
+        check(lib().mmk_samplify_cuts_i64(ptr(y), y.shape[0], e_ptrs, g_ptrs, knots, levels, ptr(cc), ptr(cp), count, ptr(sides), ptr(lr), ptr(cuts),
+                                          stream_ptr(dev)), "mmk_samplify_cuts_i64")
+    return sides, lr, cuts
 
 
 # include/mmk.h: MMK_HPSS_* - the largest median window of mmk_hpss_f32 and the frames x bins one workgroup of it owns (csrc/hpss.hip)
