@@ -1,7 +1,7 @@
 // The time-domain half of the envelope-follower functionals (mimikit/features/functionals.py:794-1004): Interpolate and Derivative.
 // (Envelop's frame energies are an epilogue of the STFT kernels: OUT 5 in istft.hip / spectral2048.hip.)  Both are single streaming
 // passes: consecutive lanes on consecutive outputs, rows at any stride, 4-byte alignment.
-#include "mmk_common.h"
+#include "entry_util.h"
 
 namespace mmk {
 
@@ -97,11 +97,7 @@ __global__ __launch_bounds__(256) void derivative_kernel(const float* __restrict
 
 static int rows_ok(const char* what, const void* x, int64_t x_row_stride, int32_t batch, int64_t n, const void* y, int64_t y_row_stride,
                    int64_t n_y) {
-  if (!x || !y || batch <= 0 || (batch > 1 && (x_row_stride < 0 || y_row_stride < n_y)))
-    return fail(MMK_ERR_INVALID, "%s: bad arguments (batch=%d, n=%lld, row strides %lld / %lld)", what, batch, (long long)n,
-                (long long)x_row_stride, (long long)y_row_stride);
-  if ((reinterpret_cast<uintptr_t>(x) & 3) || (reinterpret_cast<uintptr_t>(y) & 3))
-    return fail(MMK_ERR_INVALID, "%s: x and y must be 4-byte aligned", what);
+  MMK_TRY(rows_check(what, x, x_row_stride, batch, n, y, y_row_stride, n_y, false));
   if (batch > 65535) return fail(MMK_ERR_UNSUPPORTED, "%s: %d rows are more than one launch takes (65535)", what, batch);
   return MMK_OK;
 }
@@ -121,11 +117,9 @@ extern "C" int mmk_interp1d_f32(const float* x, int64_t x_row_stride, int32_t ba
   blocks = blocks > 4096 ? 4096 : blocks;
   const dim3 grid((unsigned)blocks, (unsigned)batch), wg(256);
   hipStream_t st = (hipStream_t)stream;
-  if (align == 0) hipLaunchKernelGGL((interp1d_kernel<0, 0>), grid, wg, 0, st, x, x_row_stride, n, y, y_row_stride, n_out, step, scale);
-  else if (mode == 0) hipLaunchKernelGGL((interp1d_kernel<1, 0>), grid, wg, 0, st, x, x_row_stride, n, y, y_row_stride, n_out, step, scale);
-  else hipLaunchKernelGGL((interp1d_kernel<1, 1>), grid, wg, 0, st, x, x_row_stride, n, y, y_row_stride, n_out, step, scale);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  if (align == 0) return launch(interp1d_kernel<0, 0>, grid, wg, 0, st, x, x_row_stride, n, y, y_row_stride, n_out, step, scale);
+  if (mode == 0) return launch(interp1d_kernel<1, 0>, grid, wg, 0, st, x, x_row_stride, n, y, y_row_stride, n_out, step, scale);
+  return launch(interp1d_kernel<1, 1>, grid, wg, 0, st, x, x_row_stride, n, y, y_row_stride, n_out, step, scale);
 }
 
 extern "C" int mmk_derivative_f32(const float* x, int64_t x_row_stride, int32_t batch, int64_t n, int32_t max_lag, float* y,
@@ -138,8 +132,6 @@ extern "C" int mmk_derivative_f32(const float* x, int64_t x_row_stride, int32_t 
   const int64_t n_tiles = (n + kDerivTile - 1) / kDerivTile;
   if (n_tiles * batch > 0x7fffffffLL)
     return fail(MMK_ERR_UNSUPPORTED, "derivative: %lld tiles of %d samples are more than one launch takes", (long long)(n_tiles * batch), kDerivTile);
-  hipLaunchKernelGGL(derivative_kernel, dim3((unsigned)(n_tiles * batch)), dim3(256), 0, (hipStream_t)stream, x, x_row_stride, n, (int)max_lag, n_tiles, y,
-                     y_row_stride);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(derivative_kernel, dim3((unsigned)(n_tiles * batch)), dim3(256), 0, (hipStream_t)stream, x, x_row_stride, n, (int)max_lag, n_tiles, y,
+                y_row_stride);
 }

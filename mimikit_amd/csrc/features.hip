@@ -3,7 +3,7 @@
 // coalesced 16 B/lane accesses, tables and frame tiles staged in LDS.
 #include <stdlib.h>
 
-#include "mmk_common.h"
+#include "entry_util.h"
 
 namespace mmk {
 
@@ -226,24 +226,20 @@ extern "C" int mmk_mulaw_compress_f32_i64(const float* x, int64_t* codes, int64_
   if (n == 0) return MMK_OK;
   if (!x || !codes || n < 0 || q_levels < 2 || q_levels > 65536)
     return fail(MMK_ERR_INVALID, "mulaw_compress: bad arguments (n=%lld, q_levels=%d)", (long long)n, q_levels);
-  const bool aligned = ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && ((reinterpret_cast<uintptr_t>(codes) & 15) == 0);
+  const bool aligned = !misaligned(x, 16) && !misaligned(codes, 16);
   if (edges && aligned && q_levels <= kMuLawLdsLevels / 2 && n >= (1 << 16)) {
     const int64_t n4 = n >> 2;
     int64_t sblocks = (n4 + 1023) / 1024;
     sblocks = sblocks > 8192 ? 8192 : sblocks;       // (1024 .. 8192 workgroups: +3 % from the first to the last, scripts/probes/rw_mix.hip)
-    hipLaunchKernelGGL(mulaw_compress_stream_kernel, dim3((unsigned)sblocks), dim3(256), (size_t)q_levels * sizeof(float2), (hipStream_t)stream,
-                       reinterpret_cast<const mu_f32x4*>(x), reinterpret_cast<mu_i64x2*>(codes), n4, q_levels, compression, edges);
-    MMK_HIP(hipGetLastError());
+    MMK_TRY(launch(mulaw_compress_stream_kernel, dim3((unsigned)sblocks), dim3(256), (size_t)q_levels * sizeof(float2), (hipStream_t)stream,
+                   reinterpret_cast<const mu_f32x4*>(x), reinterpret_cast<mu_i64x2*>(codes), n4, q_levels, compression, edges));
     if ((n & 3) == 0) return MMK_OK;
     x += n4 * 4; codes += n4 * 4; n &= 3;            // the last 1 - 3 samples: the general kernel
   }
   int64_t blocks = (n / 4 + 255) / 256;
   blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
-  hipLaunchKernelGGL(mulaw_compress_kernel, dim3((unsigned)blocks), dim3(256),
-                     (size_t)(q_levels <= kMuLawLdsLevels ? q_levels : 1) * sizeof(float), (hipStream_t)stream, x, codes, n, q_levels,
-                     compression, edges);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(mulaw_compress_kernel, dim3((unsigned)blocks), dim3(256), (size_t)(q_levels <= kMuLawLdsLevels ? q_levels : 1) * sizeof(float),
+                (hipStream_t)stream, x, codes, n, q_levels, compression, edges);
 }
 
 extern "C" int mmk_mulaw_expand_i64_f32(const int64_t* codes, float* x, int64_t n, int32_t q_levels, float compression,
@@ -254,11 +250,8 @@ extern "C" int mmk_mulaw_expand_i64_f32(const int64_t* codes, float* x, int64_t 
     return fail(MMK_ERR_INVALID, "mulaw_expand: bad arguments (n=%lld, q_levels=%d)", (long long)n, q_levels);
   int64_t blocks = (n / 2 + 255) / 256;
   blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
-  hipLaunchKernelGGL(mulaw_expand_kernel, dim3((unsigned)blocks), dim3(256),
-                     (size_t)(q_levels <= kMuLawLdsLevels ? q_levels : 1) * sizeof(float), (hipStream_t)stream, codes, x, n, q_levels,
-                     compression, table);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(mulaw_expand_kernel, dim3((unsigned)blocks), dim3(256), (size_t)(q_levels <= kMuLawLdsLevels ? q_levels : 1) * sizeof(float),
+                (hipStream_t)stream, codes, x, n, q_levels, compression, table);
 }
 
 extern "C" int64_t mmk_resample_n_out(int64_t n_in, int32_t orig, int32_t nnew) {
@@ -277,10 +270,8 @@ extern "C" int mmk_resample_f32(const float* x, int64_t x_row_stride, int32_t ba
   const int64_t n_out = mmk_resample_n_out(n_in, orig, nnew);
   const int64_t steps = (n_in + orig - 1) / orig;
   dim3 grid((unsigned)((steps + kRsSteps - 1) / kRsSteps), (unsigned)batch);
-  hipLaunchKernelGGL(resample_kernel, grid, dim3(256), lds, (hipStream_t)stream, x, x_row_stride, n_in, table, orig, nnew, width, out,
-                     out_row_stride, n_out);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(resample_kernel, grid, dim3(256), lds, (hipStream_t)stream, x, x_row_stride, n_in, table, orig, nnew, width, out, out_row_stride,
+                n_out);
 }
 
 extern "C" int64_t mmk_stft_n_frames(int64_t n_samples, int32_t n_fft, int32_t hop, int32_t center) {

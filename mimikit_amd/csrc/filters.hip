@@ -23,7 +23,7 @@
 // The two launches are the only ordering between workgroups: nothing waits for another workgroup, and there are no atomics - every
 // sum has one fixed order, so a result does not depend on the run.  Powers of p come from repeated squaring (and p^(i+1), i < 16, from
 // a product chain), never from powf.
-#include "mmk_common.h"
+#include "entry_util.h"
 #include "wave_ops.h"
 
 namespace mmk {
@@ -266,13 +266,9 @@ __global__ __launch_bounds__(kLfWg) void row_norm_scale_kernel(const float* __re
   lf_store_run(yr + s, lf_head(yr), n - s, v);
 }
 
-static int rows_check(const char* what, const void* x, int64_t x_row_stride, int32_t batch, int64_t n, const void* y, int64_t y_row_stride,
-                      int64_t* n_chunks) {
-  if (!x || !y || batch <= 0 || n <= 0 || (batch > 1 && (x_row_stride < 0 || y_row_stride < n)))
-    return fail(MMK_ERR_INVALID, "%s: bad arguments (batch=%d, n=%lld, row strides %lld / %lld)", what, batch, (long long)n,
-                (long long)x_row_stride, (long long)y_row_stride);
-  if ((reinterpret_cast<uintptr_t>(x) & 3) || (reinterpret_cast<uintptr_t>(y) & 3))
-    return fail(MMK_ERR_INVALID, "%s: x and y must be 4-byte aligned", what);
+static int chunks_check(const char* what, const void* x, int64_t x_row_stride, int32_t batch, int64_t n, const void* y, int64_t y_row_stride,
+                        int64_t* n_chunks) {
+  MMK_TRY(rows_check(what, x, x_row_stride, batch, n, y, y_row_stride, n, true));
   *n_chunks = (n + kLfChunk - 1) / kLfChunk;
   if (*n_chunks * batch > 0x7fffffffLL)
     return fail(MMK_ERR_UNSUPPORTED, "%s: %lld chunks of %d samples are more than one launch takes", what, (long long)(*n_chunks * batch), kLfChunk);
@@ -290,25 +286,19 @@ extern "C" int mmk_lfilter1_f32(const float* x, int64_t x_row_stride, int32_t ba
                                 int64_t y_row_stride, float* workspace, mmk_stream_t stream) {
   using namespace mmk;
   int64_t n_chunks = 0;
-  MMK_TRY(rows_check("lfilter1", x, x_row_stride, batch, n, y, y_row_stride, &n_chunks));
+  MMK_TRY(chunks_check("lfilter1", x, x_row_stride, batch, n, y, y_row_stride, &n_chunks));
   if (!(fabsf(a1) <= 1.f))
     return fail(MMK_ERR_UNSUPPORTED, "lfilter1: |a1| = %g > 1 (the chunk powers a1^4096 .. of an unstable section overflow)", (double)fabsf(a1));
   const unsigned grid = (unsigned)(n_chunks * batch);
-  if (a1 == 0.f) {
-    hipLaunchKernelGGL(lfilter1_fir_kernel, dim3(grid), dim3(kLfWg), 0, (hipStream_t)stream, x, x_row_stride, n, n_chunks, b0, b1, y, y_row_stride);
-    MMK_HIP(hipGetLastError());
-    return MMK_OK;
-  }
+  if (a1 == 0.f)
+    return launch(lfilter1_fir_kernel, dim3(grid), dim3(kLfWg), 0, (hipStream_t)stream, x, x_row_stride, n, n_chunks, b0, b1, y, y_row_stride);
   if (n_chunks > 1) {
     if (!workspace) return fail(MMK_ERR_WORKSPACE, "lfilter1: a row of %lld samples needs mmk_lfilter1_workspace_floats() floats", (long long)n);
-    hipLaunchKernelGGL(lfilter1_scan_kernel<false>, dim3((unsigned)((n_chunks - 1) * batch)), dim3(kLfWg), 0, (hipStream_t)stream, x, x_row_stride, n,
-                       n_chunks, n_chunks - 1, b0, b1, -a1, (float*)nullptr, (int64_t)0, workspace);
-    MMK_HIP(hipGetLastError());
+    MMK_TRY(launch(lfilter1_scan_kernel<false>, dim3((unsigned)((n_chunks - 1) * batch)), dim3(kLfWg), 0, (hipStream_t)stream, x, x_row_stride, n,
+                   n_chunks, n_chunks - 1, b0, b1, -a1, (float*)nullptr, (int64_t)0, workspace));
   }
-  hipLaunchKernelGGL(lfilter1_scan_kernel<true>, dim3(grid), dim3(kLfWg), 0, (hipStream_t)stream, x, x_row_stride, n, n_chunks, n_chunks, b0, b1, -a1,
-                     y, y_row_stride, workspace);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(lfilter1_scan_kernel<true>, dim3(grid), dim3(kLfWg), 0, (hipStream_t)stream, x, x_row_stride, n, n_chunks, n_chunks, b0, b1, -a1,
+                y, y_row_stride, workspace);
 }
 
 extern "C" size_t mmk_row_normalize_workspace_floats(int32_t batch, int64_t n) { return mmk_lfilter1_workspace_floats(batch, n); }
@@ -317,18 +307,16 @@ extern "C" int mmk_row_normalize_f32(const float* x, int64_t x_row_stride, int32
                                      int64_t y_row_stride, float* workspace, mmk_stream_t stream) {
   using namespace mmk;
   int64_t n_chunks = 0;
-  MMK_TRY(rows_check("row_normalize", x, x_row_stride, batch, n, y, y_row_stride, &n_chunks));
+  MMK_TRY(chunks_check("row_normalize", x, x_row_stride, batch, n, y, y_row_stride, &n_chunks));
   if (p < 0 || p > 2) return fail(MMK_ERR_UNSUPPORTED, "row_normalize: p must be 0 (inf), 1 or 2, got %d", p);
   if (!workspace) return fail(MMK_ERR_WORKSPACE, "row_normalize: needs mmk_row_normalize_workspace_floats() floats");
   const dim3 grid((unsigned)(n_chunks * batch)), wg(kLfWg);
   hipStream_t st = (hipStream_t)stream;
-#define MMK_NRM_LAUNCH(P)                                                                                                         \
-  hipLaunchKernelGGL(row_norm_partial_kernel<P>, grid, wg, 0, st, x, x_row_stride, n, n_chunks, workspace);                       \
-  hipLaunchKernelGGL(row_norm_scale_kernel<P>, grid, wg, 0, st, x, x_row_stride, n, n_chunks, eps, workspace, y, y_row_stride)
+#define MMK_NRM_LAUNCH(P)                                                                                                \
+  MMK_TRY(launch(row_norm_partial_kernel<P>, grid, wg, 0, st, x, x_row_stride, n, n_chunks, workspace));                 \
+  return launch(row_norm_scale_kernel<P>, grid, wg, 0, st, x, x_row_stride, n, n_chunks, eps, workspace, y, y_row_stride)
   if (p == 0) { MMK_NRM_LAUNCH(0); }
   else if (p == 1) { MMK_NRM_LAUNCH(1); }
   else { MMK_NRM_LAUNCH(2); }
 #undef MMK_NRM_LAUNCH
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
 }

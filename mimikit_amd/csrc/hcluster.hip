@@ -37,7 +37,7 @@
 //                in this file) cannot be captured into a graph.  The numbering is cc_count / cc_scan / cc_rank / cc_label above with
 //                rep = parent and cmin = the identity.  Three int32 arrays of n, one of the blocks and the flag as workspace.
 // No workgroup waits for another, no scratch, and two calls give the same bits.  NaN in the inputs is not handled.
-#include "mmk_common.h"
+#include "entry_util.h"
 
 namespace mmk {
 
@@ -196,12 +196,10 @@ extern "C" int mmk_nn_components_i64(const int64_t* nearest, int64_t n, int64_t*
   if (n > 0x7fffffffLL) return fail(MMK_ERR_UNSUPPORTED, "nn_components: n = %lld nodes: indices are kept in 32 bits", (long long)n);
   if (!nearest || !labels || !n_components || !workspace)
     return fail(MMK_ERR_INVALID, "nn_components: bad arguments (null pointer)");
-  if ((reinterpret_cast<uintptr_t>(nearest) | reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(n_components)) & 7)
+  if (misaligned(nearest, 8) || misaligned(labels, 8) || misaligned(n_components, 8))
     return fail(MMK_ERR_INVALID, "nn_components: nearest, labels and n_components must be 8-byte aligned");
-  if (reinterpret_cast<uintptr_t>(workspace) & 3) return fail(MMK_ERR_INVALID, "nn_components: the workspace must be 4-byte aligned");
-  if (workspace_bytes < mmk_nn_components_workspace_bytes(n))
-    return fail(MMK_ERR_WORKSPACE, "nn_components: the workspace has %zu bytes, %zu are needed", workspace_bytes,
-                mmk_nn_components_workspace_bytes(n));
+  if (misaligned(workspace, 4)) return fail(MMK_ERR_INVALID, "nn_components: the workspace must be 4-byte aligned");
+  MMK_TRY(workspace_check("nn_components", workspace, 4, workspace_bytes, mmk_nn_components_workspace_bytes(n)));
   hipStream_t st = (hipStream_t)stream;
   const int32_t nn = (int32_t)n;
   const int blocks = cc_blocks(n);
@@ -211,28 +209,18 @@ extern "C" int mmk_nn_components_i64(const int64_t* nearest, int64_t n, int64_t*
   int32_t* cmin = w + 4 * n;
   int32_t* counts = w + 5 * n;
   const dim3 grid((unsigned)blocks), wg(kCcThreads);
-  hipLaunchKernelGGL(cc_init_kernel, grid, wg, 0, st, nearest, nn, p[0], m[0], cmin);
-  MMK_HIP(hipGetLastError());
+  MMK_TRY(launch(cc_init_kernel, grid, wg, 0, st, nearest, nn, p[0], m[0], cmin));
   int rounds = 1;                                   // ceil(log2 n) + 1
   while (((int64_t)1 << (rounds - 1)) < n) ++rounds;
   int cur = 0;
-  for (int r = 0; r < rounds; ++r, cur ^= 1) {
-    hipLaunchKernelGGL(cc_double_kernel, grid, wg, 0, st, p[cur], m[cur], nn, p[cur ^ 1], m[cur ^ 1]);
-    MMK_HIP(hipGetLastError());
-  }
+  for (int r = 0; r < rounds; ++r, cur ^= 1) MMK_TRY(launch(cc_double_kernel, grid, wg, 0, st, p[cur], m[cur], nn, p[cur ^ 1], m[cur ^ 1]));
   int32_t* rep = p[cur ^ 1];                        // the buffers of the round before the last are free again
   int32_t* rank = m[cur ^ 1];
-  hipLaunchKernelGGL(cc_rep_kernel, grid, wg, 0, st, p[cur], m[cur], nn, rep, cmin);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(cc_count_kernel, grid, wg, 0, st, rep, cmin, nn, counts);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(cc_scan_kernel, dim3(1), wg, 0, st, counts, (int32_t)blocks, n_components);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(cc_rank_kernel, grid, wg, 0, st, rep, cmin, counts, nn, rank);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(cc_label_kernel, grid, wg, 0, st, rep, cmin, rank, nn, labels);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  MMK_TRY(launch(cc_rep_kernel, grid, wg, 0, st, p[cur], m[cur], nn, rep, cmin));
+  MMK_TRY(launch(cc_count_kernel, grid, wg, 0, st, rep, cmin, nn, counts));
+  MMK_TRY(launch(cc_scan_kernel, dim3(1), wg, 0, st, counts, (int32_t)blocks, n_components));
+  MMK_TRY(launch(cc_rank_kernel, grid, wg, 0, st, rep, cmin, counts, nn, rank));
+  return launch(cc_label_kernel, grid, wg, 0, st, rep, cmin, rank, nn, labels);
 }
 
 extern "C" size_t mmk_edge_components_workspace_bytes(int64_t n) {
@@ -251,13 +239,10 @@ extern "C" int mmk_edge_components_i64(const int64_t* src, const int64_t* dst, i
     return fail(MMK_ERR_UNSUPPORTED, "edge_components: %lld edges are more than one launch takes", (long long)n_edges);
   if ((n_edges > 0 && (!src || !dst)) || !labels || !n_components || !workspace)
     return fail(MMK_ERR_INVALID, "edge_components: bad arguments (null pointer)");
-  if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(labels) |
-       reinterpret_cast<uintptr_t>(n_components)) & 7)
+  if (misaligned(src, 8) || misaligned(dst, 8) || misaligned(labels, 8) || misaligned(n_components, 8))
     return fail(MMK_ERR_INVALID, "edge_components: src, dst, labels and n_components must be 8-byte aligned");
-  if (reinterpret_cast<uintptr_t>(workspace) & 3) return fail(MMK_ERR_INVALID, "edge_components: the workspace must be 4-byte aligned");
-  if (workspace_bytes < mmk_edge_components_workspace_bytes(n))
-    return fail(MMK_ERR_WORKSPACE, "edge_components: the workspace has %zu bytes, %zu are needed", workspace_bytes,
-                mmk_edge_components_workspace_bytes(n));
+  if (misaligned(workspace, 4)) return fail(MMK_ERR_INVALID, "edge_components: the workspace must be 4-byte aligned");
+  MMK_TRY(workspace_check("edge_components", workspace, 4, workspace_bytes, mmk_edge_components_workspace_bytes(n)));
   hipStream_t st = (hipStream_t)stream;
   const int32_t nn = (int32_t)n;
   const int blocks = cc_blocks(n);
@@ -269,32 +254,22 @@ extern "C" int mmk_edge_components_i64(const int64_t* src, const int64_t* dst, i
   int32_t* changed = counts + blocks;
   const dim3 grid((unsigned)blocks), wg(kCcThreads);
   const dim3 egrid((unsigned)((n_edges + kCcThreads - 1) / kCcThreads));
-  hipLaunchKernelGGL(ec_init_kernel, grid, wg, 0, st, nn, parent, ident);
-  MMK_HIP(hipGetLastError());
+  MMK_TRY(launch(ec_init_kernel, grid, wg, 0, st, nn, parent, ident));
   for (bool again = n_edges > 0; again;) {
     for (int r = 0; r < kEcGroup; ++r) {
       if (r == kEcGroup - 1) MMK_HIP(hipMemsetAsync(changed, 0, sizeof(int32_t), st));
-      hipLaunchKernelGGL(ec_hook_kernel, egrid, wg, 0, st, src, dst, n_edges, nn, parent, changed);
-      MMK_HIP(hipGetLastError());
-      for (int jump = 0; jump < 2; ++jump) {
-        hipLaunchKernelGGL(ec_jump_kernel, grid, wg, 0, st, nn, parent, changed);
-        MMK_HIP(hipGetLastError());
-      }
+      MMK_TRY(launch(ec_hook_kernel, egrid, wg, 0, st, src, dst, n_edges, nn, parent, changed));
+      for (int jump = 0; jump < 2; ++jump) MMK_TRY(launch(ec_jump_kernel, grid, wg, 0, st, nn, parent, changed));
     }
     int32_t flag = 0;
     MMK_HIP(hipMemcpyAsync(&flag, changed, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     MMK_HIP(hipStreamSynchronize(st));
     again = flag != 0;
   }
-  hipLaunchKernelGGL(cc_count_kernel, grid, wg, 0, st, parent, ident, nn, counts);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(cc_scan_kernel, dim3(1), wg, 0, st, counts, (int32_t)blocks, n_components);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(cc_rank_kernel, grid, wg, 0, st, parent, ident, counts, nn, rank);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(cc_label_kernel, grid, wg, 0, st, parent, ident, rank, nn, labels);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  MMK_TRY(launch(cc_count_kernel, grid, wg, 0, st, parent, ident, nn, counts));
+  MMK_TRY(launch(cc_scan_kernel, dim3(1), wg, 0, st, counts, (int32_t)blocks, n_components));
+  MMK_TRY(launch(cc_rank_kernel, grid, wg, 0, st, parent, ident, counts, nn, rank));
+  return launch(cc_label_kernel, grid, wg, 0, st, parent, ident, rank, nn, labels);
 }
 
 extern "C" int mmk_segment_mean_f32(const float* x, int64_t x_row_stride, int64_t n, int32_t k, const int64_t* order, const int64_t* offsets,
@@ -309,13 +284,9 @@ extern "C" int mmk_segment_mean_f32(const float* x, int64_t x_row_stride, int64_
   if (!x || !order || !offsets || !out || x_row_stride < 0 || out_row_stride < 0)
     return fail(MMK_ERR_INVALID, "segment_mean: bad arguments (null pointer or negative stride %lld / %lld)", (long long)x_row_stride,
                 (long long)out_row_stride);
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 3)
-    return fail(MMK_ERR_INVALID, "segment_mean: x and out must be 4-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(order) | reinterpret_cast<uintptr_t>(offsets)) & 7)
-    return fail(MMK_ERR_INVALID, "segment_mean: order and offsets must be 8-byte aligned");
+  if (misaligned(x, 4) || misaligned(out, 4)) return fail(MMK_ERR_INVALID, "segment_mean: x and out must be 4-byte aligned");
+  if (misaligned(order, 8) || misaligned(offsets, 8)) return fail(MMK_ERR_INVALID, "segment_mean: order and offsets must be 8-byte aligned");
   const int threads = k <= 64 ? 64 : (k <= 128 ? 128 : 256);
-  hipLaunchKernelGGL(segment_mean_kernel, dim3((unsigned)n_segments), dim3(threads), 0, (hipStream_t)stream, x, x_row_stride, n, k, order, offsets,
-                     out, out_row_stride);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(segment_mean_kernel, dim3((unsigned)n_segments), dim3(threads), 0, (hipStream_t)stream, x, x_row_stride, n, k, order, offsets,
+                out, out_row_stride);
 }

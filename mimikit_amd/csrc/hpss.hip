@@ -19,7 +19,7 @@
 // the outputs asked for.
 #include <math.h>
 
-#include "mmk_common.h"
+#include "entry_util.h"
 
 namespace mmk {
 
@@ -199,12 +199,12 @@ __global__ __launch_bounds__(kHpssThreads) void hpss_kernel(HpssArgs a) {
 static inline int hpss_slots(int win) { return win == 31 ? 3 : win <= 16 ? 0 : win <= 32 ? 1 : 2; }
 
 template <int WH, bool FH>
-static void hpss_launch_p(int wp, dim3 grid, size_t lds, hipStream_t st, const HpssArgs& a) {
+static int hpss_launch_p(int wp, dim3 grid, size_t lds, hipStream_t st, const HpssArgs& a) {
   switch (wp) {
-    case 0: hipLaunchKernelGGL((hpss_kernel<WH, FH, 16, false>), grid, dim3(kHpssThreads), lds, st, a); break;
-    case 1: hipLaunchKernelGGL((hpss_kernel<WH, FH, 32, false>), grid, dim3(kHpssThreads), lds, st, a); break;
-    case 2: hipLaunchKernelGGL((hpss_kernel<WH, FH, 64, false>), grid, dim3(kHpssThreads), lds, st, a); break;
-    default: hipLaunchKernelGGL((hpss_kernel<WH, FH, 31, true>), grid, dim3(kHpssThreads), lds, st, a); break;
+    case 0: return launch(hpss_kernel<WH, FH, 16, false>, grid, dim3(kHpssThreads), lds, st, a);
+    case 1: return launch(hpss_kernel<WH, FH, 32, false>, grid, dim3(kHpssThreads), lds, st, a);
+    case 2: return launch(hpss_kernel<WH, FH, 64, false>, grid, dim3(kHpssThreads), lds, st, a);
+    default: return launch(hpss_kernel<WH, FH, 31, true>, grid, dim3(kHpssThreads), lds, st, a);
   }
 }
 
@@ -231,9 +231,8 @@ extern "C" int mmk_hpss_f32(const float* s, int64_t s_batch_stride, int64_t s_ro
       (batch > 1 && (s_batch_stride < 0 || out_batch_stride < (frames - 1) * out_row_stride + bins)))
     return fail(MMK_ERR_INVALID, "hpss: strides (s %lld / %lld, out %lld / %lld) for %d clips of (%lld, %d)", (long long)s_batch_stride,
                 (long long)s_row_stride, (long long)out_batch_stride, (long long)out_row_stride, batch, (long long)frames, bins);
-  const uintptr_t ptrs = reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(harmonic) | reinterpret_cast<uintptr_t>(percussive) |
-                         reinterpret_cast<uintptr_t>(harm_median) | reinterpret_cast<uintptr_t>(perc_median);
-  if (ptrs & 3) return fail(MMK_ERR_INVALID, "hpss: s and the outputs must be 4-byte aligned");
+  if (misaligned(s, 4) || misaligned(harmonic, 4) || misaligned(percussive, 4) || misaligned(harm_median, 4) || misaligned(perc_median, 4))
+    return fail(MMK_ERR_INVALID, "hpss: s and the outputs must be 4-byte aligned");
   HpssArgs a;
   a.s = s; a.s_batch_stride = s_batch_stride; a.s_row_stride = s_row_stride; a.frames = frames;
   a.bins = bins; a.win_harm = win_harm; a.win_perc = win_perc;
@@ -251,11 +250,9 @@ extern "C" int mmk_hpss_f32(const float* s, int64_t s_batch_stride, int64_t s_ro
   const dim3 grid((unsigned)tiles);
   hipStream_t st = (hipStream_t)stream;
   switch (hpss_slots(win_harm)) {
-    case 0: hpss_launch_p<16, false>(hpss_slots(win_perc), grid, lds, st, a); break;
-    case 1: hpss_launch_p<32, false>(hpss_slots(win_perc), grid, lds, st, a); break;
-    case 2: hpss_launch_p<64, false>(hpss_slots(win_perc), grid, lds, st, a); break;
-    default: hpss_launch_p<31, true>(hpss_slots(win_perc), grid, lds, st, a); break;
+    case 0: return hpss_launch_p<16, false>(hpss_slots(win_perc), grid, lds, st, a);
+    case 1: return hpss_launch_p<32, false>(hpss_slots(win_perc), grid, lds, st, a);
+    case 2: return hpss_launch_p<64, false>(hpss_slots(win_perc), grid, lds, st, a);
+    default: return hpss_launch_p<31, true>(hpss_slots(win_perc), grid, lds, st, a);
   }
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
 }

@@ -356,8 +356,6 @@ static inline int sums_plog(int32_t d, int32_t k) {
   return (int64_t)k * (8 * (1 << plog) + 8) > kKmSumsLds ? -1 : plog;
 }
 
-static inline bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 }  // namespace mmk
 
 extern "C" int mmk_kmeans_assign_f32(const float* x, int64_t x_row_stride, const float* offset, int64_t n, int32_t d, const float* centres,
@@ -369,31 +367,27 @@ extern "C" int mmk_kmeans_assign_f32(const float* x, int64_t x_row_stride, const
     return fail(MMK_ERR_UNSUPPORTED, "kmeans_assign: k = %d centres, more than the %d (MMK_KMEANS_MAX_K) of the widest centre tile", k, MMK_KMEANS_MAX_K);
   if (!x || !centres || !shift || !labels || x_row_stride < 0 || c_row_stride < 0)
     return fail(MMK_ERR_INVALID, "kmeans_assign: bad arguments (null pointer or negative stride %lld / %lld)", (long long)x_row_stride, (long long)c_row_stride);
-  if (misaligned(x, 3) || misaligned(offset, 3) || misaligned(centres, 3) || misaligned(shift, 3) || misaligned(labels, 3) || misaligned(key, 3))
+  if (misaligned(x, 4) || misaligned(offset, 4) || misaligned(centres, 4) || misaligned(shift, 4) || misaligned(labels, 4) || misaligned(key, 4))
     return fail(MMK_ERR_INVALID, "kmeans_assign: x, offset, centres, shift, labels and key must be 4-byte aligned");
-  if (misaligned(changed, 7)) return fail(MMK_ERR_INVALID, "kmeans_assign: changed must be 8-byte aligned");
+  if (misaligned(changed, 8)) return fail(MMK_ERR_INVALID, "kmeans_assign: changed must be 8-byte aligned");
   const int64_t n_blocks = (n + kKmRows - 1) / kKmRows;
   if (n_blocks > 0x7fffffffLL) return fail(MMK_ERR_UNSUPPORTED, "kmeans_assign: %lld rows are more than one launch takes", (long long)n);
   const dim3 grid((unsigned)n_blocks), block(256);
   unsigned long long* ch = reinterpret_cast<unsigned long long*>(changed);
   hipStream_t st = (hipStream_t)stream;
-#define MMK_KM_ASSIGN(KT, NARROW)                                                                                                              \
-  hipLaunchKernelGGL((kmeans_assign_kernel<KT, NARROW>), grid, block, 0, st, x, x_row_stride, offset, n, d, centres, c_row_stride, shift, k, labels, \
-                     key, ch)
+#define MMK_KM_ASSIGN(KT, NARROW) \
+  launch(kmeans_assign_kernel<KT, NARROW>, grid, block, 0, st, x, x_row_stride, offset, n, d, centres, c_row_stride, shift, k, labels, key, ch)
   if (d <= 16) {
-    if (k <= 32) MMK_KM_ASSIGN(32, true);
-    else if (k <= 64) MMK_KM_ASSIGN(64, true);
-    else if (k <= 128) MMK_KM_ASSIGN(128, true);
-    else MMK_KM_ASSIGN(256, true);
-  } else {
-    if (k <= 32) MMK_KM_ASSIGN(32, false);
-    else if (k <= 64) MMK_KM_ASSIGN(64, false);
-    else if (k <= 128) MMK_KM_ASSIGN(128, false);
-    else MMK_KM_ASSIGN(256, false);
+    if (k <= 32) return MMK_KM_ASSIGN(32, true);
+    if (k <= 64) return MMK_KM_ASSIGN(64, true);
+    if (k <= 128) return MMK_KM_ASSIGN(128, true);
+    return MMK_KM_ASSIGN(256, true);
   }
+  if (k <= 32) return MMK_KM_ASSIGN(32, false);
+  if (k <= 64) return MMK_KM_ASSIGN(64, false);
+  if (k <= 128) return MMK_KM_ASSIGN(128, false);
+  return MMK_KM_ASSIGN(256, false);
 #undef MMK_KM_ASSIGN
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
 }
 
 extern "C" size_t mmk_kmeans_label_sums_workspace_bytes(int64_t n, int32_t d, int32_t k) {
@@ -412,14 +406,14 @@ extern "C" int mmk_kmeans_label_sums_f64(const float* x, int64_t x_row_stride, c
     return fail(MMK_ERR_INVALID, "kmeans_label_sums: bad arguments (null pointer or negative stride %lld / %lld)", (long long)x_row_stride,
                 (long long)c_row_stride);
   if (!centres && (row_d2 || inertia)) return fail(MMK_ERR_INVALID, "kmeans_label_sums: row_d2 and inertia need the centres");
-  if (misaligned(x, 3) || misaligned(offset, 3) || misaligned(labels, 3) || misaligned(centres, 3))
+  if (misaligned(x, 4) || misaligned(offset, 4) || misaligned(labels, 4) || misaligned(centres, 4))
     return fail(MMK_ERR_INVALID, "kmeans_label_sums: x, offset, labels and centres must be 4-byte aligned");
-  if (misaligned(sums, 7) || misaligned(counts, 7) || misaligned(row_d2, 7) || misaligned(inertia, 7))
+  if (misaligned(sums, 8) || misaligned(counts, 8) || misaligned(row_d2, 8) || misaligned(inertia, 8))
     return fail(MMK_ERR_INVALID, "kmeans_label_sums: sums, counts, row_d2 and inertia must be 8-byte aligned");
   const int plog = sums_plog(d, k);
   if (plog < 0) return fail(MMK_ERR_UNSUPPORTED, "kmeans_label_sums: k = %d labels: their counts alone do not fit a wave's %d bytes of LDS", k, kKmSumsLds);
   const size_t need = mmk_kmeans_label_sums_workspace_bytes(n, d, k);
-  if (!workspace || misaligned(workspace, 7) || workspace_bytes < need)
+  if (!workspace || misaligned(workspace, 8) || workspace_bytes < need)
     return fail(MMK_ERR_WORKSPACE, "kmeans_label_sums: the workspace has %zu bytes, %zu are needed, 8-byte aligned", workspace_bytes, need);
   const int slabs = sums_slabs(n, d, k);
   const int64_t rows_per_slab = (n + slabs - 1) / slabs;
@@ -432,20 +426,14 @@ extern "C" int mmk_kmeans_label_sums_f64(const float* x, int64_t x_row_stride, c
   long long* ws_counts = reinterpret_cast<long long*>(ws_sums + (size_t)slabs * kd);
   double* ws_part = reinterpret_cast<double*>(ws_counts + (size_t)slabs * k);
   const size_t lds = (size_t)k * (8 * ((size_t)1 << plog) + 8);
-  hipLaunchKernelGGL(kmeans_sums_kernel, dim3((unsigned)(chunks * slabs)), dim3(64), lds, st, x, x_row_stride, offset, n, d, labels, k, plog, rows_per_slab,
-                     (int32_t)chunks, ws_sums, ws_counts);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(kmeans_sums_combine, dim3((unsigned)((kd + k + 255) / 256)), dim3(256), 0, st, ws_sums, ws_counts, kd, k, slabs, sums, counts);
-  MMK_HIP(hipGetLastError());
+  MMK_TRY(launch(kmeans_sums_kernel, dim3((unsigned)(chunks * slabs)), dim3(64), lds, st, x, x_row_stride, offset, n, d, labels, k, plog, rows_per_slab,
+                 (int32_t)chunks, ws_sums, ws_counts));
+  MMK_TRY(launch(kmeans_sums_combine, dim3((unsigned)((kd + k + 255) / 256)), dim3(256), 0, st, ws_sums, ws_counts, kd, k, slabs, sums, counts));
   if (centres && (row_d2 || inertia)) {
     const int ds = dist_slabs(n);
     const int64_t rps = (n + ds - 1) / ds;
-    hipLaunchKernelGGL(kmeans_d2_kernel, dim3(ds), dim3(256), 0, st, x, x_row_stride, offset, n, d, labels, k, centres, c_row_stride, rps, row_d2, ws_part);
-    MMK_HIP(hipGetLastError());
-    if (inertia) {
-      hipLaunchKernelGGL(kmeans_reduce_kernel, dim3(1), dim3(256), 0, st, ws_part, ds, inertia);
-      MMK_HIP(hipGetLastError());
-    }
+    MMK_TRY(launch(kmeans_d2_kernel, dim3(ds), dim3(256), 0, st, x, x_row_stride, offset, n, d, labels, k, centres, c_row_stride, rps, row_d2, ws_part));
+    if (inertia) MMK_TRY(launch(kmeans_reduce_kernel, dim3(1), dim3(256), 0, st, ws_part, ds, inertia));
   }
   return MMK_OK;
 }
@@ -460,10 +448,10 @@ extern "C" int mmk_kmeans_pp_step_f64(const float* x, int64_t x_row_stride, cons
     return fail(MMK_ERR_UNSUPPORTED, "kmeans_pp_step: t = %d candidates, more than %d (MMK_KMEANS_PP_MAX_TRIALS)", t, MMK_KMEANS_PP_MAX_TRIALS);
   if (!x || !cand || !closest || !pot || !chosen || x_row_stride < 0)
     return fail(MMK_ERR_INVALID, "kmeans_pp_step: bad arguments (null pointer or negative stride %lld)", (long long)x_row_stride);
-  if (misaligned(x, 3) || misaligned(offset, 3)) return fail(MMK_ERR_INVALID, "kmeans_pp_step: x and offset must be 4-byte aligned");
-  if (misaligned(cand, 7) || misaligned(closest, 7) || misaligned(pot, 7) || misaligned(chosen, 7))
+  if (misaligned(x, 4) || misaligned(offset, 4)) return fail(MMK_ERR_INVALID, "kmeans_pp_step: x and offset must be 4-byte aligned");
+  if (misaligned(cand, 8) || misaligned(closest, 8) || misaligned(pot, 8) || misaligned(chosen, 8))
     return fail(MMK_ERR_INVALID, "kmeans_pp_step: cand, closest, pot and chosen must be 8-byte aligned");
-  if (!workspace || misaligned(workspace, 7) || workspace_bytes < mmk_kmeans_pp_step_workspace_bytes())
+  if (!workspace || misaligned(workspace, 8) || workspace_bytes < mmk_kmeans_pp_step_workspace_bytes())
     return fail(MMK_ERR_WORKSPACE, "kmeans_pp_step: the workspace has %zu bytes, %zu are needed, 8-byte aligned", workspace_bytes,
                 mmk_kmeans_pp_step_workspace_bytes());
   hipStream_t st = (hipStream_t)stream;
@@ -471,11 +459,7 @@ extern "C" int mmk_kmeans_pp_step_f64(const float* x, int64_t x_row_stride, cons
   const int64_t rps = (n + slabs - 1) / slabs;
   double* ws_pots = static_cast<double*>(workspace);
   int64_t* ws_row = reinterpret_cast<int64_t*>(ws_pots + (size_t)MMK_KMEANS_MAX_SLABS * MMK_KMEANS_PP_MAX_TRIALS);
-  hipLaunchKernelGGL(kmeans_pp_pots_kernel, dim3(slabs), dim3(256), 0, st, x, x_row_stride, offset, n, d, cand, t, closest, rps, ws_pots);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(kmeans_pp_pick_kernel, dim3(1), dim3(256), 0, st, ws_pots, slabs, cand, t, n, pot, chosen, ws_row);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(kmeans_pp_apply_kernel, dim3(slabs), dim3(256), 0, st, x, x_row_stride, offset, n, d, ws_row, rps, closest);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  MMK_TRY(launch(kmeans_pp_pots_kernel, dim3(slabs), dim3(256), 0, st, x, x_row_stride, offset, n, d, cand, t, closest, rps, ws_pots));
+  MMK_TRY(launch(kmeans_pp_pick_kernel, dim3(1), dim3(256), 0, st, ws_pots, slabs, cand, t, n, pot, chosen, ws_row));
+  return launch(kmeans_pp_apply_kernel, dim3(slabs), dim3(256), 0, st, x, x_row_stride, offset, n, d, ws_row, rps, closest);
 }

@@ -1,7 +1,7 @@
 // MelSpec / MFCC: librosa's mel filter bank, and the DCT behind it, applied to magnitude frames - either frames that exist
 // (mmk_melbank_f32: a spectrogram, or a mel tensor for the DCT alone) or frames that never reach memory (mmk_stft_mel_f32: output mode 6
 // of the STFT kernels of istft.hip / spectral2048.hip).  Both run mel_epilogue of melbank.h on a frame staged in LDS.
-#include "mmk_common.h"
+#include "entry_util.h"
 #include "melbank.h"
 
 namespace mmk {
@@ -65,10 +65,8 @@ extern "C" int mmk_melbank_f32(const float* in, int64_t in_row_stride, int64_t r
   const MelBank B{band, weights, dct, n_mels, dct ? n_mfcc : 0};
   const size_t lds = sizeof(float) * kMelWaves * (size_t)(n_bins + n_mels);
   const int64_t wgs = (rows + kMelWaves - 1) / kMelWaves;
-  hipLaunchKernelGGL(melbank_kernel, dim3((unsigned)(wgs < 2048 ? wgs : 2048)), dim3(64 * kMelWaves), lds, (hipStream_t)stream, B, in, in_row_stride,
-                     rows, n_bins, out);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(melbank_kernel, dim3((unsigned)(wgs < 2048 ? wgs : 2048)), dim3(64 * kMelWaves), lds, (hipStream_t)stream, B, in, in_row_stride, rows,
+                n_bins, out);
 }
 
 extern "C" int mmk_stft_mel_f32(const float* x, int64_t x_row_stride, int32_t batch, int64_t n_samples, int32_t n_fft, int32_t hop, int32_t center,

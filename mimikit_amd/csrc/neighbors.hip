@@ -226,13 +226,10 @@ extern "C" int mmk_nn_cosine_f32(const float* x, int64_t x_row_stride, const flo
   if (!x || !y || !rx || !ry || !index || !cos_best || !workspace || x_row_stride < 0 || y_row_stride < 0)
     return fail(MMK_ERR_INVALID, "nn_cosine: bad arguments (null pointer or negative stride %lld / %lld)", (long long)x_row_stride,
                 (long long)y_row_stride);
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(rx) | reinterpret_cast<uintptr_t>(ry) |
-       reinterpret_cast<uintptr_t>(cos_best) | reinterpret_cast<uintptr_t>(workspace)) & 3)
+  if (misaligned(x, 4) || misaligned(y, 4) || misaligned(rx, 4) || misaligned(ry, 4) || misaligned(cos_best, 4) || misaligned(workspace, 4))
     return fail(MMK_ERR_INVALID, "nn_cosine: x, y, rx, ry, cos_best and the workspace must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(index) & 7) return fail(MMK_ERR_INVALID, "nn_cosine: index must be 8-byte aligned");
-  if (workspace_bytes < mmk_nn_cosine_workspace_bytes(rows, m))
-    return fail(MMK_ERR_WORKSPACE, "nn_cosine: the workspace has %zu bytes, %zu are needed", workspace_bytes,
-                mmk_nn_cosine_workspace_bytes(rows, m));
+  if (misaligned(index, 8)) return fail(MMK_ERR_INVALID, "nn_cosine: index must be 8-byte aligned");
+  MMK_TRY(workspace_check("nn_cosine", workspace, 4, workspace_bytes, mmk_nn_cosine_workspace_bytes(rows, m)));
   // nn_search_launch's grid and workspace (T = 1) around the kernel above: a second copy of that arithmetic, as the kernel is of the walk -
   // a change to the kNnGroup numbering or to the workspace layout is made there, in nn_search_kernel and here
   const int n_spans = nn_spans(m);
@@ -242,13 +239,10 @@ extern "C" int mmk_nn_cosine_f32(const float* x, int64_t x_row_stride, const flo
     return fail(MMK_ERR_UNSUPPORTED, "nn_cosine: %lld rows against %lld frames are more than one launch takes", (long long)rows, (long long)m);
   float* ws_val = static_cast<float*>(workspace);
   int32_t* ws_idx = reinterpret_cast<int32_t*>(ws_val + rows * n_spans);
-  hipLaunchKernelGGL(nn_cosine_kernel, dim3((unsigned)grid), dim3(kNnThreads), 0, (hipStream_t)stream, x, x_row_stride, rx, rows, y, y_row_stride,
-                     ry, m, k, (int32_t)n_blocks, n_spans, ws_val, ws_idx);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(nn_merge_kernel<1>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ws_val, ws_idx, rows, 1, n_spans,
-                     index, cos_best);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  MMK_TRY(launch(nn_cosine_kernel, dim3((unsigned)grid), dim3(kNnThreads), 0, (hipStream_t)stream, x, x_row_stride, rx, rows, y, y_row_stride,
+                 ry, m, k, (int32_t)n_blocks, n_spans, ws_val, ws_idx));
+  return launch(nn_merge_kernel<1>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ws_val, ws_idx, rows, 1, n_spans,
+                index, cos_best);
 }
 
 extern "C" int mmk_nn_cosine_self_f32(const float* x, int64_t x_row_stride, const float* rx, int64_t rows, int32_t k, int64_t* index,
@@ -260,13 +254,10 @@ extern "C" int mmk_nn_cosine_self_f32(const float* x, int64_t x_row_stride, cons
     return fail(MMK_ERR_UNSUPPORTED, "nn_cosine_self: %lld frames: indices are kept in 32 bits across the spans", (long long)rows);
   if (!x || !rx || !index || !cos_best || !workspace || x_row_stride < 0)
     return fail(MMK_ERR_INVALID, "nn_cosine_self: bad arguments (null pointer or negative stride %lld)", (long long)x_row_stride);
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(rx) | reinterpret_cast<uintptr_t>(cos_best) |
-       reinterpret_cast<uintptr_t>(workspace)) & 3)
+  if (misaligned(x, 4) || misaligned(rx, 4) || misaligned(cos_best, 4) || misaligned(workspace, 4))
     return fail(MMK_ERR_INVALID, "nn_cosine_self: x, rx, cos_best and the workspace must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(index) & 7) return fail(MMK_ERR_INVALID, "nn_cosine_self: index must be 8-byte aligned");
-  if (workspace_bytes < mmk_nn_cosine_workspace_bytes(rows, rows))
-    return fail(MMK_ERR_WORKSPACE, "nn_cosine_self: the workspace has %zu bytes, %zu are needed", workspace_bytes,
-                mmk_nn_cosine_workspace_bytes(rows, rows));
+  if (misaligned(index, 8)) return fail(MMK_ERR_INVALID, "nn_cosine_self: index must be 8-byte aligned");
+  MMK_TRY(workspace_check("nn_cosine_self", workspace, 4, workspace_bytes, mmk_nn_cosine_workspace_bytes(rows, rows)));
   return nn_search_launch<1, true>("nn_cosine_self", x, x_row_stride, rx, rows, x, x_row_stride, NnCosineKey{rx}, rows, k, 1, index, cos_best,
                              workspace, (hipStream_t)stream);
 }
@@ -279,12 +270,9 @@ extern "C" int mmk_cum_entropy_i64(const int64_t* items, int64_t row_stride, int
   if (t > MMK_CUM_ENTROPY_MAX_T)
     return fail(MMK_ERR_UNSUPPORTED, "cum_entropy: t = %lld items per row, more than the %d (MMK_CUM_ENTROPY_MAX_T) one workgroup ranks",
                 (long long)t, MMK_CUM_ENTROPY_MAX_T);
-  if (!items || !total || row_stride < 0 || e_row_stride < 0 || (reinterpret_cast<uintptr_t>(items) & 7) ||
-      ((reinterpret_cast<uintptr_t>(total) | reinterpret_cast<uintptr_t>(e)) & 3))
+  if (!items || !total || row_stride < 0 || e_row_stride < 0 || misaligned(items, 8) || misaligned(total, 4) || misaligned(e, 4))
     return fail(MMK_ERR_INVALID, "cum_entropy: bad arguments (null or misaligned pointer, negative stride %lld / %lld)", (long long)row_stride,
                 (long long)e_row_stride);
-  hipLaunchKernelGGL(cum_entropy_kernel, dim3((unsigned)batch), dim3(kCeThreads), 0, (hipStream_t)stream, items, row_stride, (int32_t)t, total,
-                     e, e_row_stride);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(cum_entropy_kernel, dim3((unsigned)batch), dim3(kCeThreads), 0, (hipStream_t)stream, items, row_stride, (int32_t)t, total, e,
+                e_row_stride);
 }

@@ -18,7 +18,8 @@
 //
 // The MFMA units are not used: the products are fp64 FMA chains fed by LDS broadcast reads.  Measured, an iteration at
 // k = 16 is 11 times its floor of two streaming reads of X - the products on v_mfma_f64_16x16x4_f64 are the next step.
-#include "mmk_common.h"
+#include "entry_util.h"
+#include "wave_ops.h"
 
 #include <math.h>
 
@@ -74,19 +75,6 @@ static NfPlan nf_plan(int64_t n, int32_t d, int32_t k) {
   p.chunks = (int)(c < kNfStatChunks ? c : kNfStatChunks);
   p.rows_per_chunk = (n + p.chunks - 1) / p.chunks;
   return p;
-}
-
-// wave tree, then the waves' sums in rising order; every thread gets the sum.  `red` holds blockDim.x / 64 doubles
-__device__ __forceinline__ double nf_block_sum(double v, double* red) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  const int nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < nw; ++w) s += red[w];
-  return s;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the coordinate sweep
@@ -180,7 +168,7 @@ __global__ __launch_bounds__(kNfRows) void nmf_rows_kernel(const float* __restri
     for (int t = 0; t < KP; ++t)
       if (t < k) a[row * k + t] = w[t];
   }
-  viol = nf_block_sum(live ? viol : 0.0, red);
+  viol = block_sum(live ? viol : 0.0, red);
   if (tid == 0) vpart[blockIdx.x] = viol;
 }
 
@@ -258,7 +246,7 @@ __global__ __launch_bounds__(kNfRows) void nmf_cols_kernel(const double* __restr
     for (int t = 0; t < KP; ++t)
       if (t < k) ht[(int64_t)j * k + t] = h[t];
   }
-  viol = nf_block_sum(live ? viol : 0.0, red);
+  viol = block_sum(live ? viol : 0.0, red);
   if (tid == 0) vpart[blockIdx.x] = viol;
 }
 
@@ -345,7 +333,7 @@ __global__ __launch_bounds__(256) void nmf_stat_kernel(const float* __restrict__
       lo = v < lo ? v : lo;
     }
   mn[tid] = lo;
-  acc = nf_block_sum(acc, red);
+  acc = block_sum(acc, red);
   for (int off = 128; off >= 1; off >>= 1) {
     if (tid < off) mn[tid] = mn[tid + off] < mn[tid] ? mn[tid + off] : mn[tid];
     __syncthreads();
@@ -406,8 +394,8 @@ __global__ __launch_bounds__(256) void nmf_partnorm_kernel(const double* __restr
       sp = fma(p, p, sp);
       sn = fma(q, q, sn);
     }
-    sp = nf_block_sum(sp, red);
-    sn = nf_block_sum(sn, red);
+    sp = block_sum(sp, red);
+    sn = block_sum(sn, red);
     if (tid == 0) {
       partial[((int64_t)blockIdx.x * 2 + 0) * k + t] = sp;
       partial[((int64_t)blockIdx.x * 2 + 1) * k + t] = sn;
@@ -463,8 +451,6 @@ __global__ __launch_bounds__(256) void nmf_init_kernel(double* __restrict__ a, i
   a[idx] = out;
 }
 
-static bool nf_misaligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(a - 1)) != 0; }
-
 #define NF_DISPATCH(kp, ...)                                      \
   switch (kp) {                                                   \
     case 4: { constexpr int KP = 4; __VA_ARGS__; } break;         \
@@ -492,21 +478,16 @@ static NfHalfWs nf_half_ws(void* workspace, const NfPlan& p, int32_t d, int32_t 
 }
 
 static int nf_gram(const double* a, int64_t m, int32_t k, int runs, int64_t rows, const NfHalfWs& ws, const int32_t* done, hipStream_t st) {
-  hipLaunchKernelGGL(nmf_gram_kernel, dim3((unsigned)runs), dim3(256), 0, st, a, m, k, rows, ws.gpart, done);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(nmf_gram_reduce_kernel, dim3((unsigned)((k * k + 255) / 256)), dim3(256), 0, st, ws.gpart, runs, k * k, ws.gram, done);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  MMK_TRY(launch(nmf_gram_kernel, dim3((unsigned)runs), dim3(256), 0, st, a, m, k, rows, ws.gpart, done));
+  return launch(nmf_gram_reduce_kernel, dim3((unsigned)((k * k + 255) / 256)), dim3(256), 0, st, ws.gpart, runs, k * k, ws.gram, done);
 }
 
 // the W half: H H^T, then the row kernel; the workgroups' violations go to ws.vpart[0 .. nbw)
 static int nf_w_half(const float* x, int64_t xs, int64_t n, int32_t d, int32_t k, const double* ht, double* w, const NfPlan& p, const NfHalfWs& ws,
                      const int32_t* done, hipStream_t st) {
   MMK_TRY(nf_gram(ht, d, k, p.gruns_d, p.grows_d, ws, done, st));
-  NF_DISPATCH(p.kp, hipLaunchKernelGGL((nmf_rows_kernel<KP, 0>), dim3((unsigned)p.nbw), dim3(kNfRows), 0, st, x, xs, n, d, k, ht,
-                                       (const double*)ws.gram, w, ws.vpart, done));
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  NF_DISPATCH(p.kp, return launch(nmf_rows_kernel<KP, 0>, dim3((unsigned)p.nbw), dim3(kNfRows), 0, st, x, xs, n, d, k, ht,
+                                  (const double*)ws.gram, w, ws.vpart, done));
 }
 
 // the H half: W^T W, the runs' X^T W, then the sweep over the rows of H^T; violations to ws.vpart[nbw .. nbw + nbh)
@@ -514,21 +495,15 @@ static int nf_h_half(const float* x, int64_t xs, int64_t n, int32_t d, int32_t k
                      const int32_t* done, hipStream_t st) {
   MMK_TRY(nf_gram(w, n, k, p.gruns_n, p.grows_n, ws, done, st));
   const dim3 grid((unsigned)((d + kNfXtCols - 1) / kNfXtCols), (unsigned)p.runs);
-  NF_DISPATCH(p.kp, hipLaunchKernelGGL((nmf_xtw_kernel<KP>), grid, dim3(256), 0, st, x, xs, n, d, k, w, p.rows_per_run, ws.xpart, done));
-  MMK_HIP(hipGetLastError());
-  NF_DISPATCH(p.kp, hipLaunchKernelGGL((nmf_cols_kernel<KP>), dim3((unsigned)p.nbh), dim3(kNfRows), 0, st, (const double*)ws.xpart, p.runs, d, k,
-                                       (const double*)ws.gram, ht, ws.vpart + p.nbw, done));
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  NF_DISPATCH(p.kp, MMK_TRY(launch(nmf_xtw_kernel<KP>, grid, dim3(256), 0, st, x, xs, n, d, k, w, p.rows_per_run, ws.xpart, done)));
+  NF_DISPATCH(p.kp, return launch(nmf_cols_kernel<KP>, dim3((unsigned)p.nbh), dim3(kNfRows), 0, st, (const double*)ws.xpart, p.runs, d, k,
+                                  (const double*)ws.gram, ht, ws.vpart + p.nbw, done));
 }
 
 static int nf_stats(const float* x, int64_t xs, int64_t n, int32_t d, const NfPlan& p, double* psum, double* stat, hipStream_t st) {
-  hipLaunchKernelGGL(nmf_stat_kernel, dim3((unsigned)p.chunks), dim3(256), 0, st, x, xs, n, d, p.rows_per_chunk, psum, psum + p.chunks);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(nmf_stat_fin_kernel, dim3(1), dim3(64), 0, st, (const double*)psum, (const double*)(psum + p.chunks), p.chunks,
-                     (double)n * (double)d, stat);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  MMK_TRY(launch(nmf_stat_kernel, dim3((unsigned)p.chunks), dim3(256), 0, st, x, xs, n, d, p.rows_per_chunk, psum, psum + p.chunks));
+  return launch(nmf_stat_fin_kernel, dim3(1), dim3(64), 0, st, (const double*)psum, (const double*)(psum + p.chunks), p.chunks,
+                (double)n * (double)d, stat);
 }
 
 // start: n_components <= min(n, d), the condition of sklearn's NNDSVDA start; the sweeps take any 1 <= n_components <= the limit (a transform
@@ -602,19 +577,16 @@ extern "C" int mmk_nmf_start_f64(const float* x, int64_t x_row_stride, int64_t n
   if (n < 2) return fail(MMK_ERR_INVALID, "nmf_start: n = %lld rows, at least 2 are needed (the Gram matrix comes from the covariance kernel)", (long long)n);
   if (!x || !w || !ht || !s || !v || !part || !workspace || x_row_stride < 0)
     return fail(MMK_ERR_INVALID, "nmf_start: bad arguments (null pointer or negative stride %lld)", (long long)x_row_stride);
-  if (nf_misaligned(x, 4) || nf_misaligned(part, 4) || nf_misaligned(w, 8) || nf_misaligned(ht, 8) || nf_misaligned(s, 8) || nf_misaligned(v, 8) ||
-      nf_misaligned(workspace, 8))
+  if (misaligned(x, 4) || misaligned(part, 4) || misaligned(w, 8) || misaligned(ht, 8) || misaligned(s, 8) || misaligned(v, 8) ||
+      misaligned(workspace, 8))
     return fail(MMK_ERR_INVALID, "nmf_start: x and part must be 4-byte aligned, w, ht, s, v and the workspace 8-byte aligned");
-  if (workspace_bytes < mmk_nmf_start_workspace_bytes(n, d, k))
-    return fail(MMK_ERR_WORKSPACE, "nmf_start: the workspace has %zu bytes, %zu are needed", workspace_bytes, mmk_nmf_start_workspace_bytes(n, d, k));
+  MMK_TRY(workspace_check("nmf_start", workspace, 8, workspace_bytes, mmk_nmf_start_workspace_bytes(n, d, k)));
   hipStream_t st = (hipStream_t)stream;
   const NfPlan p = nf_plan(n, d, k);
   const NfStartWs ws = nf_start_ws(workspace, p, n, d, k);
   MMK_TRY(nf_stats(x, x_row_stride, n, d, p, ws.psum, ws.stat, st));
-  hipLaunchKernelGGL(nmf_fill_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, ws.zeros, d, 0.0);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(nmf_fill_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, ws.ones, d, 1.0);
-  MMK_HIP(hipGetLastError());
+  MMK_TRY(launch(nmf_fill_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, ws.zeros, d, 0.0));
+  MMK_TRY(launch(nmf_fill_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, ws.ones, d, 1.0));
   MMK_TRY(mmk_pca_cov_f64(x, x_row_stride, n, d, ws.zeros, ws.ones, ws.c, ws.cov_ws, ws.cov_bytes, stream));
   int32_t eig_iter = 0;
   MMK_TRY(mmk_pca_eig_f64(ws.c, d, k, 0, v, ws.variance, &eig_iter, ws.eig_ws, ws.eig_bytes, stream));
@@ -631,27 +603,19 @@ extern "C" int mmk_nmf_start_f64(const float* x, int64_t x_row_stride, int64_t n
                 "nmf_start: n_components = %d exceeds the numerical rank of the frames: eigenvalue %d of X^T X is %.3e, not above %.3e "
                 "(= %.0f ((n + 2) 2^-53 + %.0e sqrt(d)) times the largest, %.3e); the reference's start is arbitrary there",
                 k, k - 1, lamk, thr, MMK_NMF_RANK_MARGIN, MMK_PCA_TOL, lam0);
-  hipLaunchKernelGGL(nmf_vt_kernel, dim3((unsigned)((d * k + 255) / 256)), dim3(256), 0, st, (const double*)v, (const double*)ws.variance, d, k, nm1, ht, s);
-  MMK_HIP(hipGetLastError());
-  NF_DISPATCH(p.kp, hipLaunchKernelGGL((nmf_rows_kernel<KP, 1>), dim3((unsigned)p.nbw), dim3(kNfRows), 0, st, x, x_row_stride, n, d, k,
-                                       (const double*)ht, (const double*)s, w, (double*)nullptr, (const int32_t*)nullptr));
-  MMK_HIP(hipGetLastError());
+  MMK_TRY(launch(nmf_vt_kernel, dim3((unsigned)((d * k + 255) / 256)), dim3(256), 0, st, (const double*)v, (const double*)ws.variance, d, k, nm1, ht, s));
+  NF_DISPATCH(p.kp, MMK_TRY(launch(nmf_rows_kernel<KP, 1>, dim3((unsigned)p.nbw), dim3(kNfRows), 0, st, x, x_row_stride, n, d, k,
+                                   (const double*)ht, (const double*)s, w, (double*)nullptr, (const int32_t*)nullptr)));
   double* pu = ws.ppart;
   double* pv = ws.ppart + 2 * (size_t)k * p.gruns_n;
-  hipLaunchKernelGGL(nmf_partnorm_kernel, dim3((unsigned)p.gruns_n), dim3(256), 0, st, (const double*)w, n, k, p.grows_n, pu);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(nmf_partnorm_kernel, dim3((unsigned)p.gruns_d), dim3(256), 0, st, (const double*)ht, (int64_t)d, k, p.grows_d, pv);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(nmf_choose_kernel, dim3(1), dim3(64), 0, st, (const double*)pu, p.gruns_n, (const double*)pv, p.gruns_d, (const double*)s, k, ws.coef,
-                     part);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(nmf_init_kernel, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, st, w, n, k, 0, (const double*)ws.coef, (const int32_t*)part,
-                     (const double*)ws.stat);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(nmf_init_kernel, dim3((unsigned)(((int64_t)d * k + 255) / 256)), dim3(256), 0, st, ht, (int64_t)d, k, 1, (const double*)ws.coef,
-                     (const int32_t*)part, (const double*)ws.stat);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  MMK_TRY(launch(nmf_partnorm_kernel, dim3((unsigned)p.gruns_n), dim3(256), 0, st, (const double*)w, n, k, p.grows_n, pu));
+  MMK_TRY(launch(nmf_partnorm_kernel, dim3((unsigned)p.gruns_d), dim3(256), 0, st, (const double*)ht, (int64_t)d, k, p.grows_d, pv));
+  MMK_TRY(launch(nmf_choose_kernel, dim3(1), dim3(64), 0, st, (const double*)pu, p.gruns_n, (const double*)pv, p.gruns_d, (const double*)s, k, ws.coef,
+                 part));
+  MMK_TRY(launch(nmf_init_kernel, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, st, w, n, k, 0, (const double*)ws.coef, (const int32_t*)part,
+                 (const double*)ws.stat));
+  return launch(nmf_init_kernel, dim3((unsigned)(((int64_t)d * k + 255) / 256)), dim3(256), 0, st, ht, (int64_t)d, k, 1, (const double*)ws.coef,
+                (const int32_t*)part, (const double*)ws.stat);
 }
 
 extern "C" size_t mmk_nmf_half_workspace_bytes(int64_t n, int32_t d, int32_t k) {
@@ -666,10 +630,9 @@ static int nf_half_args(const char* who, const float* x, int64_t x_row_stride, i
   MMK_TRY(nf_check_shape(who, n, d, k));
   if (!x || !a || !b || !violation || !workspace || x_row_stride < 0)
     return fail(MMK_ERR_INVALID, "%s: bad arguments (null pointer or negative stride %lld)", who, (long long)x_row_stride);
-  if (nf_misaligned(x, 4) || nf_misaligned(a, 8) || nf_misaligned(b, 8) || nf_misaligned(violation, 8) || nf_misaligned(workspace, 8))
+  if (misaligned(x, 4) || misaligned(a, 8) || misaligned(b, 8) || misaligned(violation, 8) || misaligned(workspace, 8))
     return fail(MMK_ERR_INVALID, "%s: x must be 4-byte aligned, w, ht, violation and the workspace 8-byte aligned", who);
-  if (workspace_bytes < need) return fail(MMK_ERR_WORKSPACE, "%s: the workspace has %zu bytes, %zu are needed", who, workspace_bytes, need);
-  return MMK_OK;
+  return workspace_check(who, workspace, 8, workspace_bytes, need);
 }
 
 extern "C" int mmk_nmf_w_half_f64(const float* x, int64_t x_row_stride, int64_t n, int32_t d, int32_t k, const double* ht, double* w, double* violation,
@@ -680,9 +643,7 @@ extern "C" int mmk_nmf_w_half_f64(const float* x, int64_t x_row_stride, int64_t 
   const NfPlan p = nf_plan(n, d, k);
   const NfHalfWs ws = nf_half_ws(workspace, p, d, k);
   MMK_TRY(nf_w_half(x, x_row_stride, n, d, k, ht, w, p, ws, nullptr, st));
-  hipLaunchKernelGGL(nmf_check_kernel, dim3(1), dim3(64), 0, st, (const double*)ws.vpart, p.nbw, 0, 0.0, violation, (int32_t*)nullptr);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(nmf_check_kernel, dim3(1), dim3(64), 0, st, (const double*)ws.vpart, p.nbw, 0, 0.0, violation, (int32_t*)nullptr);
 }
 
 extern "C" int mmk_nmf_h_half_f64(const float* x, int64_t x_row_stride, int64_t n, int32_t d, int32_t k, const double* w, double* ht, double* violation,
@@ -693,9 +654,7 @@ extern "C" int mmk_nmf_h_half_f64(const float* x, int64_t x_row_stride, int64_t 
   const NfPlan p = nf_plan(n, d, k);
   const NfHalfWs ws = nf_half_ws(workspace, p, d, k);
   MMK_TRY(nf_h_half(x, x_row_stride, n, d, k, w, ht, p, ws, nullptr, st));
-  hipLaunchKernelGGL(nmf_check_kernel, dim3(1), dim3(64), 0, st, (const double*)(ws.vpart + p.nbw), p.nbh, 0, 0.0, violation, (int32_t*)nullptr);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(nmf_check_kernel, dim3(1), dim3(64), 0, st, (const double*)(ws.vpart + p.nbw), p.nbh, 0, 0.0, violation, (int32_t*)nullptr);
 }
 
 extern "C" size_t mmk_nmf_solve_workspace_bytes(int64_t n, int32_t d, int32_t k) {
@@ -733,8 +692,7 @@ extern "C" int mmk_nmf_solve_f64(const float* x, int64_t x_row_stride, int64_t n
     ++it;
     MMK_TRY(nf_w_half(x, x_row_stride, n, d, k, ht, w, p, ws, done, st));
     if (update_h) MMK_TRY(nf_h_half(x, x_row_stride, n, d, k, w, ht, p, ws, done, st));
-    hipLaunchKernelGGL(nmf_check_kernel, dim3(1), dim3(64), 0, st, (const double*)ws.vpart, update_h ? p.nbw + p.nbh : p.nbw, it, tol, stat, done);
-    MMK_HIP(hipGetLastError());
+    MMK_TRY(launch(nmf_check_kernel, dim3(1), dim3(64), 0, st, (const double*)ws.vpart, update_h ? p.nbw + p.nbh : p.nbw, it, tol, stat, done));
     if (it % every == 0 || it == max_iter) {
       MMK_HIP(hipMemcpyAsync(&host, stat, sizeof(host), hipMemcpyDeviceToHost, st));
       MMK_HIP(hipStreamSynchronize(st));

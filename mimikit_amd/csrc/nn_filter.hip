@@ -18,7 +18,7 @@
 //                mean: a float64 chain in rising slot order, one division, one rounding.
 //   Rows of 1025 floats are 4-byte aligned only: the loads and stores are one float per lane, 256 contiguous bytes per wave.
 // No atomics, no workgroup waits for another; out must not alias x.  NaN is not handled.
-#include "mmk_common.h"
+#include "entry_util.h"
 
 #include "../../include/mmk_nn_filter.h"
 
@@ -152,8 +152,6 @@ __global__ __launch_bounds__(64 * kNfWaves) void nn_aggregate_kernel(const float
   }
 }
 
-static inline bool nf_misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 }  // namespace mmk
 
 using namespace mmk;
@@ -168,22 +166,20 @@ extern "C" int mmk_nn_aggregate_f32(const float* x, int64_t x_row_stride, int64_
   if (!x || !index || !out || x_row_stride < 0 || (out_row_stride < d && n > 1))
     return fail(MMK_ERR_INVALID, "nn_aggregate: bad arguments (null pointer, x_row_stride %lld < 0 or out_row_stride %lld < d = %d)",
                 (long long)x_row_stride, (long long)out_row_stride, d);
-  if (nf_misaligned(x, 3) || nf_misaligned(out, 3) || nf_misaligned(count, 3)) return fail(MMK_ERR_INVALID, "nn_aggregate: x, out and count must be 4-byte aligned");
-  if (nf_misaligned(index, 7)) return fail(MMK_ERR_INVALID, "nn_aggregate: index must be 8-byte aligned");
+  if (misaligned(x, 4) || misaligned(out, 4) || misaligned(count, 4)) return fail(MMK_ERR_INVALID, "nn_aggregate: x, out and count must be 4-byte aligned");
+  if (misaligned(index, 8)) return fail(MMK_ERR_INVALID, "nn_aggregate: index must be 8-byte aligned");
   if (x == out) return fail(MMK_ERR_INVALID, "nn_aggregate: out must not alias x");
   const int64_t n_blocks = (n + kNfWaves - 1) / kNfWaves;
   if (n_blocks > 0x7fffffffLL) return fail(MMK_ERR_UNSUPPORTED, "nn_aggregate: %lld rows are more than one launch takes", (long long)n);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)n_blocks), block(64 * kNfWaves);
 #define NF_LAUNCH(OP) \
-  hipLaunchKernelGGL((nn_aggregate_kernel<OP>), grid, block, 0, st, x, x_row_stride, n, d, index, t, mutual, out, out_row_stride, count)
+  launch(nn_aggregate_kernel<OP>, grid, block, 0, st, x, x_row_stride, n, d, index, t, mutual, out, out_row_stride, count)
   switch (op) {
-    case MMK_NN_AGG_MEDIAN: NF_LAUNCH(MMK_NN_AGG_MEDIAN); break;
-    case MMK_NN_AGG_MEAN: NF_LAUNCH(MMK_NN_AGG_MEAN); break;
-    case MMK_NN_AGG_MAX: NF_LAUNCH(MMK_NN_AGG_MAX); break;
-    default: NF_LAUNCH(MMK_NN_AGG_MIN); break;
+    case MMK_NN_AGG_MEDIAN: return NF_LAUNCH(MMK_NN_AGG_MEDIAN);
+    case MMK_NN_AGG_MEAN: return NF_LAUNCH(MMK_NN_AGG_MEAN);
+    case MMK_NN_AGG_MAX: return NF_LAUNCH(MMK_NN_AGG_MAX);
+    default: return NF_LAUNCH(MMK_NN_AGG_MIN);
   }
 #undef NF_LAUNCH
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
 }

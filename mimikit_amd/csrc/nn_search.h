@@ -31,6 +31,7 @@
 // No atomics, no workgroup waits for another; every sum has one order, so two calls give the same bits.  NaN in the inputs is not handled
 // (> drops it silently; a key of -inf never enters a list).
 #pragma once
+#include "entry_util.h"
 #include "frame_walk.h"
 
 namespace mmk {
@@ -283,12 +284,9 @@ static int nn_search_launch(const char* who, const float* x, int64_t x_row_strid
     return fail(MMK_ERR_UNSUPPORTED, "%s: %lld rows against %lld frames are more than one launch takes", who, (long long)rows, (long long)m);
   float* ws_key = static_cast<float*>(workspace);
   int32_t* ws_idx = reinterpret_cast<int32_t*>(ws_key + rows * n_spans * t);
-  hipLaunchKernelGGL((nn_search_kernel<TC, kSelf, Key>), dim3((unsigned)grid), dim3(kNnThreads), 0, st, x, x_row_stride, qscale, rows, y, y_row_stride, kp, m, k, t,
-                     (int32_t)n_blocks, n_spans, ws_key, ws_idx);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(nn_merge_kernel<TC>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, ws_key, ws_idx, rows, t, n_spans, index, key);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  MMK_TRY(launch(nn_search_kernel<TC, kSelf, Key>, dim3((unsigned)grid), dim3(kNnThreads), 0, st, x, x_row_stride, qscale, rows, y, y_row_stride, kp, m, k, t,
+                 (int32_t)n_blocks, n_spans, ws_key, ws_idx));
+  return launch(nn_merge_kernel<TC>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, ws_key, ws_idx, rows, t, n_spans, index, key);
 }
 
 }  // namespace mmk

@@ -25,7 +25,7 @@
 //                         masks.  Lane N - 1 keeps its row's minimum and the first column that attains it (updates on < only).
 // No atomics, no workgroup waits for another, no scratch; every sum has one order, so results are the same from run to run.
 // NaN in the inputs is not handled (min and < drop it silently).
-#include "mmk_common.h"
+#include "entry_util.h"
 #include "wave_ops.h"
 
 namespace mmk {
@@ -233,15 +233,13 @@ extern "C" int mmk_inv_row_norm_f32(const float* x, int64_t x_batch_stride, int6
   if (batch < 1) return fail(MMK_ERR_INVALID, "inv_row_norm: batch = %d < 1", batch);
   if (rows < 1) return fail(MMK_ERR_INVALID, "inv_row_norm: rows = %lld < 1", (long long)rows);
   if (k < 1) return fail(MMK_ERR_INVALID, "inv_row_norm: k = %d < 1 (bins)", k);
-  if (!x || !inv_norm || x_batch_stride < 0 || x_row_stride < 0 || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(inv_norm)) & 3))
+  if (!x || !inv_norm || x_batch_stride < 0 || x_row_stride < 0 || misaligned(x, 4) || misaligned(inv_norm, 4))
     return fail(MMK_ERR_INVALID, "inv_row_norm: bad arguments (null or misaligned pointer, negative stride %lld / %lld)",
                 (long long)x_batch_stride, (long long)x_row_stride);
   const int64_t total = (int64_t)batch * rows;
   if ((total + 3) / 4 > 0x7fffffffLL) return fail(MMK_ERR_UNSUPPORTED, "inv_row_norm: %lld rows are more than one launch takes", (long long)total);
-  hipLaunchKernelGGL(inv_row_norm_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, x_batch_stride, x_row_stride,
-                     rows, total, k, inv_norm);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(inv_row_norm_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, x_batch_stride, x_row_stride, rows,
+                total, k, inv_norm);
 }
 
 extern "C" int mmk_cosine_cost_f32(const float* x, int64_t x_batch_stride, int64_t x_row_stride, const float* rx, int32_t batch, int32_t n,
@@ -252,21 +250,19 @@ extern "C" int mmk_cosine_cost_f32(const float* x, int64_t x_batch_stride, int64
   if (!x || !y || !rx || !ry || !cost || x_row_stride < 0 || y_row_stride < 0 || x_batch_stride < 0)
     return fail(MMK_ERR_INVALID, "cosine_cost: bad arguments (null pointer or negative stride %lld / %lld / %lld)", (long long)x_batch_stride,
                 (long long)x_row_stride, (long long)y_row_stride);
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(rx) | reinterpret_cast<uintptr_t>(ry)) & 3)
+  if (misaligned(x, 4) || misaligned(y, 4) || misaligned(rx, 4) || misaligned(ry, 4))
     return fail(MMK_ERR_INVALID, "cosine_cost: x, y, rx and ry must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(cost) & 15) return fail(MMK_ERR_INVALID, "cosine_cost: cost must be 16-byte aligned");
+  if (misaligned(cost, 16)) return fail(MMK_ERR_INVALID, "cosine_cost: cost must be 16-byte aligned");
   const int nt = (n + kNnnRowPad - 1) / kNnnRowPad;
   const int T = batch * nt;
   const dim3 grid((unsigned)((m + kCcJT - 1) / kCcJT)), wg(kCcThreads);
   hipStream_t st = (hipStream_t)stream;
 #define MMK_CC_LAUNCH(RT) \
-  hipLaunchKernelGGL(cosine_cost_kernel<RT>, grid, wg, 0, st, x, x_batch_stride, x_row_stride, rx, batch, n, nt, y, y_row_stride, ry, m, k, cost)
-  if (T <= 1) { MMK_CC_LAUNCH(1); }
-  else if (T <= 4) { MMK_CC_LAUNCH(4); }
-  else { MMK_CC_LAUNCH(16); }
+  launch(cosine_cost_kernel<RT>, grid, wg, 0, st, x, x_batch_stride, x_row_stride, rx, batch, n, nt, y, y_row_stride, ry, m, k, cost)
+  if (T <= 1) return MMK_CC_LAUNCH(1);
+  if (T <= 4) return MMK_CC_LAUNCH(4);
+  return MMK_CC_LAUNCH(16);
 #undef MMK_CC_LAUNCH
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
 }
 
 extern "C" int mmk_dtw_subseq_f32(const float* cost, int32_t batch, int32_t n, int64_t m, int64_t* end_col, float* end_val, float* last_row,
@@ -274,22 +270,20 @@ extern "C" int mmk_dtw_subseq_f32(const float* cost, int32_t batch, int32_t n, i
   using namespace mmk;
   MMK_TRY(nnn_sizes_check("dtw_subseq", batch, n, m, 1));
   if (!cost || !end_col || !end_val) return fail(MMK_ERR_INVALID, "dtw_subseq: cost, end_col and end_val must not be null");
-  if ((reinterpret_cast<uintptr_t>(cost) | reinterpret_cast<uintptr_t>(end_val) | reinterpret_cast<uintptr_t>(last_row)) & 3)
+  if (misaligned(cost, 4) || misaligned(end_val, 4) || misaligned(last_row, 4))
     return fail(MMK_ERR_INVALID, "dtw_subseq: cost, end_val and last_row must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(end_col) & 7) return fail(MMK_ERR_INVALID, "dtw_subseq: end_col must be 8-byte aligned");
+  if (misaligned(end_col, 8)) return fail(MMK_ERR_INVALID, "dtw_subseq: end_col must be 8-byte aligned");
   const int nt = (n + kNnnRowPad - 1) / kNnnRowPad;
   const dim3 grid((unsigned)batch), wg(64);
   hipStream_t st = (hipStream_t)stream;
-#define MMK_DTW_LAUNCH(NPAD)                                                                                              \
-  if (last_row) hipLaunchKernelGGL((dtw_subseq_kernel<NPAD, true>), grid, wg, 0, st, cost, n, (int32_t)m, end_col, end_val, last_row); \
-  else hipLaunchKernelGGL((dtw_subseq_kernel<NPAD, false>), grid, wg, 0, st, cost, n, (int32_t)m, end_col, end_val, last_row)
+#define MMK_DTW_LAUNCH(NPAD)                                                                                           \
+  last_row ? launch(dtw_subseq_kernel<NPAD, true>, grid, wg, 0, st, cost, n, (int32_t)m, end_col, end_val, last_row) \
+           : launch(dtw_subseq_kernel<NPAD, false>, grid, wg, 0, st, cost, n, (int32_t)m, end_col, end_val, last_row)
   switch (nt) {
-    case 1: MMK_DTW_LAUNCH(16); break;
-    case 2: MMK_DTW_LAUNCH(32); break;
-    case 3: MMK_DTW_LAUNCH(48); break;
-    default: MMK_DTW_LAUNCH(64); break;
+    case 1: return MMK_DTW_LAUNCH(16);
+    case 2: return MMK_DTW_LAUNCH(32);
+    case 3: return MMK_DTW_LAUNCH(48);
+    default: return MMK_DTW_LAUNCH(64);
   }
 #undef MMK_DTW_LAUNCH
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
 }

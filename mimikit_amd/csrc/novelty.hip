@@ -25,6 +25,7 @@
 //                         every higher-ranked candidate there is rejected.  The fixed point is the sequential walk's result, whatever the
 //                         order in which the threads read each other's decisions.
 // No atomics, no workgroup waits for another; every sum has one order, so two calls give the same bits.  NaN in the inputs is not handled.
+#include "entry_util.h"
 #include "frame_walk.h"
 #include "wave_ops.h"
 
@@ -313,9 +314,7 @@ template <int NB>
 static int novelty_launch(const float* x, int64_t bs, int64_t rs, const float* inv_norm, int32_t batch, int64_t frames, int32_t bins,
                           const NvHalves& hv, float* raw, hipStream_t st) {
   const int64_t tiles = (frames + kNvTile - 1) / kNvTile;
-  hipLaunchKernelGGL(novelty_kernel<NB>, dim3((unsigned)tiles, (unsigned)batch), dim3(kNvThreads), 0, st, x, bs, rs, inv_norm, frames, bins, hv, raw);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(novelty_kernel<NB>, dim3((unsigned)tiles, (unsigned)batch), dim3(kNvThreads), 0, st, x, bs, rs, inv_norm, frames, bins, hv, raw);
 }
 
 }  // namespace mmk
@@ -329,8 +328,7 @@ extern "C" int mmk_novelty_f32(const float* x, int64_t x_batch_stride, int64_t x
   if (!x || !halves || !raw || x_batch_stride < 0 || x_row_stride < 0)
     return fail(MMK_ERR_INVALID, "novelty: bad arguments (null pointer or negative stride %lld / %lld)", (long long)x_batch_stride,
                 (long long)x_row_stride);
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(inv_norm) | reinterpret_cast<uintptr_t>(raw)) & 3)
-    return fail(MMK_ERR_INVALID, "novelty: x, inv_norm and raw must be 4-byte aligned");
+  if (misaligned(x, 4) || misaligned(inv_norm, 4) || misaligned(raw, 4)) return fail(MMK_ERR_INVALID, "novelty: x, inv_norm and raw must be 4-byte aligned");
   if (n_half < 1) return fail(MMK_ERR_INVALID, "novelty: n_half = %d < 1 (half-widths)", n_half);
   if (n_half > kNvMaxKernels)
     return fail(MMK_ERR_UNSUPPORTED, "novelty: %d half-widths, more than the %d (MMK_NOVELTY_MAX_KERNELS) one launch sums", n_half, kNvMaxKernels);
@@ -366,9 +364,7 @@ extern "C" int mmk_novelty_finish_f32(const float* raw, int32_t batch, int32_t n
   if (n_half < 1) return fail(MMK_ERR_INVALID, "novelty_finish: n_half = %d < 1", n_half);
   if (n_half > kNvMaxKernels)
     return fail(MMK_ERR_UNSUPPORTED, "novelty_finish: %d half-widths, the limit is %d (MMK_NOVELTY_MAX_KERNELS)", n_half, kNvMaxKernels);
-  if (!raw || !scores || !dg || !workspace ||
-      ((reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(scores) | reinterpret_cast<uintptr_t>(dg) |
-        reinterpret_cast<uintptr_t>(workspace)) & 3))
+  if (!raw || !scores || !dg || !workspace || misaligned(raw, 4) || misaligned(scores, 4) || misaligned(dg, 4) || misaligned(workspace, 4))
     return fail(MMK_ERR_INVALID, "novelty_finish: bad arguments (null or misaligned pointer)");
   if (workspace_floats < mmk_novelty_finish_workspace_floats(batch, n_half, frames))
     return fail(MMK_ERR_WORKSPACE, "novelty_finish: the workspace has %zu floats, %zu are needed", workspace_floats,
@@ -377,12 +373,9 @@ extern "C" int mmk_novelty_finish_f32(const float* raw, int32_t batch, int32_t n
   if ((int64_t)batch * n_half > 65535 || n_chunks > 0x7fffffffLL || (frames + 255) / 256 > 0x7fffffffLL)
     return fail(MMK_ERR_UNSUPPORTED, "novelty_finish: %d clips of %lld frames are more than one launch takes", batch, (long long)frames);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(novelty_min_kernel, dim3((unsigned)n_chunks, (unsigned)(batch * n_half)), dim3(256), 0, st, raw, frames, (int32_t)n_chunks, workspace);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(novelty_finish_kernel, dim3((unsigned)((frames + 255) / 256), (unsigned)batch), dim3(256), 0, st, raw, frames, n_half,
-                     (int32_t)n_chunks, workspace, scores, dg);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  MMK_TRY(launch(novelty_min_kernel, dim3((unsigned)n_chunks, (unsigned)(batch * n_half)), dim3(256), 0, st, raw, frames, (int32_t)n_chunks, workspace));
+  return launch(novelty_finish_kernel, dim3((unsigned)((frames + 255) / 256), (unsigned)batch), dim3(256), 0, st, raw, frames, n_half,
+                (int32_t)n_chunks, workspace, scores, dg);
 }
 
 extern "C" size_t mmk_pick_peaks_workspace_bytes(int64_t n) { return n < 1 ? 0 : ((size_t)n + 2) * 4; }
@@ -398,19 +391,14 @@ extern "C" int mmk_pick_peaks_f32(const float* x, int64_t n, int32_t wait_before
     return fail(MMK_ERR_UNSUPPORTED, "pick_peaks: wait_before = %d, wait_after = %d, the limit is %d (MMK_NOVELTY_MAX_WAIT)", wait_before, wait_after,
                 MMK_NOVELTY_MAX_WAIT);
   if (!(min_strength == min_strength)) return fail(MMK_ERR_INVALID, "pick_peaks: min_strength is NaN");
-  if (!x || !picked || !workspace || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(workspace)) & 3))
+  if (!x || !picked || !workspace || misaligned(x, 4) || misaligned(workspace, 4))
     return fail(MMK_ERR_INVALID, "pick_peaks: bad arguments (null or misaligned pointer)");
-  if (workspace_bytes < mmk_pick_peaks_workspace_bytes(n))
-    return fail(MMK_ERR_WORKSPACE, "pick_peaks: the workspace has %zu bytes, %zu are needed", workspace_bytes, mmk_pick_peaks_workspace_bytes(n));
+  MMK_TRY(workspace_check("pick_peaks", workspace, 4, workspace_bytes, mmk_pick_peaks_workspace_bytes(n)));
   if ((n + 255) / 256 > 0x7fffffffLL) return fail(MMK_ERR_UNSUPPORTED, "pick_peaks: n = %lld is more than one launch takes", (long long)n);
   hipStream_t st = (hipStream_t)stream;
   float* mm = static_cast<float*>(workspace);
   int32_t* state = reinterpret_cast<int32_t*>(mm + 2);
-  hipLaunchKernelGGL(peaks_minmax_kernel, dim3(1), dim3(kPkThreads), 0, st, x, n, mm);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(peaks_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, n, wait_before, wait_after, min_strength, mm, state);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(peaks_suppress_kernel, dim3(1), dim3(kPkThreads), 0, st, x, n, wait_before, wait_after, state, picked);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  MMK_TRY(launch(peaks_minmax_kernel, dim3(1), dim3(kPkThreads), 0, st, x, n, mm));
+  MMK_TRY(launch(peaks_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, n, wait_before, wait_after, min_strength, mm, state));
+  return launch(peaks_suppress_kernel, dim3(1), dim3(kPkThreads), 0, st, x, n, wait_before, wait_after, state, picked);
 }

@@ -24,7 +24,8 @@
 //                         At the end each vector's sign makes its entry of largest magnitude (the first of equals) positive.
 //   projection            scores = ((y - mean) / scale) components^T, per (row, component) one fp64 fma chain over rising column, rounded to
 //                         fp32 once.
-#include "mmk_common.h"
+#include "entry_util.h"
+#include "wave_ops.h"
 
 #include <math.h>
 
@@ -213,19 +214,6 @@ __global__ __launch_bounds__(256) void pca_cov_reduce_kernel(const double* __res
 }
 
 // ---------------------------------------------------------------------------------------------------------------- eigenpairs
-// wave tree, then the waves' sums in rising order; every thread gets the sum.  `red` holds blockDim.x / 64 doubles
-__device__ __forceinline__ double pc_block_sum(double v, double* red) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  const int nw = blockDim.x >> 6;
-  __syncthreads();                                   // (red may still be read from the call before)
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < nw; ++w) s += red[w];
-  return s;
-}
-
 __global__ __launch_bounds__(256) void pca_start_kernel(int32_t d, int32_t b, double* __restrict__ y) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (int64_t)d * b) return;
@@ -243,7 +231,7 @@ __global__ __launch_bounds__(256) void pca_rowsum_kernel(const double* __restric
   __shared__ double red[4];
   double acc = 0.0;
   for (int j = threadIdx.x; j < d; j += 256) acc += fabs(c[(int64_t)blockIdx.x * d + j]);
-  acc = pc_block_sum(acc, red);
+  acc = block_sum(acc, red);
   if (threadIdx.x == 0) rowsum[blockIdx.x] = acc;
 }
 __global__ __launch_bounds__(64) void pca_cnorm_kernel(const double* __restrict__ rowsum, int32_t d, double* __restrict__ stat) {
@@ -272,7 +260,7 @@ __global__ __launch_bounds__(kPcWide) void pca_qr_kernel(int32_t d, int32_t b, d
       ss = fma(v, v, ss);
     }
     const double x0 = y[(int64_t)k * b + k];
-    ss = pc_block_sum(ss, red);
+    ss = block_sum(ss, red);
     const double nrm = sqrt(ss);
     double beta = 0.0, v0 = x0;
     if (nrm > 0.0) {
@@ -493,7 +481,7 @@ __global__ __launch_bounds__(256) void pca_resid_kernel(int32_t d, int32_t b, co
     const double r = fma(-th, q[(int64_t)i * b + k], y[(int64_t)i * b + k]);
     acc = fma(r, r, acc);
   }
-  acc = pc_block_sum(acc, red);
+  acc = block_sum(acc, red);
   if (threadIdx.x == 0) resid[k] = sqrt(acc);
 }
 
@@ -583,8 +571,6 @@ __global__ __launch_bounds__(256) void pca_project_kernel(const float* __restric
 
 static int pc_block(int32_t d, int32_t ncomp) { return d < ncomp + kPcExtra ? d : ncomp + kPcExtra; }
 
-static bool pc_misaligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(a - 1)) != 0; }
-
 }  // namespace mmk
 
 // ---------------------------------------------------------------------------------------------------------------- entry points
@@ -601,30 +587,21 @@ extern "C" int mmk_pca_colstats_f64(const float* x, int64_t x_row_stride, int64_
   if (d > MMK_PCA_MAX_D) return fail(MMK_ERR_UNSUPPORTED, "pca_colstats: d = %d columns, the limit is %d (MMK_PCA_MAX_D)", d, MMK_PCA_MAX_D);
   if (!x || !mean || !scale || !workspace || x_row_stride < 0)
     return fail(MMK_ERR_INVALID, "pca_colstats: bad arguments (null pointer or negative stride %lld)", (long long)x_row_stride);
-  if (pc_misaligned(x, 4) || pc_misaligned(mean, 8) || pc_misaligned(scale, 8) || pc_misaligned(workspace, 8))
+  if (misaligned(x, 4) || misaligned(mean, 8) || misaligned(scale, 8) || misaligned(workspace, 8))
     return fail(MMK_ERR_INVALID, "pca_colstats: x must be 4-byte aligned, mean, scale and the workspace 8-byte aligned");
-  if (workspace_bytes < mmk_pca_colstats_workspace_bytes(n, d))
-    return fail(MMK_ERR_WORKSPACE, "pca_colstats: the workspace has %zu bytes, %zu are needed", workspace_bytes,
-                mmk_pca_colstats_workspace_bytes(n, d));
+  MMK_TRY(workspace_check("pca_colstats", workspace, 8, workspace_bytes, mmk_pca_colstats_workspace_bytes(n, d)));
   hipStream_t st = (hipStream_t)stream;
   const int chunks = st_chunks(n);
   const int64_t rows_per_chunk = (n + chunks - 1) / chunks;
   double* mu = static_cast<double*>(workspace);
   double* partial = mu + d;
   const dim3 grid((unsigned)((d + 63) / 64), (unsigned)chunks), fin((unsigned)((d + 255) / 256)), wg(256);
-  hipLaunchKernelGGL(pca_colsum_kernel<0>, grid, wg, 0, st, x, x_row_stride, n, d, (const double*)nullptr, (const double*)nullptr, rows_per_chunk, partial);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(pca_colfin_kernel<0>, fin, wg, 0, st, partial, chunks, n, d, mu, scale, mean);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(pca_colsum_kernel<1>, grid, wg, 0, st, x, x_row_stride, n, d, mu, (const double*)nullptr, rows_per_chunk, partial);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(pca_colfin_kernel<1>, fin, wg, 0, st, partial, chunks, n, d, mu, scale, mean);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(pca_colsum_kernel<2>, grid, wg, 0, st, x, x_row_stride, n, d, mu, scale, rows_per_chunk, partial);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(pca_colfin_kernel<2>, fin, wg, 0, st, partial, chunks, n, d, mu, scale, mean);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  MMK_TRY(launch(pca_colsum_kernel<0>, grid, wg, 0, st, x, x_row_stride, n, d, (const double*)nullptr, (const double*)nullptr, rows_per_chunk, partial));
+  MMK_TRY(launch(pca_colfin_kernel<0>, fin, wg, 0, st, partial, chunks, n, d, mu, scale, mean));
+  MMK_TRY(launch(pca_colsum_kernel<1>, grid, wg, 0, st, x, x_row_stride, n, d, mu, (const double*)nullptr, rows_per_chunk, partial));
+  MMK_TRY(launch(pca_colfin_kernel<1>, fin, wg, 0, st, partial, chunks, n, d, mu, scale, mean));
+  MMK_TRY(launch(pca_colsum_kernel<2>, grid, wg, 0, st, x, x_row_stride, n, d, mu, scale, rows_per_chunk, partial));
+  return launch(pca_colfin_kernel<2>, fin, wg, 0, st, partial, chunks, n, d, mu, scale, mean);
 }
 
 extern "C" size_t mmk_pca_cov_workspace_bytes(int64_t n, int32_t d) {
@@ -641,20 +618,16 @@ extern "C" int mmk_pca_cov_f64(const float* x, int64_t x_row_stride, int64_t n, 
   if (d > MMK_PCA_MAX_D) return fail(MMK_ERR_UNSUPPORTED, "pca_cov: d = %d columns, the limit is %d (MMK_PCA_MAX_D)", d, MMK_PCA_MAX_D);
   if (!x || !mean || !scale || !c || !workspace || x_row_stride < 0)
     return fail(MMK_ERR_INVALID, "pca_cov: bad arguments (null pointer or negative stride %lld)", (long long)x_row_stride);
-  if (pc_misaligned(x, 4) || pc_misaligned(mean, 8) || pc_misaligned(scale, 8) || pc_misaligned(c, 8) || pc_misaligned(workspace, 8))
+  if (misaligned(x, 4) || misaligned(mean, 8) || misaligned(scale, 8) || misaligned(c, 8) || misaligned(workspace, 8))
     return fail(MMK_ERR_INVALID, "pca_cov: x must be 4-byte aligned, mean, scale, c and the workspace 8-byte aligned");
-  if (workspace_bytes < mmk_pca_cov_workspace_bytes(n, d))
-    return fail(MMK_ERR_WORKSPACE, "pca_cov: the workspace has %zu bytes, %zu are needed", workspace_bytes, mmk_pca_cov_workspace_bytes(n, d));
+  MMK_TRY(workspace_check("pca_cov", workspace, 8, workspace_bytes, mmk_pca_cov_workspace_bytes(n, d)));
   hipStream_t st = (hipStream_t)stream;
   const CvPlan p = cv_plan(n, d);
   double* partial = static_cast<double*>(workspace);
-  hipLaunchKernelGGL(pca_cov_kernel, dim3((unsigned)(p.pairs * p.runs)), dim3(256), 0, st, x, x_row_stride, n, d, mean, scale, p.rows_per_run, p.pairs,
-                     partial);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(pca_cov_reduce_kernel, dim3((unsigned)(p.pairs * (kCvTile * kCvTile / 256))), dim3(256), 0, st, partial, p.pairs, p.runs, d,
-                     (double)(n - 1), c);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  MMK_TRY(launch(pca_cov_kernel, dim3((unsigned)(p.pairs * p.runs)), dim3(256), 0, st, x, x_row_stride, n, d, mean, scale, p.rows_per_run, p.pairs,
+                 partial));
+  return launch(pca_cov_reduce_kernel, dim3((unsigned)(p.pairs * (kCvTile * kCvTile / 256))), dim3(256), 0, st, partial, p.pairs, p.runs, d,
+                (double)(n - 1), c);
 }
 
 extern "C" size_t mmk_pca_eig_workspace_bytes(int32_t d, int32_t n_components) {
@@ -675,11 +648,9 @@ extern "C" int mmk_pca_eig_f64(const double* c, int32_t d, int32_t n_components,
                 n_components, MMK_PCA_MAX_COMPONENTS);
   if (max_iter < 0) return fail(MMK_ERR_INVALID, "pca_eig: max_iter = %d < 0 (0: MMK_PCA_MAX_ITER)", max_iter);
   if (!c || !components || !variance || !n_iter || !workspace) return fail(MMK_ERR_INVALID, "pca_eig: bad arguments (null pointer)");
-  if (pc_misaligned(c, 8) || pc_misaligned(components, 8) || pc_misaligned(variance, 8) || pc_misaligned(workspace, 8))
+  if (misaligned(c, 8) || misaligned(components, 8) || misaligned(variance, 8) || misaligned(workspace, 8))
     return fail(MMK_ERR_INVALID, "pca_eig: c, components, variance and the workspace must be 8-byte aligned");
-  if (workspace_bytes < mmk_pca_eig_workspace_bytes(d, n_components))
-    return fail(MMK_ERR_WORKSPACE, "pca_eig: the workspace has %zu bytes, %zu are needed", workspace_bytes,
-                mmk_pca_eig_workspace_bytes(d, n_components));
+  MMK_TRY(workspace_check("pca_eig", workspace, 8, workspace_bytes, mmk_pca_eig_workspace_bytes(d, n_components)));
   hipStream_t st = (hipStream_t)stream;
   const int b = pc_block(d, n_components);
   const int cap = max_iter > 0 ? max_iter : MMK_PCA_MAX_ITER;
@@ -698,12 +669,9 @@ extern "C" int mmk_pca_eig_f64(const double* c, int32_t d, int32_t n_components,
   int32_t* done = reinterpret_cast<int32_t*>(stat + 2);
   const dim3 wg(256), wide(kPcWide), per_elem((unsigned)((db + 255) / 256));
   MMK_HIP(hipMemsetAsync(stat, 0, 4 * sizeof(double), st));
-  hipLaunchKernelGGL(pca_start_kernel, per_elem, wg, 0, st, d, b, y);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(pca_rowsum_kernel, dim3((unsigned)d), wg, 0, st, c, d, rowsum);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(pca_cnorm_kernel, dim3(1), dim3(64), 0, st, rowsum, d, stat);
-  MMK_HIP(hipGetLastError());
+  MMK_TRY(launch(pca_start_kernel, per_elem, wg, 0, st, d, b, y));
+  MMK_TRY(launch(pca_rowsum_kernel, dim3((unsigned)d), wg, 0, st, c, d, rowsum));
+  MMK_TRY(launch(pca_cnorm_kernel, dim3(1), dim3(64), 0, st, rowsum, d, stat));
   struct {
     double cnorm, resid;
     int32_t done, pad;
@@ -711,20 +679,13 @@ extern "C" int mmk_pca_eig_f64(const double* c, int32_t d, int32_t n_components,
   int it = 0;
   while (it < cap && !host.done) {
     ++it;
-    hipLaunchKernelGGL(pca_qr_kernel, dim3(1), wide, 0, st, d, b, y, qp, done);
-    MMK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(pca_cq_kernel, dim3((unsigned)((d + 15) / 16), (unsigned)((b + 15) / 16)), wg, 0, st, c, d, b, qp, z, done);
-    MMK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(pca_h_kernel, dim3((unsigned)b), wide, 0, st, d, b, qp, z, h, done);
-    MMK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(pca_jacobi_kernel, dim3(1), wide, 0, st, b, h, w, w2, theta, done);
-    MMK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(pca_rotate_kernel, per_elem, wg, 0, st, d, b, qp, z, w2, q, y, done);
-    MMK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(pca_resid_kernel, dim3((unsigned)n_components), wg, 0, st, d, b, q, y, theta, resid, done);
-    MMK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(pca_check_kernel, dim3(1), dim3(64), 0, st, n_components, it, resid, stat, done);
-    MMK_HIP(hipGetLastError());
+    MMK_TRY(launch(pca_qr_kernel, dim3(1), wide, 0, st, d, b, y, qp, done));
+    MMK_TRY(launch(pca_cq_kernel, dim3((unsigned)((d + 15) / 16), (unsigned)((b + 15) / 16)), wg, 0, st, c, d, b, qp, z, done));
+    MMK_TRY(launch(pca_h_kernel, dim3((unsigned)b), wide, 0, st, d, b, qp, z, h, done));
+    MMK_TRY(launch(pca_jacobi_kernel, dim3(1), wide, 0, st, b, h, w, w2, theta, done));
+    MMK_TRY(launch(pca_rotate_kernel, per_elem, wg, 0, st, d, b, qp, z, w2, q, y, done));
+    MMK_TRY(launch(pca_resid_kernel, dim3((unsigned)n_components), wg, 0, st, d, b, q, y, theta, resid, done));
+    MMK_TRY(launch(pca_check_kernel, dim3(1), dim3(64), 0, st, n_components, it, resid, stat, done));
     if (it % kPcPoll == 0 || it == cap) {
       MMK_HIP(hipMemcpyAsync(&host, stat, sizeof(host), hipMemcpyDeviceToHost, st));
       MMK_HIP(hipStreamSynchronize(st));
@@ -737,9 +698,7 @@ extern "C" int mmk_pca_eig_f64(const double* c, int32_t d, int32_t n_components,
                 "over the first %d of %d columns",
                 it, host.resid, kPcTol * host.cnorm, kPcTol, n_components, b);
   *n_iter = host.done;
-  hipLaunchKernelGGL(pca_finish_kernel, dim3((unsigned)n_components), wg, 0, st, d, b, q, theta, components, variance);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(pca_finish_kernel, dim3((unsigned)n_components), wg, 0, st, d, b, q, theta, components, variance);
 }
 
 extern "C" int mmk_pca_project_f32(const float* y, int64_t y_row_stride, int64_t m, int32_t d, const double* mean, const double* scale,
@@ -756,10 +715,8 @@ extern "C" int mmk_pca_project_f32(const float* y, int64_t y_row_stride, int64_t
   if (!y || !mean || !scale || !components || !out || y_row_stride < 0 || out_row_stride < n_components)
     return fail(MMK_ERR_INVALID, "pca_project: bad arguments (null pointer, negative stride %lld or an output stride %lld below n_components)",
                 (long long)y_row_stride, (long long)out_row_stride);
-  if (pc_misaligned(y, 4) || pc_misaligned(out, 4) || pc_misaligned(mean, 8) || pc_misaligned(scale, 8) || pc_misaligned(components, 8))
+  if (misaligned(y, 4) || misaligned(out, 4) || misaligned(mean, 8) || misaligned(scale, 8) || misaligned(components, 8))
     return fail(MMK_ERR_INVALID, "pca_project: y and out must be 4-byte aligned, mean, scale and components 8-byte aligned");
-  hipLaunchKernelGGL(pca_project_kernel, dim3((unsigned)((m + kPjRows - 1) / kPjRows)), dim3(256), 0, (hipStream_t)stream, y, y_row_stride, m, d, mean,
-                     scale, components, n_components, out, out_row_stride);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(pca_project_kernel, dim3((unsigned)((m + kPjRows - 1) / kPjRows)), dim3(256), 0, (hipStream_t)stream, y, y_row_stride, m, d, mean,
+                scale, components, n_components, out, out_row_stride);
 }

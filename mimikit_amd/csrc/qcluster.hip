@@ -59,16 +59,14 @@ extern "C" int mmk_nn_topk_f32(const float* x, int64_t x_row_stride, const float
   if (!x || !y || !qscale || !cscale || !cshift || !index || !key || !workspace || x_row_stride < 0 || y_row_stride < 0)
     return fail(MMK_ERR_INVALID, "nn_topk: bad arguments (null pointer or negative stride %lld / %lld)", (long long)x_row_stride,
                 (long long)y_row_stride);
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(qscale) | reinterpret_cast<uintptr_t>(cscale) |
-       reinterpret_cast<uintptr_t>(cshift) | reinterpret_cast<uintptr_t>(key) | reinterpret_cast<uintptr_t>(workspace)) & 3)
+  if (misaligned(x, 4) || misaligned(y, 4) || misaligned(qscale, 4) || misaligned(cscale, 4) || misaligned(cshift, 4) || misaligned(key, 4) ||
+      misaligned(workspace, 4))
     return fail(MMK_ERR_INVALID, "nn_topk: x, y, qscale, cscale, cshift, key and the workspace must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(index) & 7) return fail(MMK_ERR_INVALID, "nn_topk: index must be 8-byte aligned");
-  if (workspace_bytes < mmk_nn_topk_workspace_bytes(rows, m, t))
-    return fail(MMK_ERR_WORKSPACE, "nn_topk: the workspace has %zu bytes, %zu are needed", workspace_bytes,
-                mmk_nn_topk_workspace_bytes(rows, m, t));
+  if (misaligned(index, 8)) return fail(MMK_ERR_INVALID, "nn_topk: index must be 8-byte aligned");
+  MMK_TRY(workspace_check("nn_topk", workspace, 4, workspace_bytes, mmk_nn_topk_workspace_bytes(rows, m, t)));
   const bool self = self_exclude != 0;
-  const auto launch = t == 1 ? topk_launch<1>(self) : t <= 4 ? topk_launch<4>(self) : t <= 8 ? topk_launch<8>(self) : topk_launch<16>(self);
-  return launch("nn_topk", x, x_row_stride, qscale, rows, y, y_row_stride, NnAffineKey{cscale, cshift, key_min, key_max}, m, k, t,
+  const auto search = t == 1 ? topk_launch<1>(self) : t <= 4 ? topk_launch<4>(self) : t <= 8 ? topk_launch<8>(self) : topk_launch<16>(self);
+  return search("nn_topk", x, x_row_stride, qscale, rows, y, y_row_stride, NnAffineKey{cscale, cshift, key_min, key_max}, m, k, t,
                 index, key, workspace, (hipStream_t)stream);
 }
 
@@ -76,9 +74,7 @@ extern "C" int mmk_half_neg_sqnorm_f32(const float* y, int64_t y_row_stride, int
   using namespace mmk;
   if (rows < 1 || k < 1) return fail(MMK_ERR_INVALID, "half_neg_sqnorm: rows = %lld, k = %d (both at least 1)", (long long)rows, k);
   if ((rows + 3) / 4 > 0x7fffffffLL) return fail(MMK_ERR_UNSUPPORTED, "half_neg_sqnorm: %lld rows are more than one launch takes", (long long)rows);
-  if (!y || !out || y_row_stride < 0 || ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(out)) & 3))
+  if (!y || !out || y_row_stride < 0 || misaligned(y, 4) || misaligned(out, 4))
     return fail(MMK_ERR_INVALID, "half_neg_sqnorm: bad arguments (null or misaligned pointer, negative stride %lld)", (long long)y_row_stride);
-  hipLaunchKernelGGL(half_neg_sqnorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, y, y_row_stride, rows, k, out);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(half_neg_sqnorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, y, y_row_stride, rows, k, out);
 }

@@ -2,7 +2,7 @@
 // and evaluation), the attack / peak search of attack_decay and the scoring, side test, refinement and zero-crossing snap of
 // Samplifyer.fit - all from the per-frame spline coefficients (spline2.h); no T-long envelope or gradient is written by anything here
 // but the evaluation kernel, which exists for the callers that want one.
-#include "mmk_common.h"
+#include "entry_util.h"
 #include "spline2.h"
 #include "../../include/mmk_samplify.h"
 
@@ -325,8 +325,6 @@ __global__ __launch_bounds__(kGroup) void samplify_cuts_kernel(const float* __re
 }
 
 // ---- argument checks ------------------------------------------------------------------------------------------------------------------------
-static bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 static int spline_ok(const char* what, const void* coef, int64_t n) {
   if (!coef || misaligned(coef, 8)) return fail(MMK_ERR_INVALID, "%s: the coefficients must be a float64 device pointer, 8-byte aligned", what);
   if (n < 3) return fail(MMK_ERR_INVALID, "%s: a quadratic spline needs n >= 3 knots, got %lld", what, (long long)n);
@@ -352,10 +350,8 @@ extern "C" int mmk_spline2_coef_f64(const float* y, int64_t y_row_stride, int32_
   const int64_t n_tiles = (n + kSpTile - 1) / kSpTile;
   if (n_tiles * batch > 0x7fffffffLL)
     return fail(MMK_ERR_UNSUPPORTED, "spline2_coef: %lld tiles of %d knots are more than one launch takes", (long long)(n_tiles * batch), kSpTile);
-  hipLaunchKernelGGL(spline2_coef_kernel, dim3((unsigned)(n_tiles * batch)), dim3(kSpTile), 0, (hipStream_t)stream, y, y_row_stride, n, n_tiles, coef,
-                     coef_row_stride);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(spline2_coef_kernel, dim3((unsigned)(n_tiles * batch)), dim3(kSpTile), 0, (hipStream_t)stream, y, y_row_stride, n, n_tiles, coef,
+                coef_row_stride);
 }
 
 extern "C" int mmk_spline2_eval_f32(const double* coef, int64_t coef_row_stride, int32_t batch, int64_t n, float* out, int64_t out_row_stride,
@@ -370,10 +366,8 @@ extern "C" int mmk_spline2_eval_f32(const double* coef, int64_t coef_row_stride,
   if (batch > 65535) return fail(MMK_ERR_UNSUPPORTED, "spline2_eval: %d rows are more than one launch takes (65535)", batch);
   int64_t blocks = (n_out + MMK_SPLINE2_EVAL_TILE - 1) / MMK_SPLINE2_EVAL_TILE;
   blocks = blocks > 8192 ? 8192 : blocks;
-  hipLaunchKernelGGL(spline2_eval_kernel, dim3((unsigned)blocks, (unsigned)batch), dim3(MMK_SPLINE2_EVAL_TILE), 0, (hipStream_t)stream, coef,
-                     coef_row_stride, n, out, out_row_stride, n_out, linspace_step(n, n_out));
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(spline2_eval_kernel, dim3((unsigned)blocks, (unsigned)batch), dim3(MMK_SPLINE2_EVAL_TILE), 0, (hipStream_t)stream, coef,
+                coef_row_stride, n, out, out_row_stride, n_out, linspace_step(n, n_out));
 }
 
 extern "C" size_t mmk_periods_workspace_bytes(int64_t n_samples) {
@@ -402,15 +396,12 @@ extern "C" int mmk_periods_count_i64(const double* coef, int64_t n, const float*
   hipStream_t st = (hipStream_t)stream;
   const double step = coef ? linspace_step(n, n_samples) : 0.0;
   if (coef)
-    hipLaunchKernelGGL((periods_kernel<0, 0>), dim3((unsigned)n_tiles), dim3(256), 0, st, coef, n, row, n_samples, step, (int64_t*)work, (int64_t)0,
-                       (int64_t)0, (int64_t*)nullptr, (int64_t*)nullptr);
+    MMK_TRY(launch(periods_kernel<0, 0>, dim3((unsigned)n_tiles), dim3(256), 0, st, coef, n, row, n_samples, step, (int64_t*)work, (int64_t)0,
+                   (int64_t)0, (int64_t*)nullptr, (int64_t*)nullptr));
   else
-    hipLaunchKernelGGL((periods_kernel<0, 1>), dim3((unsigned)n_tiles), dim3(256), 0, st, coef, n, row, n_samples, step, (int64_t*)work, (int64_t)0,
-                       (int64_t)0, (int64_t*)nullptr, (int64_t*)nullptr);
-  MMK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(periods_scan_kernel, dim3(1), dim3(256), 0, st, (int64_t*)work, n_tiles, counts);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+    MMK_TRY(launch(periods_kernel<0, 1>, dim3((unsigned)n_tiles), dim3(256), 0, st, coef, n, row, n_samples, step, (int64_t*)work, (int64_t)0,
+                   (int64_t)0, (int64_t*)nullptr, (int64_t*)nullptr));
+  return launch(periods_scan_kernel, dim3(1), dim3(256), 0, st, (int64_t*)work, n_tiles, counts);
 }
 
 extern "C" int mmk_periods_fill_i64(const double* coef, int64_t n, const float* row, int64_t n_samples, const void* work, size_t work_bytes, int64_t n_att,
@@ -426,14 +417,11 @@ extern "C" int mmk_periods_fill_i64(const double* coef, int64_t n, const float* 
   hipStream_t st = (hipStream_t)stream;
   const double step = coef ? linspace_step(n, n_samples) : 0.0;
   const dim3 grid((unsigned)period_tiles(n_samples));
-  if (coef) hipLaunchKernelGGL((periods_kernel<1, 0>), grid, dim3(256), 0, st, coef, n, row, n_samples, step, (int64_t*)work, n_att, n_peak, att, peaks);
-  else hipLaunchKernelGGL((periods_kernel<1, 1>), grid, dim3(256), 0, st, coef, n, row, n_samples, step, (int64_t*)work, n_att, n_peak, att, peaks);
-  MMK_HIP(hipGetLastError());
-  if (n_att > 0) {
-    hipLaunchKernelGGL(periods_dec_kernel, dim3((unsigned)((n_att + 255) / 256)), dim3(256), 0, st, (const int64_t*)att, n_att, (const int64_t*)peaks, n_peak,
-                       n_samples, dec);
-    MMK_HIP(hipGetLastError());
-  }
+  if (coef) MMK_TRY(launch(periods_kernel<1, 0>, grid, dim3(256), 0, st, coef, n, row, n_samples, step, (int64_t*)work, n_att, n_peak, att, peaks));
+  else MMK_TRY(launch(periods_kernel<1, 1>, grid, dim3(256), 0, st, coef, n, row, n_samples, step, (int64_t*)work, n_att, n_peak, att, peaks));
+  if (n_att > 0)
+    MMK_TRY(launch(periods_dec_kernel, dim3((unsigned)((n_att + 255) / 256)), dim3(256), 0, st, (const int64_t*)att, n_att, (const int64_t*)peaks, n_peak,
+                   n_samples, dec));
   return MMK_OK;
 }
 
@@ -447,10 +435,8 @@ extern "C" int mmk_samplify_scores_f32(const double* env_coef, int64_t n, int64_
       misaligned(env_att, 4) || misaligned(env_dec, 4))
     return fail(MMK_ERR_INVALID, "samplify_scores: att / dec must be int64, scores / env_att / env_dec float32 and keep uint8 device pointers");
   if ((count + 255) / 256 > 0x7fffffffLL) return fail(MMK_ERR_UNSUPPORTED, "samplify_scores: count = %lld", (long long)count);
-  hipLaunchKernelGGL(samplify_scores_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, env_coef, n, n_samples,
-                     linspace_step(n, n_samples), att, dec, count, sensitivity, scores, env_att, env_dec, keep);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(samplify_scores_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, env_coef, n, n_samples,
+                linspace_step(n, n_samples), att, dec, count, sensitivity, scores, env_att, env_dec, keep);
 }
 
 extern "C" int mmk_samplify_cuts_i64(const float* y, int64_t n_samples, const double* const* env_coef, const double* const* grad_coef,
@@ -477,8 +463,6 @@ extern "C" int mmk_samplify_cuts_i64(const float* y, int64_t n_samples, const do
       misaligned(cuts, 8) || misaligned(lr_scores, 4))
     return fail(MMK_ERR_INVALID, "samplify_cuts: coarse_cuts / coarse_peaks / sides / cuts must be int64 device pointers, lr_scores float32 or NULL");
   if (count > 0x7fffffffLL) return fail(MMK_ERR_UNSUPPORTED, "samplify_cuts: count = %lld cuts are more than one launch takes", (long long)count);
-  hipLaunchKernelGGL(samplify_cuts_kernel, dim3((unsigned)count), dim3(kGroup), 0, (hipStream_t)stream, y, n_samples, lv, coarse_cuts, coarse_peaks, sides,
-                     lr_scores, cuts);
-  MMK_HIP(hipGetLastError());
-  return MMK_OK;
+  return launch(samplify_cuts_kernel, dim3((unsigned)count), dim3(kGroup), 0, (hipStream_t)stream, y, n_samples, lv, coarse_cuts, coarse_peaks, sides,
+                lr_scores, cuts);
 }

@@ -5,7 +5,9 @@
 //     the lane 32 further only;
 //   * filters.hip's lf_wave_scan is a scan that multiplies by powers;
 //   * sampler256.h's wave_max_dpp / wave_scan_dpp / wave_argmax_first go through the DPP rows and four scalar reads, where wave_max
-//     and wave_incl_scan go through ds_bpermute (and the scan adds in another order).
+//     and wave_incl_scan go through ds_bpermute (and the scan adds in another order);
+//   * beside block_sum: kmeans.hip's reduce_slabs is a tree in LDS and adds in another order, samplify.hip's block_scan_incl / block_max /
+//     block_arg are integer or argmax forms, and the Hillis-Steele scans of hcluster.hip and neighbors.hip differ from each other too.
 // The general class picker, still written out at five sites (wavenet_persist.hip, wavenet_chain.hip, srnn_bottom.hip twice,
 // srnn_resident.hip), uses the named moves and wave_max; its scan and its index butterflies are still its own loops: as shared calls they change
 // the instruction streams of those kernels (so does wave_max in srnn_resident.hip alone, which keeps that loop too).
@@ -105,6 +107,19 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
+}
+// float64 sum over the workgroup (pca.hip, nmf.hip): the same butterfly, then the waves' sums in rising order; every thread gets the sum.
+// `red` holds blockDim.x / 64 doubles
+__device__ __forceinline__ double block_sum(double v, double* red) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  const int nw = blockDim.x >> 6;
+  __syncthreads();                                   // (red may still be read from the call before)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int w = 0; w < nw; ++w) s += red[w];
+  return s;
 }
 // 1 / |row|_2 of K floats at p, 0 for a row of norm 0: lane l adds the squares of bins l, l + 64, ... in turn, the butterfly joins the lanes.
 // The whole of inv_row_norm_kernel (nnn.hip); novelty.hip calls it for the rows of a tile where the caller passes no norms.

@@ -381,6 +381,12 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _workspace(n_bytes: int, device) -> torch.Tensor:
+    """scratch for a ``*_workspace_bytes`` / ``*_workspace_floats`` entry point: at least ``n_bytes`` (never zero elements) of float64, which
+    the allocator hands out aligned far beyond the 8 bytes any of them asks for; the size passed on stays the one the library returned"""
+    return torch.empty((max((n_bytes + 7) // 8, 1),), dtype=torch.float64, device=device)
+
+
 # ---------------------------------------------------------------------------
 # feature functionals
 # ---------------------------------------------------------------------------
@@ -446,7 +452,7 @@ def lfilter1(x: torch.Tensor, b0: float, b1: float, a1: float) -> torch.Tensor:
     out = torch.empty((batch, n), dtype=torch.float32, device=x.device)
     if out.numel() == 0:
         return out.reshape(x.shape)
-    work = torch.empty((lib().mmk_lfilter1_workspace_floats(batch, n),), dtype=torch.float32, device=x.device) if a1 != 0 else None
+    work = _workspace(4 * lib().mmk_lfilter1_workspace_floats(batch, n), x.device) if a1 != 0 else None
     check(lib().mmk_lfilter1_f32(ptr(x2), x2.stride(0), batch, n, b0, b1, a1, ptr(out), out.stride(0), ptr(work), stream_ptr(x.device)),
           "mmk_lfilter1_f32")
     return out.reshape(x.shape)
@@ -461,7 +467,7 @@ def row_normalize(x: torch.Tensor, p: float, eps: float = 1e-12) -> torch.Tensor
     out = torch.empty((batch, n), dtype=torch.float32, device=x.device)
     if out.numel() == 0:
         return out.reshape(x.shape)
-    work = torch.empty((lib().mmk_row_normalize_workspace_floats(batch, n),), dtype=torch.float32, device=x.device)
+    work = _workspace(4 * lib().mmk_row_normalize_workspace_floats(batch, n), x.device)
     check(lib().mmk_row_normalize_f32(ptr(x2), x2.stride(0), batch, n, NORM_ORDERS[p], eps, ptr(out), out.stride(0), ptr(work),
                                       stream_ptr(x.device)), "mmk_row_normalize_f32")
     return out.reshape(x.shape)
@@ -573,7 +579,7 @@ def nn_cosine(x: torch.Tensor, corpus: torch.Tensor, corpus_inv_norm: torch.Tens
     index = torch.empty((rows,), dtype=torch.int64, device=x.device)
     best = torch.empty((rows,), dtype=torch.float32, device=x.device)
     n_work = lib().mmk_nn_cosine_workspace_bytes(rows, m)
-    work = torch.empty((n_work // 4,), dtype=torch.float32, device=x.device)
+    work = _workspace(n_work, x.device)
     check(lib().mmk_nn_cosine_f32(ptr(x), x.stride(0), ptr(rx), rows, ptr(y), y.stride(0), ptr(corpus_inv_norm), m, k, ptr(index), ptr(best),
                                   ptr(work), n_work, stream_ptr(x.device)), "mmk_nn_cosine_f32")
     return index, best
@@ -617,7 +623,7 @@ def nn_cosine_self(x: torch.Tensor, inv_norm: Optional[torch.Tensor] = None):
     index = torch.empty((rows,), dtype=torch.int64, device=x.device)
     best = torch.empty((rows,), dtype=torch.float32, device=x.device)
     n_work = lib().mmk_nn_cosine_workspace_bytes(rows, rows)
-    work = torch.empty((n_work // 4,), dtype=torch.float32, device=x.device)
+    work = _workspace(n_work, x.device)
     check(lib().mmk_nn_cosine_self_f32(ptr(x), x.stride(0), ptr(rx), rows, k, ptr(index), ptr(best), ptr(work), n_work, stream_ptr(x.device)),
           "mmk_nn_cosine_self_f32")
     return index, best
@@ -638,7 +644,7 @@ def nn_components(nearest: torch.Tensor):
     labels = torch.empty((n,), dtype=torch.int64, device=nearest.device)
     count = torch.empty((), dtype=torch.int64, device=nearest.device)
     n_work = lib().mmk_nn_components_workspace_bytes(n)
-    work = torch.empty((n_work // 4,), dtype=torch.int32, device=nearest.device)
+    work = _workspace(n_work, nearest.device)
     check(lib().mmk_nn_components_i64(ptr(nearest), n, ptr(labels), ptr(count), ptr(work), n_work, stream_ptr(nearest.device)),
           "mmk_nn_components_i64")
     return labels, count
@@ -708,7 +714,7 @@ def nn_topk(x: torch.Tensor, y: torch.Tensor, t: int, metric: str = "euclidean",
     index = torch.empty((rows, t), dtype=torch.int64, device=dev)
     key = torch.empty((rows, t), dtype=torch.float32, device=dev)
     n_work = lib().mmk_nn_topk_workspace_bytes(rows, m, t)
-    work = torch.empty((n_work // 4,), dtype=torch.float32, device=dev)
+    work = _workspace(n_work, dev)
     check(lib().mmk_nn_topk_f32(ptr(x), x.stride(0), ptr(qscale), rows, ptr(y), y.stride(0), ptr(cscale), ptr(cshift), lo, hi, m, k, t,
                                 1 if self_exclude else 0, ptr(index), ptr(key), ptr(work), n_work, stream_ptr(dev)), "mmk_nn_topk_f32")
     return index, key
@@ -733,7 +739,7 @@ def edge_components(src: torch.Tensor, dst: torch.Tensor, n: int):
     labels = torch.empty((n,), dtype=torch.int64, device=src.device)
     count = torch.empty((), dtype=torch.int64, device=src.device)
     n_work = lib().mmk_edge_components_workspace_bytes(n)
-    work = torch.empty((n_work // 4,), dtype=torch.int32, device=src.device)
+    work = _workspace(n_work, src.device)
     n_edges = src.shape[0]
     check(lib().mmk_edge_components_i64(ptr(src) if n_edges else None, ptr(dst) if n_edges else None, n_edges, n, ptr(labels), ptr(count),
                                         ptr(work), n_work, stream_ptr(src.device)), "mmk_edge_components_i64")
@@ -846,7 +852,7 @@ def kmeans_label_sums(x: torch.Tensor, offset: Optional[torch.Tensor], labels: t
         inertia = torch.empty((), dtype=torch.float64, device=dev)
         d2 = torch.empty((n,), dtype=torch.float64, device=dev) if row_d2 else None
     n_work = lib().mmk_kmeans_label_sums_workspace_bytes(n, d, k)
-    work = torch.empty((n_work // 8,), dtype=torch.float64, device=dev)
+    work = _workspace(n_work, dev)
     check(lib().mmk_kmeans_label_sums_f64(ptr(x), x.stride(0), ptr(offset), n, d, ptr(labels), k, ptr(sums), ptr(counts), ptr(centres), c_stride,
                                           ptr(d2), ptr(inertia), ptr(work), n_work, stream_ptr(dev)), "mmk_kmeans_label_sums_f64")
     return (sums, counts) if centres is None else (sums, counts, inertia, d2)
@@ -871,7 +877,7 @@ def kmeans_pp_step(x: torch.Tensor, offset: Optional[torch.Tensor], cand: torch.
         raise NotImplementedError(f"kmeans_pp_step: {t} candidates, the limit is {KMEANS_PP_MAX_TRIALS} (native.KMEANS_PP_MAX_TRIALS)")
     n_work = lib().mmk_kmeans_pp_step_workspace_bytes()
     if work is None:
-        work = torch.empty((n_work // 8,), dtype=torch.float64, device=x.device)
+        work = _workspace(n_work, x.device)
     check(lib().mmk_kmeans_pp_step_f64(ptr(x), x.stride(0), ptr(offset), n, d, ptr(cand), t, ptr(closest), ptr(pot), ptr(chosen), ptr(work),
                                        work.numel() * 8, stream_ptr(x.device)), "mmk_kmeans_pp_step_f64")
     return chosen
@@ -910,7 +916,7 @@ def pca_colstats(x: torch.Tensor):
     mean = torch.empty((d,), dtype=torch.float64, device=x.device)
     scale = torch.empty((d,), dtype=torch.float64, device=x.device)
     n_work = lib().mmk_pca_colstats_workspace_bytes(n, d)
-    work = torch.empty((n_work // 8,), dtype=torch.float64, device=x.device)
+    work = _workspace(n_work, x.device)
     check(lib().mmk_pca_colstats_f64(ptr(x), x.stride(0), n, d, ptr(mean), ptr(scale), ptr(work), n_work, stream_ptr(x.device)),
           "mmk_pca_colstats_f64")
     return mean, scale
@@ -926,7 +932,7 @@ def pca_cov(x: torch.Tensor, mean: torch.Tensor, scale: torch.Tensor) -> torch.T
     mean, scale = _f64_vector(mean, (d,), "pca_cov: mean"), _f64_vector(scale, (d,), "pca_cov: scale")
     c = torch.empty((d, d), dtype=torch.float64, device=x.device)
     n_work = lib().mmk_pca_cov_workspace_bytes(n, d)
-    work = torch.empty((n_work // 8,), dtype=torch.float64, device=x.device)
+    work = _workspace(n_work, x.device)
     check(lib().mmk_pca_cov_f64(ptr(x), x.stride(0), n, d, ptr(mean), ptr(scale), ptr(c), ptr(work), n_work, stream_ptr(x.device)),
           "mmk_pca_cov_f64")
     return c
@@ -946,7 +952,7 @@ def pca_eig(c: torch.Tensor, n_components: int, max_iter: int = 0):
     variance = torch.empty((n_components,), dtype=torch.float64, device=c.device)
     n_iter = i32(0)
     n_work = lib().mmk_pca_eig_workspace_bytes(d, n_components)
-    work = torch.empty((n_work // 8,), dtype=torch.float64, device=c.device)
+    work = _workspace(n_work, c.device)
     check(lib().mmk_pca_eig_f64(ptr(c), d, n_components, max_iter, ptr(components), ptr(variance), C.byref(n_iter), ptr(work), n_work,
                                 stream_ptr(c.device)), "mmk_pca_eig_f64")
     return components, variance, int(n_iter.value)
@@ -1001,10 +1007,6 @@ def _nmf_factor(t: torch.Tensor, shape, what: str) -> torch.Tensor:
     return _f64_vector(t, shape, what)
 
 
-def _nmf_work(n_bytes: int, device) -> torch.Tensor:
-    return torch.empty((max(n_bytes // 8, 1),), dtype=torch.float64, device=device)
-
-
 def nmf_start(x: torch.Tensor, n_components: int):
     """x (N >= 2, D) fp32 >= 0 -> (w (N, k), ht (D, k), s (k,), v (k, D)) fp64 on the device and part (k,) int32: sklearn's NNDSVDA start
     from the k leading eigenpairs of X^T X (mmk_nmf.h).  Waits for the stream.  ValueError for a negative entry and for n_components
@@ -1019,7 +1021,7 @@ def nmf_start(x: torch.Tensor, n_components: int):
     v = torch.empty((k, d), dtype=torch.float64, device=x.device)
     part = torch.empty((k,), dtype=torch.int32, device=x.device)
     n_work = lib().mmk_nmf_start_workspace_bytes(n, d, k)
-    work = _nmf_work(n_work, x.device)
+    work = _workspace(n_work, x.device)
     check(lib().mmk_nmf_start_f64(ptr(x), x.stride(0), n, d, k, ptr(w), ptr(ht), ptr(s), ptr(v), ptr(part), ptr(work), n_work, stream_ptr(x.device)),
           "mmk_nmf_start_f64")
     return w, ht, s, v, part
@@ -1031,7 +1033,7 @@ def _nmf_half(which: str, x: torch.Tensor, w: torch.Tensor, ht: torch.Tensor) ->
     w, ht = _nmf_factor(w, (n, k), f"nmf_{which}_half: w"), _nmf_factor(ht, (d, k), f"nmf_{which}_half: ht")
     violation = torch.empty((1,), dtype=torch.float64, device=x.device)
     n_work = lib().mmk_nmf_half_workspace_bytes(n, d, k)
-    work = _nmf_work(n_work, x.device)
+    work = _workspace(n_work, x.device)
     if which == "w":
         rc = lib().mmk_nmf_w_half_f64(ptr(x), x.stride(0), n, d, k, ptr(ht), ptr(w), ptr(violation), ptr(work), n_work, stream_ptr(x.device))
     else:
@@ -1062,7 +1064,7 @@ def nmf_solve(x: torch.Tensor, w: torch.Tensor, ht: torch.Tensor, update_h: bool
         raise ValueError(f"nmf_solve: max_iter = {max_iter} must be at least 1, poll = {poll} and tol = {tol} 0 or above")
     n_iter = i32(0)
     n_work = lib().mmk_nmf_solve_workspace_bytes(n, d, k)
-    work = _nmf_work(n_work, x.device)
+    work = _workspace(n_work, x.device)
     check(lib().mmk_nmf_solve_f64(ptr(x), x.stride(0), n, d, k, ptr(w), ptr(ht), 1 if update_h else 0, tol, max_iter, poll, 1 if check_nonneg else 0,
                                   C.byref(n_iter), ptr(work), n_work, stream_ptr(x.device)), "mmk_nmf_solve_f64")
     return int(n_iter.value)
@@ -1265,7 +1267,7 @@ def periods(coef: Optional[torch.Tensor], n_samples: int, row: Optional[torch.Te
         raise ValueError(f"periods: n_samples = {n_samples} < 1")
     dev = src.device
     n_work = lib().mmk_periods_workspace_bytes(n_samples)
-    work = torch.empty((n_work // 8,), dtype=torch.int64, device=dev)
+    work = _workspace(n_work, dev)
     counts = torch.empty((2,), dtype=torch.int64, device=dev)
     check(lib().mmk_periods_count_i64(ptr(coef), n, ptr(row), n_samples, ptr(counts), ptr(work), n_work, stream_ptr(dev)), "mmk_periods_count_i64")
     n_att, n_peak = (int(v) for v in counts.tolist())
@@ -1497,7 +1499,7 @@ def novelty_finish(raw: torch.Tensor):
     scores = torch.empty_like(r3)
     dg = torch.empty((batch, frames), dtype=torch.float32, device=raw.device)
     n_work = lib().mmk_novelty_finish_workspace_floats(batch, n_half, frames)
-    work = torch.empty((n_work,), dtype=torch.float32, device=raw.device)
+    work = _workspace(4 * n_work, raw.device)
     check(lib().mmk_novelty_finish_f32(ptr(r3), batch, n_half, frames, ptr(scores), ptr(dg), ptr(work), n_work, stream_ptr(raw.device)),
           "mmk_novelty_finish_f32")
     return (scores[0], dg[0]) if raw.dim() == 2 else (scores, dg)
@@ -1517,7 +1519,7 @@ def pick_peaks(x: torch.Tensor, wait_before: int, wait_after: int, min_strength:
     n = x.shape[0]
     picked = torch.empty((n,), dtype=torch.uint8, device=x.device)
     n_work = lib().mmk_pick_peaks_workspace_bytes(n)
-    work = torch.empty((n_work // 4,), dtype=torch.int32, device=x.device)
+    work = _workspace(n_work, x.device)
     check(lib().mmk_pick_peaks_f32(ptr(x), n, wait_before, wait_after, float(min_strength), ptr(picked), ptr(work), n_work, stream_ptr(x.device)),
           "mmk_pick_peaks_f32")
     return picked.bool()
