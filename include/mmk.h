@@ -12,6 +12,12 @@
  *     failure;
  *   - all data buffers are CALLER-OWNED DEVICE pointers (e.g. torch
  *     `tensor.data_ptr()`); sizes and strides are explicit, in ELEMENTS;
+ *   - strides.  Row, clip, frame and group strides and leading dimensions are honoured over the full 64-bit range: the kernels
+ *     compute their offsets in 64 bits, the logits copy-outs (`*_last_logits*`) included, so a view of a buffer of more than 4 GiB is
+ *     read and written where it lies.  One kernel addresses the caller's rows with a 32-bit byte offset: the Seq2Seq input projection
+ *     that reads continuous frames in place; it is taken only while the frames of a call span less than 2^31 bytes, and beyond that
+ *     the frames are gathered first.  tests/far_cases.py lists every stride parameter with the test that drives it beyond 4 GiB (only
+ *     mmk_wavenet_profile_steps has none, with its reason);
  *   - the library allocates no device memory: plans take a caller-provided
  *     workspace whose size is reported by `*_workspace_bytes`;
  *   - streams.  Every kernel, memset and copy of a call is enqueued on its `stream` argument (a `hipStream_t`, passed as void*; any

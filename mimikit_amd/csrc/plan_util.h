@@ -209,9 +209,9 @@ struct MlpHead {
   }
   // the n_out() columns of the last step's rows -> out (device memory)
   int copy_logits(float* out, int64_t out_ld, int64_t rows, hipStream_t st) const {
-    MMK_HIP(hipMemcpy2DAsync(out, (size_t)out_ld * sizeof(float), logits, (size_t)logits_ld * sizeof(float), (size_t)n_out() * sizeof(float),
-                             (size_t)rows, hipMemcpyDeviceToDevice, st));
-    return MMK_OK;
+    // (a kernel of ours, not the runtime's 2D copy: the caller's rows may lie any 64-bit leading dimension apart; `rows` is the plan's
+    //  max_batch x hop at the most - every caller has checked batch <= Bmax - and becomes the grid's x dimension)
+    return launch_copy_rows(addr_static(logits), logits_ld, addr_static(out), out_ld, (int)rows, n_out(), nullptr, 0, st);
   }
 };
 

@@ -1340,11 +1340,9 @@ extern "C" int mmk_wavenet_last_logits(mmk_wavenet_plan* p, int32_t batch, float
   if (p->cfg.head_kind != 0) return fail(MMK_ERR_UNSUPPORTED, "wavenet_last_logits: only for the MLP head");
   if (p->spipe || p->lpipe) {      // these kernels' head writes 256 classes + the temperature at column 256: the network's classes, then its temperature
     constexpr int PQ = mmk_wavenet_plan::kSpQ, PLD = mmk_wavenet_plan::kSpLogitsLd;
-    MMK_HIP(hipMemcpy2DAsync(out, ld * sizeof(float), p->sp_logits, PLD * sizeof(float), p->cfg.out_dim * sizeof(float), batch, hipMemcpyDeviceToDevice,
-                             (hipStream_t)stream));
+    MMK_TRY(launch_copy_rows(addr_static(p->sp_logits), PLD, addr_static(out), ld, batch, p->cfg.out_dim, nullptr, 0, (hipStream_t)stream));
     if (p->cfg.learn_temp)
-      MMK_HIP(hipMemcpy2DAsync(out + p->cfg.out_dim, ld * sizeof(float), p->sp_logits + PQ, PLD * sizeof(float), sizeof(float), batch,
-                               hipMemcpyDeviceToDevice, (hipStream_t)stream));
+      MMK_TRY(launch_copy_rows(addr_static(p->sp_logits + PQ), PLD, addr_static(out + p->cfg.out_dim), ld, batch, 1, nullptr, 0, (hipStream_t)stream));
     return MMK_OK;
   }
   return p->heads[0].copy_logits(out, ld, batch, (hipStream_t)stream);
