@@ -33,6 +33,9 @@ here:
   search of ``csrc/neighbors.hip`` and one gather-and-aggregate launch behind it (``native.nn_aggregate``, ``csrc/nn_filter.hip``).
 * ``NMF`` (:1141-1170), sklearn's non-negative matrix factorisation with its defaults: the NNDSVDA start from the PCA kernels' Gram
   matrix and eigenpairs, and the cyclic coordinate-descent solver with its stop rule on the device (``csrc/nmf.hip``).
+* ``AutoConvolve`` / ``F0Filter`` (:1007-1080), the two harmonic filters of a magnitude spectrogram: a float64 weight per bin (the log of
+  a product over neighbouring frames; overtone samples minus interpolated undertone samples), normalised over the frame and multiplied
+  onto the input, one launch each (``native.auto_convolve``, ``native.f0_filter``, ``csrc/spec_filter.hip``).
 * float64 tensors are computed in fp32 on the device (the kernels are fp32; the reference computes in the input's
   dtype, so float64 mu-law codes may differ from it for inputs within one fp32 ulp of a bin edge).
 """
@@ -50,7 +53,7 @@ from .item_spec import Frame, Sample, Unit, convert
 __all__ = [
     "Continuous", "Discrete", "Functional", "Identity", "Compose", "FileToSignal", "RemoveDC", "Normalize", "Emphasis", "Deemphasis",
     "MuLawCompress", "MuLawExpand", "STFT", "ISTFT", "MagSpec", "GLA", "Resample", "Envelop", "EnvelopBank", "Interpolate", "Derivative",
-    "PCA", "HarmonicSource", "PercussiveSource", "MelSpec", "MFCC", "NearestNeighborFilter", "NMF",
+    "PCA", "HarmonicSource", "PercussiveSource", "MelSpec", "MFCC", "NearestNeighborFilter", "NMF", "AutoConvolve", "F0Filter",
 ]
 
 N_FFT = 2048
@@ -1123,6 +1126,95 @@ class NearestNeighborFilter(Functional):
         x = x if x.stride(-1) == 1 or x.shape[-1] == 1 else x.contiguous()       # (nn_topk's self_exclude wants the very rows it is given)
         index, _ = native.nn_topk(x, x, min(int(self.n_neighbors), x.shape[0] - 1), self.metric, self_exclude=True)
         return native.nn_aggregate(x, index, self.aggregate, mutual=True)
+
+    @property
+    def inv(self) -> Functional:
+        return Identity()
+
+
+# ---------------------------------------------------------------------------
+# harmonic spectrogram filters
+# ---------------------------------------------------------------------------
+@dtc.dataclass
+class AutoConvolve(Functional):
+    """reference :1007-1036 on (T, F) or (B, T, F) non-negative float32 magnitudes on the device, one launch of ``native.auto_convolve``
+    (``csrc/spec_filter.hip``).  With k = ``window_size``, frame t is weighted over the frames t - k // 2 ... t - k // 2 + k - 1 of its
+    clip: p[t, b] is the float64 product of their values at bin b in rising frame order, a frame outside [0, T) counting as 1;
+    z = log(1.0 + p) (the rounded sum, not log1p); out = z / (sum_b z + 1e-8) * inputs.  An even k gives the lopsided window this
+    formula gives (k = 2: frames t - 1 and t).  Nothing of size k x T x F is written.
+
+    The reference builds its window with ``np.pad`` and ``librosa.feature.stack_memory(n_steps=k, delay=-1, constant_values=1)``; librosa
+    is not installed where this was written, and its part is restated from memory of the published source (block s of the stack at time
+    t' is padded[t' + s]).
+
+    Differences from the reference: the result is float32, rounded once from the float64 value (the reference returns float64); a batch
+    (B, T, F) is filtered clip by clip, the window never crosses a clip (the reference takes 2-D input only); ``window_size`` < 2 raises
+    ValueError (the reference's own slice ``[:, :-0]`` is empty at 1) and above ``native.AUTO_CONVOLVE_MAX_WINDOW`` (64)
+    NotImplementedError; at most ``native.SPEC_FILTER_MAX_BINS`` (4097) bins; NaN, negative or infinite bins are not looked for and
+    their results are unspecified."""
+    window_size: int = 3
+
+    @property
+    def unit(self) -> Optional[Unit]:
+        return None
+
+    @property
+    def elem_type(self) -> Optional[EventType]:
+        return None
+
+    def np_func(self, inputs):
+        raise NotImplementedError("the numpy (librosa) AutoConvolve belongs to dataset extraction; use the torch path on the HIP device")
+
+    def torch_func(self, inputs):
+        from .. import native
+        return native.auto_convolve(inputs, self.window_size)
+
+    @property
+    def inv(self) -> Functional:
+        return Identity()
+
+
+@dtc.dataclass
+class F0Filter(Functional):
+    """reference :1039-1080 on (T, F) or (B, T, F) non-negative float32 magnitudes on the device, one launch of ``native.f0_filter``
+    (``csrc/spec_filter.hip``).  The reference samples every frame z at the harmonics of its bins with ``librosa.interp_harmonics(z,
+    librosa.fft_frequencies(), harmonics)``, which is ``scipy.interpolate.interp1d(freqs, z, kind="linear", bounds_error=False,
+    fill_value=0)`` evaluated at h * freqs; librosa is not installed where this was written, and that part is restated from memory of the
+    published source.  The grid is uniform from 0, so harmonic h of bin b sits at bin position h * b whatever the sample rate, and the
+    device forms every index in integers:
+
+      sl[b]  = sum over h = 1 .. n_overtone - 1 of z[h b], a term counting only where h b <= F - 1 (0 beyond: ``fill_value``)
+      sl2[b] = sum over x = 2 .. n_undertone - 1 of z[lo] + (z[min(lo + 1, F - 1)] - z[lo]) * (r / x), lo = b // x, r = b % x
+      y = sl - sl2;  ``soft``: y+ = y where y > 0 else 0, otherwise y+ = 1 where y > 0 else 0;  ``normalize``: y+ /= sum_b y+ + 1e-8
+      out = inputs * y+
+
+    all in float64, rounded to float32 once.  ``n_overtone`` <= 1 makes sl zero and ``n_undertone`` <= 2 makes sl2 zero.
+
+    Differences from the reference: any F from 2 to ``native.SPEC_FILTER_MAX_BINS`` (4097) (the reference works at F = 1025 only, its grid
+    being the default one); the result is float32 (the reference returns float64); a batch (B, T, F) is filtered clip by clip (the
+    reference takes 2-D input only); at most ``native.F0_FILTER_MAX_OVERTONE`` / ``native.F0_FILTER_MAX_UNDERTONE`` (16 each); NaN,
+    negative or infinite bins are not looked for.  scipy does not compute exactly the definition above: it subtracts the two float32
+    knots in float32 before it goes to float64, and it may take an integer harmonic's knot as the upper end of [h b - 1, h b], returning
+    z[h b - 1] + fl32(difference) for z[h b].  The device evaluates the definition; DESIGN.md 5.6.14 bounds the gap."""
+    n_overtone: int = 4
+    n_undertone: int = 4
+    soft: bool = True
+    normalize: bool = True
+
+    @property
+    def unit(self) -> Optional[Unit]:
+        return None
+
+    @property
+    def elem_type(self) -> Optional[EventType]:
+        return None
+
+    def np_func(self, inputs):
+        raise NotImplementedError("the numpy (librosa) F0Filter belongs to dataset extraction; use the torch path on the HIP device")
+
+    def torch_func(self, inputs):
+        from .. import native
+        return native.f0_filter(inputs, self.n_overtone, self.n_undertone, self.soft, self.normalize)
 
     @property
     def inv(self) -> Functional:

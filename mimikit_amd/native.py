@@ -313,6 +313,14 @@ _SAMPLIFY_SIGNATURES = {
 
 SAMPLIFY_SYMBOLS = tuple(_SAMPLIFY_SIGNATURES)
 
+# include/mmk_spec_filter.h: the two harmonic spectrogram filters (AutoConvolve, F0Filter), a header and a table of their own like the four above
+_SPEC_FILTER_SIGNATURES = {
+    "mmk_auto_convolve_f32": (i32, [vp, i64, i64, i32, i32, i32, i32, vp, i64, i64, vp]),
+    "mmk_f0_filter_f32": (i32, [vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, vp, i64, i64, vp]),
+}
+
+SPEC_FILTER_SYMBOLS = tuple(_SPEC_FILTER_SIGNATURES)
+
 _lib = None
 
 
@@ -327,7 +335,8 @@ def load_library(path: Optional[str] = None):
             f"{path} is missing: build it with `python -m mimikit_amd.build` (hipcc, --offload-arch=gfx950). "
             "There is no CPU fallback for the generate path.")
     lib = C.CDLL(path)
-    for name, (res, args) in {**_SIGNATURES, **_KMEANS_SIGNATURES, **_NN_FILTER_SIGNATURES, **_NMF_SIGNATURES, **_SAMPLIFY_SIGNATURES}.items():
+    for name, (res, args) in {**_SIGNATURES, **_KMEANS_SIGNATURES, **_NN_FILTER_SIGNATURES, **_NMF_SIGNATURES, **_SAMPLIFY_SIGNATURES,
+                              **_SPEC_FILTER_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -780,6 +789,74 @@ def nn_aggregate(x: torch.Tensor, index: torch.Tensor, op: str = "median", mutua
     check(lib().mmk_nn_aggregate_f32(ptr(x), x.stride(0), n, k, ptr(index), t, 1 if mutual else 0, NN_AGGREGATES.index(op), ptr(out), out.stride(0),
                                      ptr(count), stream_ptr(x.device)), "mmk_nn_aggregate_f32")
     return (out, count) if return_count else out
+
+
+# include/mmk_spec_filter.h: MMK_SPEC_FILTER_* / MMK_AUTO_CONVOLVE_* / MMK_F0_FILTER_* - the bins of a frame a workgroup keeps in LDS beside
+# their float64 weights, the frames a workgroup takes in turn, the longest product window and the harmonic counts
+SPEC_FILTER_MAX_BINS = 4097
+SPEC_FILTER_TILE_FRAMES = 4
+AUTO_CONVOLVE_MAX_WINDOW = 64
+F0_FILTER_MAX_OVERTONE = 16
+F0_FILTER_MAX_UNDERTONE = 16
+
+
+def _spec_filter_input(s, who: str) -> torch.Tensor:
+    """the checks the two filters share, made on the host before a device is asked for -> (B, T, F) with bins contiguous"""
+    if not isinstance(s, torch.Tensor):
+        raise TypeError(f"{who}: expected a torch.Tensor, got {type(s)}")
+    if s.dtype != torch.float32:
+        raise TypeError(f"{who} runs in float32 on the HIP path, got {s.dtype}")
+    if s.dim() not in (2, 3):
+        raise ValueError(f"{who} takes (T, F) or (B, T, F), got shape {tuple(s.shape)}")
+    if min(s.shape) < 1 or s.shape[-1] < 2:
+        raise ValueError(f"{who}: at least one frame of at least 2 bins, got shape {tuple(s.shape)}")
+    if s.shape[-1] > SPEC_FILTER_MAX_BINS:
+        raise NotImplementedError(f"{who}: {s.shape[-1]} bins, the limit of the HIP path is {SPEC_FILTER_MAX_BINS} (native.SPEC_FILTER_MAX_BINS)")
+    require_device(s)
+    s3 = s if s.dim() == 3 else s.unsqueeze(0)
+    if s3.stride(2) != 1 or s3.stride(1) < 0 or s3.stride(0) < 0:
+        s3 = s3.contiguous()
+    return s3
+
+
+def auto_convolve(s: torch.Tensor, window_size: int = 3) -> torch.Tensor:
+    """s: (T, F) or (B, T, F) non-negative fp32 magnitudes, rows and clips at any stride -> fp32 of s's shape: the reference's AutoConvolve
+    (``mmk_auto_convolve_f32``, one launch on the current stream, no synchronisation, no workspace): per bin the float64 product over the
+    frames t - k // 2 ... t - k // 2 + k - 1 of the clip (1 outside it), log(1.0 + p), normalised over the frame, times s.
+    ``window_size`` < 2 raises ValueError (the reference's own slice is empty at 1), above AUTO_CONVOLVE_MAX_WINDOW NotImplementedError."""
+    k = int(window_size)
+    if k < 2:
+        raise ValueError(f"auto_convolve: window_size = {k}, at least 2 is needed")
+    if k > AUTO_CONVOLVE_MAX_WINDOW:
+        raise NotImplementedError(f"auto_convolve: window_size = {k}, the limit of the HIP path is {AUTO_CONVOLVE_MAX_WINDOW} "
+                                  "(native.AUTO_CONVOLVE_MAX_WINDOW)")
+    s3 = _spec_filter_input(s, "auto_convolve")
+    batch, frames, bins = s3.shape
+    out = torch.empty((batch, frames, bins), dtype=torch.float32, device=s.device)
+    check(lib().mmk_auto_convolve_f32(ptr(s3), s3.stride(0), s3.stride(1), batch, frames, bins, k, ptr(out), frames * bins, bins,
+                                      stream_ptr(s.device)), "mmk_auto_convolve_f32")
+    return out.reshape(s.shape)
+
+
+def f0_filter(s: torch.Tensor, n_overtone: int = 4, n_undertone: int = 4, soft: bool = True, normalize: bool = True) -> torch.Tensor:
+    """s: (T, F) or (B, T, F) non-negative fp32 magnitudes, rows and clips at any stride -> fp32 of s's shape: the reference's F0Filter on a
+    uniform frequency grid (``mmk_f0_filter_f32``, one launch on the current stream, no synchronisation, no workspace): per bin the float64
+    sum of the overtones z[h b], h < n_overtone, minus the interpolated undertones at b / x, 2 <= x < n_undertone; the positive part (or
+    its indicator without ``soft``), normalised over the frame with ``normalize``, times s.  Counts above F0_FILTER_MAX_OVERTONE /
+    F0_FILTER_MAX_UNDERTONE raise NotImplementedError, negative ones ValueError."""
+    n_over, n_under = int(n_overtone), int(n_undertone)
+    if n_over < 0 or n_under < 0:
+        raise ValueError(f"f0_filter: n_overtone = {n_over}, n_undertone = {n_under}: neither may be negative")
+    if n_over > F0_FILTER_MAX_OVERTONE or n_under > F0_FILTER_MAX_UNDERTONE:
+        raise NotImplementedError(f"f0_filter: n_overtone = {n_over}, n_undertone = {n_under}, the limits of the HIP path are "
+                                  f"{F0_FILTER_MAX_OVERTONE} (native.F0_FILTER_MAX_OVERTONE) and {F0_FILTER_MAX_UNDERTONE} "
+                                  "(native.F0_FILTER_MAX_UNDERTONE)")
+    s3 = _spec_filter_input(s, "f0_filter")
+    batch, frames, bins = s3.shape
+    out = torch.empty((batch, frames, bins), dtype=torch.float32, device=s.device)
+    check(lib().mmk_f0_filter_f32(ptr(s3), s3.stride(0), s3.stride(1), batch, frames, bins, n_over, n_under, 1 if soft else 0,
+                                  1 if normalize else 0, ptr(out), frames * bins, bins, stream_ptr(s.device)), "mmk_f0_filter_f32")
+    return out.reshape(s.shape)
 
 
 # include/mmk_kmeans.h: MMK_KMEANS_* - the centres of one assignment (the widest centre tile of csrc/kmeans.hip), the candidates of one
