@@ -35,7 +35,8 @@
  *       mmk_edge_components_i64: once per four rounds, to read its changed-flag;
  *       mmk_pca_eig_f64: every 8 iterations, to read its convergence flag;
  *       mmk_nmf_start_f64 and mmk_nmf_solve_f64 of mmk_nmf.h: the start inside mmk_pca_eig_f64 and once more for the smallest entry and
- *         the eigenvalues, the solver every 8 iterations (its `poll`) to read its convergence flag.
+ *         the eigenvalues, the solver every 8 iterations (its `poll`) to read its convergence flag;
+ *       mmk_fa_fit_f64 of mmk_factor_analysis.h: every 8 inner iterations, to read its state.
  *     Two more waits depend on what came before the call.  mmk_wavenet_warmup, mmk_wavenet_generate, mmk_srnn_warmup(_multi),
  *     mmk_srnn_generate(_multi) and mmk_tr_generate replay a cached graph of their step kernels from a block length on (16 steps; SampleRNN: two periods of
  *     frame_sizes[0]); the graph is keyed by the call's pointers, strides and phase, and a call whose key differs from the cached

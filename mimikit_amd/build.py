@@ -12,13 +12,14 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libmmk_hip.so")
-SOURCES = ["kernels.hip", "linear.hip", "gemm.hip", "skinny.hip", "features.hip", "filters.hip", "nnn.hip", "neighbors.hip", "hcluster.hip", "qcluster.hip", "kmeans.hip", "nn_filter.hip", "spec_filter.hip", "pca.hip", "nmf.hip", "envelope.hip", "samplify.hip", "hpss.hip", "melbank.hip", "novelty.hip", "wavenet_plan.hip", "wavenet_persist.hip", "wavenet_chain.hip", "wavenet_lpipe.hip", "wavenet_spipe.hip", "wavenet_bpipe.hip", "wavenet_prefill.hip", "srnn_plan.hip",
+SOURCES = ["kernels.hip", "linear.hip", "gemm.hip", "skinny.hip", "features.hip", "filters.hip", "nnn.hip", "neighbors.hip", "hcluster.hip", "qcluster.hip", "kmeans.hip", "nn_filter.hip", "spec_filter.hip", "pca.hip", "nmf.hip", "factor_analysis.hip", "envelope.hip", "samplify.hip", "hpss.hip", "melbank.hip", "novelty.hip", "wavenet_plan.hip", "wavenet_persist.hip", "wavenet_chain.hip", "wavenet_lpipe.hip", "wavenet_spipe.hip", "wavenet_bpipe.hip", "wavenet_prefill.hip", "srnn_plan.hip",
            "srnn_bottom.hip", "srnn_gru.hip", "srnn_resident.hip", "lstm_step.hip", "lstm_seq.hip", "lstm_inproj.hip", "istft.hip", "spectral2048.hip", "s2s_plan.hip",
            "transformer.hip", "transformer_plan.hip"]
 # every header under csrc/ (a header missing from a hand-kept list once left a stale library behind) + the C ABI
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) + [os.path.join("..", "..", "include", "mmk.h"), os.path.join("..", "..", "include", "mmk_kmeans.h"),
                                                                              os.path.join("..", "..", "include", "mmk_nn_filter.h"), os.path.join("..", "..", "include", "mmk_nmf.h"),
-                                                                             os.path.join("..", "..", "include", "mmk_samplify.h"), os.path.join("..", "..", "include", "mmk_spec_filter.h")]
+                                                                             os.path.join("..", "..", "include", "mmk_samplify.h"), os.path.join("..", "..", "include", "mmk_spec_filter.h"),
+                                                                             os.path.join("..", "..", "include", "mmk_factor_analysis.h")]
 ARCH = "gfx950"
 
 

@@ -36,6 +36,8 @@ here:
 * ``AutoConvolve`` / ``F0Filter`` (:1007-1080), the two harmonic filters of a magnitude spectrogram: a float64 weight per bin (the log of
   a product over neighbouring frames; overtone samples minus interpolated undertone samples), normalised over the frame and multiplied
   onto the input, one launch each (``native.auto_convolve``, ``native.f0_filter``, ``csrc/spec_filter.hip``).
+* ``FactorAnalysis`` (:1173-1203), sklearn's EM factor analysis in Gram form: one covariance pass by the PCA kernels, then the whole EM
+  loop on the device on the D x D matrix alone (``native.fa_fit``, ``csrc/factor_analysis.hip``), the scores by ``native.pca_project``.
 * float64 tensors are computed in fp32 on the device (the kernels are fp32; the reference computes in the input's
   dtype, so float64 mu-law codes may differ from it for inputs within one fp32 ulp of a bin edge).
 """
@@ -54,6 +56,7 @@ __all__ = [
     "Continuous", "Discrete", "Functional", "Identity", "Compose", "FileToSignal", "RemoveDC", "Normalize", "Emphasis", "Deemphasis",
     "MuLawCompress", "MuLawExpand", "STFT", "ISTFT", "MagSpec", "GLA", "Resample", "Envelop", "EnvelopBank", "Interpolate", "Derivative",
     "PCA", "HarmonicSource", "PercussiveSource", "MelSpec", "MFCC", "NearestNeighborFilter", "NMF", "AutoConvolve", "F0Filter",
+    "FactorAnalysis",
 ]
 
 N_FFT = 2048
@@ -998,6 +1001,110 @@ class NMF(Functional):
 
     def torch_func(self, inputs):
         return self.fit_transform(inputs)
+
+    @property
+    def inv(self) -> Functional:
+        return Identity()
+
+
+@dtc.dataclass
+class FactorAnalysis(Functional):
+    """reference :1173-1203: ``sklearn.decomposition.FactorAnalysis(n_components, tol=tol, max_iter=max_iter).fit_transform(x)`` for (N, D)
+    float32 frames on the device, computed in float64 (sklearn converts float32 frames itself) and returned as (N, n_components) float32
+    scores (``csrc/factor_analysis.hip``, ``include/mmk_factor_analysis.h``).  sklearn's EM in Gram form: per step it needs the k leading
+    singular values and right vectors of ``Xc / (sqrt(psi) sqrt(N))``, which are the k leading eigenpairs of ``S C S`` with
+    ``C = Xc^T Xc / N`` and ``S = diag(1 / (sqrt(psi) + 1e-12))`` - so the frames are read once:
+
+        native.pca_colstats          ``mean_``
+        native.pca_cov               C (scale 1), by v_mfma_f64_16x16x4_f64, times (N - 1) / N
+        native.fa_fit                the whole EM loop on the device: the PCA kernels' block subspace iteration on S C S, warm-started from
+                                     one EM step to the next, the log-likelihood, sklearn's stop ``ll - old < tol`` and the psi update
+        native.fa_transform_matrix   A = (I + Wpsi W^T)^-1 Wpsi by a Cholesky in one workgroup; ``transform`` is native.pca_project with A
+
+    ``torch_func`` / ``__call__`` are ``fit(x).transform(x)``, which is what sklearn's ``fit_transform`` is for this estimator.  ``fit``
+    stores ``mean_`` (D,), ``components_`` (n_components, D), ``noise_variance_`` (D,) and ``loglike_`` (n_iter_,) as float64 on the device
+    and ``n_iter_`` (int).  The sign of a component makes its entry of largest magnitude positive (PCA's rule; sklearn's own sign is an
+    artefact of its SVD).  ``random_seed`` is kept for the YAML form and unused: sklearn's seed enters its randomised SVD only, which
+    approximates exactly the eigenpairs computed here.
+
+    Known limit: where n_components exceeds the number of factors in the frames, S C S has no gap after its k-th eigenvalue (the noise
+    eigenvalues all sit near 1); the subspace iteration converges slowly there and may reach its cap (a RuntimeError naming the EM step
+    and the residual), and sklearn's own default (randomised) method does not reproduce its exact method there either.
+
+    ValueError: N < 2, n_components outside [1, min(N, D)].  NotImplementedError: D > ``native.PCA_MAX_D``, n_components >
+    ``native.PCA_MAX_COMPONENTS``.  Running out of ``max_iter`` warns (RuntimeWarning); then ``n_iter_ == max_iter`` and
+    ``noise_variance_`` is the psi updated after the last W, as sklearn's ``for ... else`` leaves it.  Not built: ``rotation``,
+    ``noise_variance_init``, ``score``, ``get_covariance``."""
+    n_components: int = 16
+    tol: float = 1e-2
+    max_iter: int = 1000
+    random_seed: int = 42
+
+    def __post_init__(self):
+        self.mean_: Optional[torch.Tensor] = None
+        self.components_: Optional[torch.Tensor] = None
+        self.noise_variance_: Optional[torch.Tensor] = None
+        self.loglike_: Optional[torch.Tensor] = None
+        self.n_iter_: Optional[int] = None
+        self._ones: Optional[torch.Tensor] = None
+        self._matrix: Optional[torch.Tensor] = None
+
+    @property
+    def unit(self) -> Optional[Unit]:
+        return None
+
+    @property
+    def elem_type(self) -> Optional[EventType]:
+        return None
+
+    def fit(self, x: torch.Tensor) -> "FactorAnalysis":
+        from .. import native
+        x = PCA._frames(x, "FactorAnalysis")
+        n, d = x.shape
+        k = int(self.n_components)
+        if int(self.max_iter) < 1 or not float(self.tol) >= 0.0:
+            raise ValueError(f"FactorAnalysis: max_iter = {self.max_iter} must be at least 1 and tol = {self.tol} 0 or above")
+        if n < 2:
+            raise ValueError(f"FactorAnalysis: N = {n} frames, at least 2 are needed")
+        if not 1 <= k <= min(n, d):
+            raise ValueError(f"FactorAnalysis: n_components = {k} must lie in [1, min(N, D) = {min(n, d)}]")
+        if d > native.PCA_MAX_D:
+            raise NotImplementedError(f"FactorAnalysis: D = {d} bins, the limit of the HIP path is {native.PCA_MAX_D} (native.PCA_MAX_D)")
+        if k > native.PCA_MAX_COMPONENTS:
+            raise NotImplementedError(f"FactorAnalysis: n_components = {k}, the limit of the HIP path is {native.PCA_MAX_COMPONENTS} "
+                                      "(native.PCA_MAX_COMPONENTS)")
+        native.require_device(x)
+        mean, _ = native.pca_colstats(x)
+        ones = torch.ones((d,), dtype=torch.float64, device=x.device)
+        c = native.pca_cov(x, mean, ones) * ((n - 1) / n)
+        components, noise, loglike, n_iter, converged, _ = native.fa_fit(c, n, k, self.tol, self.max_iter)
+        self.mean_, self.components_, self.noise_variance_, self.loglike_, self.n_iter_, self._ones = mean, components, noise, loglike, n_iter, ones
+        self._matrix = native.fa_transform_matrix(components, noise)
+        if not converged:
+            import warnings
+            warnings.warn(f"FactorAnalysis did not converge: maximum number of iterations {self.max_iter} reached. You might want to increase it.",
+                          RuntimeWarning)
+        return self
+
+    def transform(self, y: torch.Tensor) -> torch.Tensor:
+        from .. import native
+        if self.components_ is None:
+            raise RuntimeError("FactorAnalysis.transform before FactorAnalysis.fit")
+        y = PCA._frames(y, "FactorAnalysis.transform")
+        if y.shape[0] < 1 or y.shape[1] != self.mean_.shape[0]:
+            raise ValueError(f"FactorAnalysis.transform: y must be (M >= 1, D = {self.mean_.shape[0]}), got shape {tuple(y.shape)}")
+        native.require_device(y)
+        return native.pca_project(y, self.mean_, self._ones, self._matrix)
+
+    def fit_transform(self, x: torch.Tensor) -> torch.Tensor:
+        return self.fit(x).transform(x)
+
+    def np_func(self, inputs):
+        raise NotImplementedError("FactorAnalysis runs on device tensors only (csrc/factor_analysis.hip): pass a float32 tensor on the HIP "
+                                  "device; this package has no CPU path")
+
+    def torch_func(self, inputs):
+        return self.fit(inputs).transform(inputs)
 
     @property
     def inv(self) -> Functional:

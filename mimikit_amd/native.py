@@ -321,6 +321,16 @@ _SPEC_FILTER_SIGNATURES = {
 
 SPEC_FILTER_SYMBOLS = tuple(_SPEC_FILTER_SIGNATURES)
 
+# include/mmk_factor_analysis.h: the EM entry and the transform matrix of FactorAnalysis, a header and a table of their own like the five above
+_FACTOR_ANALYSIS_SIGNATURES = {
+    "mmk_fa_fit_workspace_bytes": (C.c_size_t, [i32, i32]),
+    "mmk_fa_fit_f64": (i32, [vp, i32, i32, i64, C.c_double, i32, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    "mmk_fa_transform_matrix_workspace_bytes": (C.c_size_t, [i32, i32]),
+    "mmk_fa_transform_matrix_f64": (i32, [vp, vp, i32, i32, vp, vp, C.c_size_t, vp]),
+}
+
+FACTOR_ANALYSIS_SYMBOLS = tuple(_FACTOR_ANALYSIS_SIGNATURES)
+
 _lib = None
 
 
@@ -336,7 +346,7 @@ def load_library(path: Optional[str] = None):
             "There is no CPU fallback for the generate path.")
     lib = C.CDLL(path)
     for name, (res, args) in {**_SIGNATURES, **_KMEANS_SIGNATURES, **_NN_FILTER_SIGNATURES, **_NMF_SIGNATURES, **_SAMPLIFY_SIGNATURES,
-                              **_SPEC_FILTER_SIGNATURES}.items():
+                              **_SPEC_FILTER_SIGNATURES, **_FACTOR_ANALYSIS_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -1145,6 +1155,61 @@ def nmf_solve(x: torch.Tensor, w: torch.Tensor, ht: torch.Tensor, update_h: bool
     check(lib().mmk_nmf_solve_f64(ptr(x), x.stride(0), n, d, k, ptr(w), ptr(ht), 1 if update_h else 0, tol, max_iter, poll, 1 if check_nonneg else 0,
                                   C.byref(n_iter), ptr(work), n_work, stream_ptr(x.device)), "mmk_nmf_solve_f64")
     return int(n_iter.value)
+
+
+# include/mmk_factor_analysis.h: MMK_FA_* - the PCA limits (the eigen step is the PCA kernels' subspace iteration), the host's read interval
+# and sklearn's SMALL
+FA_MAX_D = PCA_MAX_D
+FA_MAX_COMPONENTS = PCA_MAX_COMPONENTS
+FA_POLL = 8
+FA_SMALL = 1e-12
+
+
+def _fa_shape(d: int, k: int, what: str):
+    if d < 1 or not 1 <= k <= d:
+        raise ValueError(f"{what}: n_components = {k} must lie in [1, D = {d}]")
+    if d > FA_MAX_D:
+        raise NotImplementedError(f"{what}: D = {d} bins, the limit of the HIP path is {FA_MAX_D} (native.FA_MAX_D)")
+    if k > FA_MAX_COMPONENTS:
+        raise NotImplementedError(f"{what}: n_components = {k}, the limit of the HIP path is {FA_MAX_COMPONENTS} (native.FA_MAX_COMPONENTS)")
+
+
+def fa_fit(c: torch.Tensor, n: int, n_components: int, tol: float = 1e-2, max_iter: int = 1000):
+    """c (D, D) fp64 = Xc^T Xc / n of n frames -> (components (k, D), noise_variance (D,), loglike (n_iter,), n_iter, converged, (inner
+    iterations in all, those of EM step 0)): sklearn's FactorAnalysis EM in Gram form (mmk_factor_analysis.h), the whole loop on the
+    device.  The call waits for the stream every 8 inner iterations; an eigen step that does not converge raises NativeError"""
+    d = c.shape[0] if isinstance(c, torch.Tensor) and c.dim() == 2 else -1
+    c = _f64_vector(c, (d, d), "fa_fit: c")
+    n, k, tol, max_iter = int(n), int(n_components), float(tol), int(max_iter)
+    _fa_shape(d, k, "fa_fit")
+    if n < 2 or max_iter < 1 or not tol >= 0.0:
+        raise ValueError(f"fa_fit: n = {n} frames must be at least 2, max_iter = {max_iter} at least 1 and tol = {tol} 0 or above")
+    components = torch.empty((k, d), dtype=torch.float64, device=c.device)
+    noise = torch.empty((d,), dtype=torch.float64, device=c.device)
+    loglike = torch.empty((max_iter,), dtype=torch.float64, device=c.device)
+    n_iter, converged, inner = i32(0), i32(0), (i32 * 2)(0, 0)
+    n_work = lib().mmk_fa_fit_workspace_bytes(d, k)
+    work = _workspace(n_work, c.device)
+    check(lib().mmk_fa_fit_f64(ptr(c), d, k, n, tol, max_iter, ptr(components), ptr(noise), ptr(loglike), C.byref(n_iter), C.byref(converged), inner,
+                               ptr(work), n_work, stream_ptr(c.device)), "mmk_fa_fit_f64")
+    return components, noise, loglike[:int(n_iter.value)].clone(), int(n_iter.value), bool(converged.value), (int(inner[0]), int(inner[1]))
+
+
+def fa_transform_matrix(components: torch.Tensor, noise_variance: torch.Tensor) -> torch.Tensor:
+    """components (k, D), noise_variance (D,) fp64 -> A (k, D) fp64 = (I + Wpsi W^T)^-1 Wpsi, Wpsi = components / noise_variance: sklearn's
+    FactorAnalysis.transform is ``pca_project(y, mean_, ones, A)``.  A Cholesky of the k x k matrix in one workgroup; returns without waiting"""
+    if not isinstance(components, torch.Tensor) or components.dim() != 2:
+        raise TypeError("fa_transform_matrix: components must be a (k, D) float64 tensor")
+    k, d = components.shape
+    components = _f64_vector(components, (k, d), "fa_transform_matrix: components")
+    noise_variance = _f64_vector(noise_variance, (d,), "fa_transform_matrix: noise_variance")
+    _fa_shape(d, k, "fa_transform_matrix")
+    a = torch.empty((k, d), dtype=torch.float64, device=components.device)
+    n_work = lib().mmk_fa_transform_matrix_workspace_bytes(d, k)
+    work = _workspace(n_work, components.device)
+    check(lib().mmk_fa_transform_matrix_f64(ptr(components), ptr(noise_variance), d, k, ptr(a), ptr(work), n_work, stream_ptr(components.device)),
+          "mmk_fa_transform_matrix_f64")
+    return a
 
 
 def _rows(x: torch.Tensor) -> torch.Tensor:
