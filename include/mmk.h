@@ -43,6 +43,12 @@
  *     one waits for `stream` before it captures again (shorter blocks and repeated keys do not wait).  And the first spectral call
  *     of a process on a device (mmk_stft*_f32, mmk_istft_f32, mmk_gla_f32) builds the twiddle and window tables on its `stream` and
  *     waits for them once; later calls, on any stream, find them ready.
+ *     Graph capture.  Every stateless entry point that is not listed above can be captured into a graph on its `stream` (it allocates
+ *     nothing, queries nothing and copies nothing from the host) and replayed on other contents of the same buffers, with the workspace
+ *     as the last replay left it; the first spectral call of a process comes before the capture.  The plans' calls are not captured
+ *     from outside: they keep state on the host (the position, the graph cache and its key, the phase) and from that block length on
+ *     begin a capture of their own.  tests/graph_cases.py lists every entry point of the headers under include/ under one of the two
+ *     rules and tests/test_gpu_graphs.py replays the first kind.
  *     A plan is driven from ONE stream at a time: its workspace, queues and error word are ordered by that stream alone, and a
  *     caller who moves a plan to another stream synchronises the old one first.  The stateless functions keep nothing between
  *     calls but those tables: two of them may run on two streams at once, each with its own workspace;

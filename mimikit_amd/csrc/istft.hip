@@ -1447,13 +1447,17 @@ extern "C" int mmk_gla_f32(const float* mag, const float* init, int32_t batch, i
   const size_t bins = (size_t)n_fft / 2 + 1;
   const size_t spec_floats = 2 * (size_t)batch * n_frames * bins;
   const float m = momentum / (1.f + momentum);
-  auto fill_ones = [&](float* dst) -> int {                  // rand_init=False: every phase estimate starts at 1 + 0i
+  auto fill = [&](float* dst, float re) -> int {
     const int64_t n = (int64_t)batch * n_frames * (int64_t)bins;
     hipLaunchKernelGGL(fill_complex_kernel, dim3((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256)), dim3(256), 0, s, dst, n,
-                       cf32{1.f, 0.f});
+                       cf32{re, 0.f});
     MMK_HIP(hipGetLastError());
     return MMK_OK;
   };
+  auto fill_ones = [&](float* dst) -> int { return fill(dst, 1.f); };      // rand_init=False: every phase estimate starts at 1 + 0i
+  // the previous spectrum starts at zero - by a kernel like every other step of the call, not by hipMemsetAsync: the runtime's memset
+  // node writes a wrong pattern from the second launch of a captured graph on (tests/test_gpu_graphs.py: records)
+  auto fill_zeros = [&](float* dst) -> int { return fill(dst, 0.f); };
   if (n_fft == 1024 || n_fft == 2048) {
     // one launch per iteration: stft -> phase update -> istft fused per output segment (gla1024_iter_kernel / gla2048_iter_kernel)
     float* wave_a = work;
@@ -1467,7 +1471,7 @@ extern "C" int mmk_gla_f32(const float* mag, const float* init, int32_t batch, i
     }
     if (int rc = istft_any(angles0, mag, 2, batch, n_frames, n_fft, hop, nullptr, n_iter ? wave_a : out, s)) return rc;
     if (!n_iter) return MMK_OK;
-    MMK_HIP(hipMemsetAsync(tprev_a, 0, spec_floats * sizeof(float), s));
+    if (int rc = fill_zeros(tprev_a)) return rc;
     int seg_hops = 0, segs_per_clip = 0;
     int64_t total_tasks = 0;
     dim3 grid(1), block(64 * kIstftWaves);
@@ -1509,7 +1513,7 @@ extern "C" int mmk_gla_f32(const float* mag, const float* init, int32_t batch, i
   float* frames = tprev + spec_floats;
   if (init) MMK_HIP(hipMemcpyAsync(angles, init, spec_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
   else if (int rc = fill_ones(angles)) return rc;
-  MMK_HIP(hipMemsetAsync(tprev, 0, spec_floats * sizeof(float), s));
+  if (int rc = fill_zeros(tprev)) return rc;
   for (int it = 0; it < n_iter; ++it) {
     if (int rc = istft_any(angles, mag, 2, batch, n_frames, n_fft, hop, frames, wave, s)) return rc;
     if (int rc = stft_any(wave, n_out, batch, n_out, n_fft, hop, 1, 1, 3, angles, tprev, m, s)) return rc;

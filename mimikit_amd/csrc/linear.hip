@@ -401,7 +401,9 @@ extern "C" int mmk_fingerprint_buffers_u32(const void* const* buffers, const int
                                            mmk_stream_t stream) {
   using namespace mmk;
   if (!out || n_buffers < 0 || (n_buffers > 0 && (!buffers || !n_words))) return fail(MMK_ERR_INVALID, "fingerprint: bad arguments");
-  MMK_HIP(hipMemsetAsync(out, 0, sizeof(uint64_t), (hipStream_t)stream));
+  // (a kernel, not hipMemsetAsync: the runtime's memset node writes a wrong pattern from the second launch of a captured graph on -
+  // tests/test_gpu_graphs.py: records - and every stateless entry point can be captured, include/mmk.h)
+  MMK_TRY(launch_set_i64(reinterpret_cast<int64_t*>(out), 0, (hipStream_t)stream));
   uint64_t pos = 0;
   for (int first = 0; first < n_buffers; first += kFpMaxBuffers) {
     FingerprintArgs a = {};
@@ -445,7 +447,7 @@ extern "C" int mmk_pack_weight_f32(const float* w, int64_t ldw, int32_t n_rows, 
   using namespace mmk;
   if (!w || !packed || n_rows <= 0 || k_cols <= 0) return fail(MMK_ERR_INVALID, "pack_weight: bad arguments");
   hipStream_t st = (hipStream_t)stream;
-  MMK_HIP(hipMemsetAsync(packed, 0, packed_floats(n_rows, k_cols) * sizeof(float), st));
+  MMK_TRY(launch_fill(packed, 0.f, packed_floats(n_rows, k_cols), st));      // (the padding; a kernel, not a memset: see mmk_fingerprint_buffers_u32)
   return pack_rect(packed, (k_cols + 15) / 16, 0, 1, n_rows, 0, k_cols, w, ldw, 1, st);
 }
 

@@ -958,14 +958,16 @@ class Bound:
             assert rc == 0, (case.id, "setup", rc, self.L.mmk_last_error())
         torch.cuda.synchronize()
 
-    def fill(self, which):
-        """put the real or the stale inputs in place, clear the outputs and the workspaces (default stream)"""
+    def fill(self, which, keep_work=False):
+        """put the real or the stale inputs in place, clear the outputs and the workspaces (default stream); keep_work: leave the workspaces
+        as the previous call left them (tests/graph_cases.py: what a replayed graph finds)"""
         for k, v in (self.real if which == "real" else self.stale).items():
             self.inp[k].copy_(v)
         for k, b in self.bufs.items():
             b.fill_(_FILL[b.dtype])
-        for w in self.work.values():
-            w.zero_()
+        if not keep_work:
+            for w in self.work.values():
+                w.zero_()
 
     def late_copy(self):
         for k, v in self.real.items():
