@@ -40,7 +40,8 @@ BIG_SELF_CASE = (2 * SPAN + 3, 33)        # the diagonal crosses tile, query-blo
 COPIES = ((127, 128), (2047, 2048))       # exact copies across a tile / query-block edge and across a span edge
 ZERO_ROW = 1000
 MEAN_KS = (1, 33, 1025)
-MEAN_SEGMENTS = (2, 3, 700)
+MEAN_SEGMENTS = (2, 3, 700, 1)            # (the last: a segment of one member, whose mean is the row)
+ONE_ROW = (1,)                            # the whole input is one row in one segment
 DEFECTS = ("self_allowed", "last_tie", "mean_of_frames", "number_by_cycle", "no_relabel")
 
 
@@ -226,14 +227,14 @@ def big_self_case():
 
 # ---------------------------------------------------------------------------------------------------------------- segment mean
 @functools.lru_cache(maxsize=None)
-def mean_case(k):
-    """x (n, k) signed float32, order (a seeded permutation of the rows), offsets of segments of MEAN_SEGMENTS members, the float64 means
+def mean_case(k, sizes=MEAN_SEGMENTS):
+    """x (n, k) signed float32, order (a seeded permutation of the rows), offsets of segments of `sizes` members, the float64 means
     (taken in the order given) and their bound"""
     rng = np.random.default_rng(8100 + k)
-    n = sum(MEAN_SEGMENTS)
+    n = sum(sizes)
     x = (rng.standard_normal((n, k)) * np.exp(rng.uniform(-3, 3, (n, 1)))).astype(np.float32)
     order = rng.permutation(n).astype(np.int64)
-    offsets = np.concatenate([[0], np.cumsum(MEAN_SEGMENTS)]).astype(np.int64)
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     x64 = x.astype(np.float64)
     want = np.stack([x64[order[a:b]].mean(0) for a, b in zip(offsets[:-1], offsets[1:])])
     mag = np.stack([np.abs(x64[order[a:b]]).mean(0) for a, b in zip(offsets[:-1], offsets[1:])])

@@ -36,7 +36,7 @@ GOLDEN_OPS = ("median", "mean", "max")
 DEFECTS = ("one_sided", "self_included", "lower_median", "upper_median", "empty_row_zero", "k_plus_two", "mean_over_slots", "empty_slot_as_row0")
 
 # the kernel cases: host-drawn lists, independent of the search
-NS = (2, 3, 5, 129)                            # one wave of a workgroup, three, two workgroups, 33 workgroups with a tail
+NS = (1, 2, 3, 5, 129)                         # a single row (every slot empty), one wave of a workgroup, three, two workgroups, 33 workgroups with a tail
 DS = (1, 63, 64, 65, 257)                      # below, at and past one lane stride; past two steps of 128 bins
 TS = (1, 2, 15, TOPK_MAX)
 

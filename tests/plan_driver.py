@@ -36,17 +36,19 @@ def logits_into(case, plan, clips, out, target=0):
     return out
 
 
-def generate(case, device, what, net=None, blocks_before=0, warmups=1, after_block=None):
+def generate(case, device, what, net=None, blocks_before=0, warmups=1, after_block=None, place=None):
     """the blocks of the case - or of a net_refs.Life of it - on the device -> (history on the host, the outputs the device hands back: (clips,
     compared steps, columns)).  net: the network to run it on (its plan may have generated before: `blocks_before` generate blocks, and
     `warmups` generations with a warm-up of whole periods, this one included - what case.ran counts); None: a fresh one.
-    after_block(plan): called after every block, behind its checks"""
+    after_block(plan): called after every block, behind its checks.  place(host tensor, 'data' | 'cond') -> the device tensor the plan is
+    given for it, a view of a wider buffer for one (tests/test_gpu_strided_inputs.py); None: a contiguous copy"""
+    place = place or (lambda x, role: x.to(device))
     net = case.make()[0].to(device) if net is None else net
     prompt, conds = case.inputs()
     B, P, n, hop = case.clips, case.P, case.n, case.hop or 1
-    conds_d = tuple(c.to(device) for c in conds)
+    conds_d = tuple(place(c, "cond") for c in conds)
     # one tensor per class stream (or the one of frames): the prompt and blanks - a stream no target feeds is given for the whole length
-    data = tuple(torch.cat([p, torch.zeros(B, P + n - p.size(1), *p.shape[2:], dtype=p.dtype)], 1).to(device) for p in R.streams(prompt))
+    data = tuple(place(torch.cat([p, torch.zeros(B, P + n - p.size(1), *p.shape[2:], dtype=p.dtype)], 1), "data") for p in R.streams(prompt))
     if case.kind in ("srnn", "s2s", "s2s_classes"):
         net.before_generate(tuple(x[:, :P] for x in data), None)
         if case.kind == "srnn" and "MMK_SRNN_RESIDENT_WARMUP" in case.env:

@@ -44,7 +44,8 @@ METRICS = ("euclidean", "cosine")
 SELF_ROWS = (2, 3, 50, 129)
 SELF_KS = (1, 33, 64)
 TS = (1, 2, 9, TOPK_MAX)
-CROSS_CASES = ((200, 5, 33), (200, 131, 33))      # (queries, corpus frames, bins) without self_exclude
+# (queries, corpus frames, bins) without self_exclude; the last three: one query row, one corpus frame, one of each with one bin
+CROSS_CASES = ((200, 5, 33), (200, 131, 33), (1, 131, 33), (200, 1, 33), (1, 1, 1))
 BIG_CASE = (2 * SPAN + 3, 33)
 COPIES = ((127, 128), (2047, 2048))               # exact copies across a tile / query-block edge and across a span edge
 ZERO_ROW = 1000

@@ -12,37 +12,13 @@ from mimikit_amd import native
 from mimikit_amd.features.functionals import Derivative, Envelop, EnvelopBank, Interpolate, MagSpec
 from tests import envelope_refs as R
 from tests.f64_bounds import check_written
+from tests.strided_inputs import FLOAT_SURROUNDS, PAD, Strided, surround_rule
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
 G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "envelope.npz"))
-PAD = 7                                   # row stride = n + PAD: the rows of one call differ in alignment
 OFFSETS = ((1, 3), (3, 0))                # element offsets of the first row of x and of y in their buffers
-
-
-class Rows:
-    """(batch, n) rows inside a longer buffer: row stride n + PAD, first row `offset` elements in"""
-
-    def __init__(self, batch, n, offset, device, fill):
-        self.batch, self.n, self.offset, self.stride = batch, n, offset, n + PAD
-        self.buf = torch.full((offset + batch * self.stride + 5,), fill, dtype=torch.float32, device=device)
-        self.view = self.buf.as_strided((batch, n), (self.stride, 1), offset)
-
-    @classmethod
-    def of(cls, x_np, offset, device):
-        r = cls(x_np.shape[0], x_np.shape[1], offset, device, 0.0)
-        r.view.copy_(torch.from_numpy(x_np.copy()))
-        return r
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + 4 * self.offset
-
-    def mask(self):
-        m = torch.zeros(self.buf.shape, dtype=torch.bool)
-        m.as_strided((self.batch, self.n), (self.stride, 1), self.offset).fill_(True)
-        return m
 
 
 def same_bits(a, b):
@@ -50,10 +26,11 @@ def same_bits(a, b):
 
 
 # ------------------------------------------------------------------------------------------------------------------------ energy
-def energy_call(x_np, n_fft, hop, center, reflect, x_off, device):
+@surround_rule(*FLOAT_SURROUNDS)
+def energy_call(x_np, n_fft, hop, center, reflect, x_off, device, pad=PAD):
     batch, n = x_np.shape
     frames = R.n_frames(n, n_fft, hop, center)
-    x = Rows.of(x_np, x_off, device)
+    x = Strided.of(x_np, x_off, device, row_stride=n + pad)
     out = torch.full((batch * frames + 9,), float("nan"), dtype=torch.float32, device=device)
     native.check(native.lib().mmk_stft_energy_f32(x.ptr, x.stride, batch, n, n_fft, hop, center, reflect, out.data_ptr(), native.stream_ptr(device)))
     mask = torch.zeros(out.shape, dtype=torch.bool)
@@ -74,6 +51,8 @@ def test_stft_energy_against_the_bound(device, n_fft):
             worst = max(worst, R.assert_inside(got, want[:batch], bound[:batch], what))
             again, _, _ = energy_call(R.case_input(n)[:batch], n_fft, hop, center, reflect, x_off, device)
             assert same_bits(again, out), f"{what}: two calls differ"
+            if batch > 1:                     # rows end to end: a window that leaves a row meets the next row's samples
+                assert same_bits(energy_call(R.case_input(n)[:batch], n_fft, hop, center, reflect, x_off, device, pad=0)[0], out), f"{what}: rows end to end"
     print(f"stft_energy n_fft {n_fft}: worst error / bound {worst:.3f}")
 
 
@@ -88,9 +67,10 @@ def test_stft_energy_is_the_sum_of_the_spectrogram(device):
 
 
 # ----------------------------------------------------------------------------------------------------------------- interpolation
+@surround_rule(*FLOAT_SURROUNDS)
 def interp_call(x_np, n_out, mode, align, x_off, y_off, device):
     batch, n = x_np.shape
-    x, y = Rows.of(x_np, x_off, device), Rows(batch, n_out, y_off, device, float("nan"))
+    x, y = Strided.of(x_np, x_off, device), Strided((batch, n_out), y_off, device, float("nan"))
     native.check(native.lib().mmk_interp1d_f32(x.ptr, x.stride, batch, n, y.ptr, y.stride, n_out, native.INTERP_MODES[mode], align,
                                                native.stream_ptr(device)))
     return y
@@ -129,9 +109,10 @@ def test_interp1d_previous_at_exact_knots(device):
 
 
 # -------------------------------------------------------------------------------------------------------------------- derivative
-def derivative_call(x_np, L, x_off, y_off, device):
+@surround_rule(*FLOAT_SURROUNDS)
+def derivative_call(x_np, L, x_off, y_off, device, pad=PAD):
     batch, n = x_np.shape
-    x, y = Rows.of(x_np, x_off, device), Rows(batch, n, y_off, device, float("nan"))
+    x, y = Strided.of(x_np, x_off, device, row_stride=n + pad), Strided((batch, n), y_off, device, float("nan"))
     native.check(native.lib().mmk_derivative_f32(x.ptr, x.stride, batch, n, L, y.ptr, y.stride, native.stream_ptr(device)))
     return y
 
@@ -147,6 +128,9 @@ def test_derivative_against_the_bound(device, L, n):
             y = derivative_call(x[:batch], L, x_off, y_off, device)
             check_written(y.buf, y.mask(), what)
             worst = max(worst, R.assert_inside(y.view.cpu().numpy(), want[:batch], bound[:batch], what))
+            if batch > 1:                     # rows end to end: a lag that leaves a row meets the row before it
+                packed = derivative_call(x[:batch], L, x_off, y_off, device, pad=0)
+                assert same_bits(packed.view.contiguous(), y.view.contiguous()), f"{what}: rows end to end"
     print(f"derivative max_lag {L}, n {n}: worst error / bound {worst:.3f}")
 
 

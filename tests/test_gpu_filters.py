@@ -14,45 +14,27 @@ from oracle.weights import load_recipe
 from tests import filter_refs as R
 from tests import helpers as H
 from tests.f64_bounds import check_written
+from tests.strided_inputs import FLOAT_SURROUNDS, Strided, surround_rule
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
-PAD = 7                                   # row stride = n + PAD: odd or even with n, so the rows of one call differ in alignment
 OFFSETS = ((1, 3), (3, 0))                # element offsets of the first row of x and of y in their buffers
 
 
-class Rows:
-    """(batch, n) rows inside a longer buffer: row stride n + PAD, first row `offset` elements in"""
-
-    def __init__(self, batch, n, offset, device, fill):
-        self.batch, self.n, self.offset, self.stride = batch, n, offset, n + PAD
-        self.buf = torch.full((offset + batch * self.stride + 5,), fill, dtype=torch.float32, device=device)
-        self.view = self.buf.as_strided((batch, n), (self.stride, 1), offset)
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + 4 * self.offset
-
-    def mask(self):
-        m = torch.zeros(self.buf.shape, dtype=torch.bool)
-        m.as_strided((self.batch, self.n), (self.stride, 1), self.offset).fill_(True)
-        return m
-
-
+@surround_rule(*FLOAT_SURROUNDS)
 def lfilter1_rows(x_np, coeffs, x_off, y_off, device):
     batch, n = x_np.shape
-    x, y = Rows(batch, n, x_off, device, 0.0), Rows(batch, n, y_off, device, float("nan"))
-    x.view.copy_(torch.from_numpy(x_np.copy()))
+    x, y = Strided.of(x_np, x_off, device), Strided((batch, n), y_off, device, float("nan"))
     work = torch.empty((max(1, native.lib().mmk_lfilter1_workspace_floats(batch, n)),), dtype=torch.float32, device=device)
     native.check(native.lib().mmk_lfilter1_f32(x.ptr, x.stride, batch, n, *coeffs, y.ptr, y.stride, work.data_ptr(), native.stream_ptr(device)))
     return y
 
 
+@surround_rule(*FLOAT_SURROUNDS)
 def normalize_rows(x_np, p, x_off, y_off, device):
     batch, n = x_np.shape
-    x, y = Rows(batch, n, x_off, device, 0.0), Rows(batch, n, y_off, device, float("nan"))
-    x.view.copy_(torch.from_numpy(x_np.copy()))
+    x, y = Strided.of(x_np, x_off, device), Strided((batch, n), y_off, device, float("nan"))
     work = torch.empty((native.lib().mmk_row_normalize_workspace_floats(batch, n),), dtype=torch.float32, device=device)
     native.check(native.lib().mmk_row_normalize_f32(x.ptr, x.stride, batch, n, native.NORM_ORDERS[p], R.EPS, y.ptr, y.stride, work.data_ptr(),
                                                     native.stream_ptr(device)))

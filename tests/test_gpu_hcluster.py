@@ -13,38 +13,14 @@ from mimikit_amd import native
 from tests import hcluster_refs as H
 from tests import neighbors_refs as NR
 from tests.f64_bounds import check_written
+from tests.strided_inputs import FLOAT_SURROUNDS, INT_SURROUNDS, MONOTONE, Strided, surround_rule
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
 G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "clusters.npz"))
-PAD = 7                                   # row stride = k + PAD: the rows of one call differ in alignment
 SPAN = native.NN_SPAN
 POISON = -7
-
-
-class Rows:
-    """(batch, n) float32 rows inside a longer buffer: row stride n + PAD, first row `offset` elements in"""
-
-    def __init__(self, batch, n, offset, device, fill):
-        self.batch, self.n, self.offset, self.stride = batch, n, offset, n + PAD
-        self.buf = torch.full((offset + batch * self.stride + 5,), fill, dtype=torch.float32, device=device)
-        self.view = self.buf.as_strided((batch, n), (self.stride, 1), offset)
-
-    @classmethod
-    def of(cls, x_np, offset, device):
-        r = cls(x_np.shape[0], x_np.shape[1], offset, device, 0.0)
-        r.view.copy_(torch.from_numpy(x_np.copy()))
-        return r
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + 4 * self.offset
-
-    def mask(self):
-        m = torch.zeros(self.buf.shape, dtype=torch.bool)
-        m.as_strided((self.batch, self.n), (self.stride, 1), self.offset).fill_(True)
-        return m
 
 
 def same_bits(a, b):
@@ -52,11 +28,12 @@ def same_bits(a, b):
 
 
 # ------------------------------------------------------------------------------------------------------------------ self arg-max kernel
+@surround_rule(*FLOAT_SURROUNDS)
 def self_call(x_np, device, x_off=1):
     """mmk_nn_cosine_self_f32 on strided, misaligned rows; outputs and workspace NaN-filled (the index buffer holds -1)"""
     rows, k = x_np.shape
     lib = native.lib()
-    x = Rows.of(x_np, x_off, device)
+    x = Strided.of(x_np, x_off, device)
     rx = native.inv_row_norm(x.view)
     n_work = lib.mmk_nn_cosine_workspace_bytes(rows, rows)
     assert 0 < n_work <= rows * -(-rows // SPAN) * 16 + 4096
@@ -114,10 +91,11 @@ def test_self_argmax_of_zero_rows(device):
 
 
 # ------------------------------------------------------------------------------------------------------------------ components kernel
+@surround_rule(*INT_SURROUNDS)
 def components_call(nearest_np, device):
     n = nearest_np.shape[0]
     lib = native.lib()
-    nearest = torch.from_numpy(nearest_np.copy()).to(device)
+    nearest = Strided.of(nearest_np.reshape(1, n), 4, device, row_stride=n, decoy=(0, n)).view[0]      # (a contiguous list between decoy frames)
     n_work = lib.mmk_nn_components_workspace_bytes(n)
     work = torch.full((n_work // 4 + 3,), POISON, dtype=torch.int32, device=device)
     labels = torch.full((n + 4,), POISON, dtype=torch.int64, device=device)
@@ -150,24 +128,35 @@ def test_components_python_wrapper(device):
 
 
 # ------------------------------------------------------------------------------------------------------------------ segment mean
+@surround_rule(*FLOAT_SURROUNDS)
+def mean_call(x_np, order_np, offsets_np, device):
+    """mmk_segment_mean_f32 on strided, misaligned rows; order and offsets are contiguous lists with decoys (frames of the case, the first
+    and the last offset) in front and behind"""
+    (n, k), segments = x_np.shape, offsets_np.shape[0] - 1
+    x = Strided.of(x_np, 3, device)
+    order = Strided.of(order_np[None], 4, device, row_stride=n, decoy=(0, n))
+    offsets = Strided.of(offsets_np[None], 4, device, row_stride=segments + 1, decoy=MONOTONE)
+    out = Strided((segments, k), 1, device, float("nan"))
+    native.check(native.lib().mmk_segment_mean_f32(x.ptr, x.stride, n, k, order.ptr, offsets.ptr, segments, out.ptr, out.stride,
+                                                   native.stream_ptr(device)))
+    check_written(out.buf, out.mask(), f"segment means, k {k}")
+    return out.view.clone()
+
+
 @pytest.mark.parametrize("k", H.MEAN_KS)
 def test_segment_mean_against_the_bound(device, k):
-    x_np, order_np, offsets_np, want, bound = H.mean_case(k)
-    n, segments = x_np.shape[0], offsets_np.shape[0] - 1
-    lib = native.lib()
-    x = Rows.of(x_np, 3, device)
-    order, offsets = torch.from_numpy(order_np.copy()).to(device), torch.from_numpy(offsets_np.copy()).to(device)
-    outs = []
-    for _ in range(2):
-        out = Rows(segments, k, 1, device, float("nan"))
-        native.check(lib.mmk_segment_mean_f32(x.ptr, x.stride, n, k, order.data_ptr(), offsets.data_ptr(), segments, out.ptr, out.stride,
-                                              native.stream_ptr(device)))
-        check_written(out.buf, out.mask(), f"segment means, k {k}")
-        outs.append(out.view.clone())
-    assert same_bits(outs[0], outs[1]), "two calls differ"
-    worst = NR.assert_inside(outs[0].cpu().numpy(), want, bound, f"segment means, k {k}")
-    got = native.segment_mean(torch.from_numpy(x_np.copy()).to(device), order, offsets)
-    assert got.shape == (segments, k) and same_bits(got, outs[0])
+    worst = 0.0
+    for sizes in (H.MEAN_SEGMENTS, H.ONE_ROW):             # segments of 2, 3, 700 and 1 members; one row in one segment
+        x_np, order_np, offsets_np, want, bound = H.mean_case(k, sizes)
+        n, segments = x_np.shape[0], offsets_np.shape[0] - 1
+        outs = [mean_call(x_np, order_np, offsets_np, device) for _ in range(2)]
+        order, offsets = torch.from_numpy(order_np.copy()).to(device), torch.from_numpy(offsets_np.copy()).to(device)
+        assert same_bits(outs[0], outs[1]), "two calls differ"
+        worst = max(worst, NR.assert_inside(outs[0].cpu().numpy(), want, bound, f"segment means, k {k}, segments of {sizes}"))
+        got = native.segment_mean(torch.from_numpy(x_np.copy()).to(device), order, offsets)
+        assert got.shape == (segments, k) and same_bits(got, outs[0])
+        single = np.diff(offsets_np) == 1                  # a segment of one member is that row, bit for bit
+        assert np.array_equal(outs[0].cpu().numpy()[single].view(np.int32), x_np[order_np[offsets_np[:-1][single]]].view(np.int32))
     print(f"segment_mean k {k}: worst error / bound {worst:.3f}")
 
 

@@ -13,55 +13,32 @@ from mimikit_amd import native
 from mimikit_amd.features.functionals import HarmonicSource, MagSpec, PercussiveSource
 from tests import hpss_refs as R
 from tests.f64_bounds import check_written
+from tests.strided_inputs import FLOAT_SURROUNDS, PAD, Strided, surround_rule
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
 G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hpss.npz"))
 TF, TB = native.HPSS_TILE_FRAMES, native.HPSS_TILE_BINS
-PAD, GAP = 7, 11                          # row stride = bins + PAD; a clip starts GAP elements after the previous one's last row
 INF = float("inf")
 OUTPUTS = ("harmonic", "percussive", "harm_median", "perc_median")
 
 
-class Clips:
-    """(batch, frames, bins) inside a longer buffer: row stride bins + PAD, batch stride frames rows + GAP, first element `offset` in"""
-
-    def __init__(self, batch, frames, bins, offset, device, fill):
-        self.shape, self.offset = (batch, frames, bins), offset
-        self.row, self.clip = bins + PAD, frames * (bins + PAD) + GAP
-        self.buf = torch.full((offset + batch * self.clip + 5,), fill, dtype=torch.float32, device=device)
-        self.view = self.buf.as_strided(self.shape, (self.clip, self.row, 1), offset)
-
-    @classmethod
-    def of(cls, x_np, offset, device):
-        c = cls(*x_np.shape, offset, device, 0.0)
-        c.view.copy_(torch.from_numpy(x_np.copy()))
-        return c
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + 4 * self.offset
-
-    def mask(self):
-        m = torch.zeros(self.buf.shape, dtype=torch.bool)
-        m.as_strided(self.shape, (self.clip, self.row, 1), self.offset).fill_(True)
-        return m
-
-
-def hpss_call(x_np, kernel_size, power, margin, wanted, device, what):
-    """-> {name: (batch, frames, bins) numpy} of the outputs in `wanted`; confirms that each was written exactly, and nothing else"""
+@surround_rule(*FLOAT_SURROUNDS)
+def hpss_call(x_np, kernel_size, power, margin, wanted, device, what, gap=None):
+    """-> {name: (batch, frames, bins) numpy} of the outputs in `wanted`; confirms that each was written exactly, and nothing else.  gap: the
+    floats between a clip's last frame and the next clip's first (None: a row's padding and GAP; 0: the clips end to end)"""
     (wh, wp), (mh, mp) = R.pair(kernel_size), R.pair(margin)
-    s = Clips.of(x_np, 1, device)
-    outs = {name: Clips(*x_np.shape, 3, device, float("nan")) for name in wanted}
+    _, frames, bins = x_np.shape
+    s = Strided.of(x_np, 1, device, batch_stride=None if gap is None else (frames - 1) * (bins + PAD) + bins + gap)
+    outs = {name: Strided(x_np.shape, 3, device, float("nan")) for name in wanted}
     first = outs[wanted[0]]
-    before = s.buf.clone()
-    native.check(native.lib().mmk_hpss_f32(s.ptr, s.clip, s.row, *x_np.shape, wh, wp, power, mh, mp,
-                                           *(outs[name].ptr if name in outs else None for name in OUTPUTS), first.clip, first.row,
+    native.check(native.lib().mmk_hpss_f32(s.ptr, s.clip, s.stride, *x_np.shape, wh, wp, power, mh, mp,
+                                           *(outs[name].ptr if name in outs else None for name in OUTPUTS), first.clip, first.stride,
                                            native.stream_ptr(device)), what)
     for name, o in outs.items():
         check_written(o.buf, o.mask(), f"{what}: {name}")
-    assert torch.equal(before, s.buf), f"{what}: the input changed"
+    assert s.untouched(), f"{what}: the input changed"
     return {name: o.view.cpu().numpy() for name, o in outs.items()}
 
 
@@ -70,6 +47,9 @@ def check_case(kind, batch, frames, bins, kernel_size, device, power=1.0, margin
     x = R.case_input(kind, batch, frames, bins)
     harm, perc, hm, pm, bad = R.reference(kind, batch, frames, bins, kernel_size, power, margin)
     got = hpss_call(x, kernel_size, power, margin, wanted, device, what)
+    if batch > 1:                       # a window that leaves a clip meets the next clip's frames, not padding
+        packed = hpss_call(x, kernel_size, power, margin, wanted, device, what, gap=0)
+        assert all(R.same_bits(packed[name], got[name]) for name in wanted), f"{what}: clips end to end give other bits"
     worst = 0.0
     for name, want in (("harm_median", hm), ("perc_median", pm)):
         if name in got:

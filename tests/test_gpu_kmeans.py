@@ -15,38 +15,22 @@ from tests import kmeans_refs as R
 from tests import stream_cases as S
 from tests.f64_bounds import check_written
 from tests.neighbors_refs import assert_inside
+from tests.strided_inputs import FLOAT_SURROUNDS, Strided, surround_rule
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
 G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kmeans.npz"))
-PAD = 7                                   # row stride = d + PAD: the rows of one call differ in alignment
 POISON = -7
 NAN = float("nan")
-
-
-class Rows:
-    """(batch, n) float32 rows inside a longer buffer: row stride n + PAD, first row `offset` elements in"""
-
-    def __init__(self, x_np, offset, device):
-        self.batch, self.n = x_np.shape
-        self.offset, self.stride = offset, self.n + PAD
-        self.buf = torch.zeros((offset + self.batch * self.stride + 5,), dtype=torch.float32, device=device)
-        self.view = self.buf.as_strided((self.batch, self.n), (self.stride, 1), offset)
-        self.view.copy_(torch.from_numpy(x_np.copy()))
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + 4 * self.offset
 
 
 def vector(v_np, device):
     """a float vector one element into its buffer (4-byte aligned only), or None"""
     if v_np is None:
         return None, None
-    buf = torch.zeros((v_np.shape[0] + 2,), dtype=torch.float32, device=device)
-    buf[1:1 + v_np.shape[0]] = torch.from_numpy(v_np.copy())
-    return buf, buf.data_ptr() + 4
+    v = Strided.of(v_np[None], 1, device, row_stride=v_np.shape[0], tail=1)
+    return v, v.ptr
 
 
 def padded(n, dtype, fill, device, before=3, after=4):
@@ -70,12 +54,13 @@ def same_bits(a, b):
 
 
 # ------------------------------------------------------------------------------------------------------------------ assignment
+@surround_rule(*FLOAT_SURROUNDS)
 def assign_call(x_np, offset_np, centres_np, device, labels_in=None, want_key=True, want_changed=True):
     """mmk_kmeans_assign_f32 on strided, misaligned rows -> (labels int32, key or None, changed or None)"""
     lib = native.lib()
-    x, c = Rows(x_np, 1, device), Rows(centres_np, 2, device)
+    x, c = Strided.of(x_np, 1, device), Strided.of(centres_np, 2, device)
     obuf, optr = vector(offset_np, device)
-    n, d, k = x.batch, x.n, c.batch
+    n, d, k = x.rows, x.k, c.rows
     shift = torch.full((k + 3,), NAN, dtype=torch.float32, device=device)
     native.check(lib.mmk_half_neg_sqnorm_f32(c.ptr, c.stride, k, d, shift.data_ptr(), native.stream_ptr(device)))
     lbuf, labels = padded(n, torch.int32, POISON, device, before=1)
@@ -154,12 +139,13 @@ def test_assign_special_inputs(device, with_offset):
 
 
 # ------------------------------------------------------------------------------------------------------------------ sums
+@surround_rule(*FLOAT_SURROUNDS)
 def sums_call(x_np, offset_np, labels_np, k, device, centres_np=None, want_d2=True, want_inertia=True):
     lib = native.lib()
-    x = Rows(x_np, 1, device)
+    x = Strided.of(x_np, 1, device)
     obuf, optr = vector(offset_np, device)
-    n, d = x.batch, x.n
-    labels = torch.from_numpy(labels_np.astype(np.int32)).to(device)
+    n, d = x.rows, x.k
+    labels = Strided.of(labels_np.astype(np.int32)[None], 4, device, row_stride=n, decoy=(0, k)).view[0]      # (contiguous: decoy labels in front and behind)
     n_work = lib.mmk_kmeans_label_sums_workspace_bytes(n, d, k)
     assert 0 < n_work <= (native.KMEANS_MAX_SLABS * (k * (d + 1) + 1)) * 8
     work = torch.full((n_work // 8 + 3,), NAN, dtype=torch.float64, device=device)
@@ -167,7 +153,7 @@ def sums_call(x_np, offset_np, labels_np, k, device, centres_np=None, want_d2=Tr
     cbuf, counts = padded(k, torch.int64, POISON, device)
     dbuf, d2 = padded(n, torch.float64, NAN, device)
     ibuf, inertia = padded(1, torch.float64, NAN, device)
-    c = Rows(centres_np, 2, device) if centres_np is not None else None
+    c = Strided.of(centres_np, 2, device) if centres_np is not None else None
     native.check(lib.mmk_kmeans_label_sums_f64(x.ptr, x.stride, optr, n, d, labels.data_ptr(), k, sums.data_ptr(), counts.data_ptr(),
                                                c.ptr if c else None, c.stride if c else 0, d2.data_ptr() if c and want_d2 else None,
                                                inertia.data_ptr() if c and want_inertia else None, work.data_ptr(), n_work, native.stream_ptr(device)))
@@ -241,12 +227,13 @@ def test_label_sums_special_inputs_and_many_slabs(device):
 
 
 # ------------------------------------------------------------------------------------------------------------------ seeding step
+@surround_rule(*FLOAT_SURROUNDS)
 def pp_call(x_np, offset_np, cand_np, closest_np, device):
     lib = native.lib()
-    x = Rows(x_np, 1, device)
+    x = Strided.of(x_np, 1, device)
     obuf, optr = vector(offset_np, device)
-    n, d = x.batch, x.n
-    cand = torch.from_numpy(np.asarray(cand_np, dtype=np.int64)).to(device)
+    n, d = x.rows, x.k
+    cand = Strided.of(np.asarray(cand_np, dtype=np.int64)[None], 4, device, row_stride=len(cand_np), decoy=(0, n)).view[0]
     cbuf, closest = padded(n, torch.float64, NAN, device)
     closest.copy_(torch.from_numpy(closest_np))
     pbuf, pot = padded(1, torch.float64, NAN, device)

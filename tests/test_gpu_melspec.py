@@ -11,6 +11,7 @@ from mimikit_amd import native
 from mimikit_amd.features import mel
 from mimikit_amd.features.functionals import MFCC, MagSpec, MelSpec
 from tests import melspec_refs as R
+from tests.strided_inputs import FLOAT_SURROUNDS, Strided, surround_rule
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -36,6 +37,11 @@ def dense_of(name, n_bins, **kw):
     return R.mel_bank(n_bins, n_mels, fmin, fmax, htk, **kw)
 
 
+@surround_rule(*FLOAT_SURROUNDS)
+def bank_on_placed_rows(f, s_np, device):
+    return f(Strided.of(s_np, 1, device).view).cpu().numpy()
+
+
 @pytest.mark.parametrize("name,n_bins", BANK_CASES)
 def test_bank_kernel_within_the_bound_of_float64(device, name, n_bins):
     f = melspec_of(name)[0]
@@ -54,6 +60,8 @@ def test_bank_kernel_within_the_bound_of_float64(device, name, n_bins):
             bound = R.bank_bound(want, dense)
             worst = max(worst, R.assert_inside(got, want, bound, f"MelSpec {name} on {shape}"))
             assert not got[..., length == 0].any(), "a band of length 0 gives exactly 0"
+            if len(shape) == 2:                           # the same frames as rows of a wider buffer: in_row_stride, and what lies around them
+                assert np.array_equal(bank_on_placed_rows(f, s, device).view(np.int32), got.view(np.int32)), f"MelSpec {name} on placed rows of {shape}"
             if rows == 65 and len(shape) == 2:            # the bound is no wider than the defects it has to catch
                 R.assert_near_miss_leaves(R.mel64(s, R.shifted(dense)), want, bound, f"{name} {n_bins}: shifted by one bin")
                 R.assert_near_miss_leaves(R.mel64(s, dense_of(name, n_bins, slaney=False)), want, bound, f"{name} {n_bins}: no Slaney factor")
@@ -130,6 +138,14 @@ FUSED = [
 ]
 
 
+@surround_rule(*FLOAT_SURROUNDS)
+def on_placed_rows(x_np, magspec, melspec, device):
+    """MagSpec and MelSpec.from_signal on rows of a wider buffer (5 samples in, 37 more than a row apart) -> magnitudes, mel bands"""
+    rows = Strided.of(x_np, 5, device, row_stride=x_np.shape[1] + 37, tail=32)
+    x = rows.view if x_np.shape[0] > 1 else rows.view[0]
+    return magspec(x), melspec.from_signal(x, magspec)
+
+
 @pytest.mark.parametrize("n_fft,hop,center,pad_mode,batch,n,n_mels,covers", FUSED, ids=[f"{c[0]}-{c[1]}-{c[2]}-{c[3]}-{c[4]}" for c in FUSED])
 def test_fused_path_against_float64_on_magspec(device, n_fft, hop, center, pad_mode, batch, n, n_mels, covers):
     magspec = MagSpec(n_fft, hop, center=center, pad_mode=pad_mode, alignment=None)
@@ -142,6 +158,8 @@ def test_fused_path_against_float64_on_magspec(device, n_fft, hop, center, pad_m
     mag = magspec(x)
     mag_bits = bits(mag).clone()
     got = melspec.from_signal(x, magspec)
+    rows_mag, rows_mel = on_placed_rows(R.signal(batch, n + 37)[:, 5:5 + n], magspec, melspec, device)     # the same rows, other neighbours
+    assert torch.equal(bits(rows_mag), bits(mag)) and torch.equal(bits(rows_mel), bits(got)), "what lies around the rows shows in the result"
     n_frames = mag.shape[-2]
     assert got.shape == mag.shape[:-1] + (n_mels,) and got.dtype == torch.float32
     if "odd" in covers or "7 frames" in covers:

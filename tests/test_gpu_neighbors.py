@@ -12,37 +12,13 @@ import mimikit_amd as mmk
 from mimikit_amd import native
 from tests import neighbors_refs as R
 from tests.f64_bounds import check_written
+from tests.strided_inputs import FLOAT_SURROUNDS, INT_SURROUNDS, Strided, surround_rule
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
 G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "neighbors.npz"))
-PAD = 7                                   # row stride = k + PAD: the rows of one call differ in alignment
 SPAN = native.NN_SPAN
-
-
-class Rows:
-    """(batch, n) rows inside a longer buffer: row stride n + PAD, first row `offset` elements in"""
-
-    def __init__(self, batch, n, offset, device, fill, dtype=torch.float32):
-        self.batch, self.n, self.offset, self.stride = batch, n, offset, n + PAD
-        self.buf = torch.full((offset + batch * self.stride + 5,), fill, dtype=dtype, device=device)
-        self.view = self.buf.as_strided((batch, n), (self.stride, 1), offset)
-
-    @classmethod
-    def of(cls, x_np, offset, device):
-        r = cls(x_np.shape[0], x_np.shape[1], offset, device, 0, torch.from_numpy(x_np[:1, :1]).dtype)
-        r.view.copy_(torch.from_numpy(x_np.copy()))
-        return r
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + self.buf.element_size() * self.offset
-
-    def mask(self):
-        m = torch.zeros(self.buf.shape, dtype=torch.bool)
-        m.as_strided((self.batch, self.n), (self.stride, 1), self.offset).fill_(True)
-        return m
 
 
 def same_bits(a, b):
@@ -50,12 +26,13 @@ def same_bits(a, b):
 
 
 # ------------------------------------------------------------------------------------------------------------------ arg-max kernel
+@surround_rule(*FLOAT_SURROUNDS)
 def nn_call(x_np, y_np, device, x_off=1, y_off=3):
     """mmk_nn_cosine_f32 on strided, misaligned rows; outputs and workspace NaN-filled (the index buffer holds -1).  -> index, cos_best (numpy)"""
     rows, k = x_np.shape
     m = y_np.shape[0]
     lib = native.lib()
-    x, y = Rows.of(x_np, x_off, device), Rows.of(y_np, y_off, device)
+    x, y = Strided.of(x_np, x_off, device), Strided.of(y_np, y_off, device)
     rx, ry = native.inv_row_norm(x.view), native.inv_row_norm(y.view)
     n_work = lib.mmk_nn_cosine_workspace_bytes(rows, m)
     assert 0 < n_work <= rows * -(-m // SPAN) * 16 + 4096
@@ -189,11 +166,12 @@ def test_nearest_neighbor_against_the_fixture(device, name):
 
 
 # ------------------------------------------------------------------------------------------------------------------ cumulative entropy
+@surround_rule(*INT_SURROUNDS)
 def entropy_call(items_np, device, per_step=True, off=1):
     batch, t = items_np.shape
-    it = Rows.of(items_np, off, device)
+    it = Strided.of(items_np, off, device, decoy=(int(items_np.min()), int(items_np.max()) + 2))      # (any int64 is an item: decoys from the rows' own range)
     total = torch.full((batch + 3,), float("nan"), dtype=torch.float32, device=device)
-    e = Rows(batch, t, 3, device, float("nan"))
+    e = Strided((batch, t), 3, device, float("nan"))
     native.check(native.lib().mmk_cum_entropy_i64(it.ptr, it.stride, batch, t, total.data_ptr(), e.ptr if per_step else None, e.stride,
                                                   native.stream_ptr(device)))
     mask = torch.zeros(total.shape, dtype=torch.bool)

@@ -15,7 +15,8 @@ from mimikit_amd import native
 from tests import nmf_refs as R
 from tests import stream_cases as S
 from tests.f64_bounds import check_written
-from tests.test_gpu_pca import Rows, front_mask, poisoned, same_bits, to_dev
+from tests.strided_inputs import FLOAT_SURROUNDS, Strided, surround_rule
+from tests.test_gpu_pca import front_mask, poisoned, same_bits, to_dev
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -39,9 +40,10 @@ def mid_mask(buf, n):
     return mask
 
 
+@surround_rule(*FLOAT_SURROUNDS)
 def start_call(x_np, k, device):
     lib = native.lib()
-    x = Rows(x_np, 1, device)
+    x = Strided.of(x_np, 1, device)
     n, d = x_np.shape
     n_work = lib.mmk_nmf_start_workspace_bytes(n, d, k)
     assert n_work > lib.mmk_pca_cov_workspace_bytes(n, d) + lib.mmk_pca_eig_workspace_bytes(d, k) + d * d * 8
@@ -56,10 +58,11 @@ def start_call(x_np, k, device):
     return w[:n * k].view(n, k), ht[:d * k].view(d, k), s[:k], v[:k * d].view(k, d), part[:k]
 
 
+@surround_rule(*FLOAT_SURROUNDS)
 def half_call(which, x_np, w_np, ht_np, device):
     """one half-sweep through the C ABI -> (the updated factor, the violation); the other factor must stay untouched"""
     lib = native.lib()
-    x = Rows(x_np, 2, device)
+    x = Strided.of(x_np, 2, device)
     n, d = x_np.shape
     k = w_np.shape[1]
     n_work = lib.mmk_nmf_half_workspace_bytes(n, d, k)
@@ -80,9 +83,10 @@ def half_call(which, x_np, w_np, ht_np, device):
     return (w if which == "w" else ht).clone(), viol[:1].clone()
 
 
+@surround_rule(*FLOAT_SURROUNDS)
 def solve_call(x_np, w_np, ht_np, device, update_h=True, tol=1e-4, max_iter=200, poll=0):
     lib = native.lib()
-    x = Rows(x_np, 3, device)
+    x = Strided.of(x_np, 3, device)
     n, d = x_np.shape
     k = w_np.shape[1]
     n_work = lib.mmk_nmf_solve_workspace_bytes(n, d, k)

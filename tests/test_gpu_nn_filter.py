@@ -16,12 +16,12 @@ from tests import nn_filter_refs as R
 from tests import stream_cases as S
 from tests.f64_bounds import check_written
 from tests.neighbors_refs import assert_inside
+from tests.strided_inputs import FLOAT_SURROUNDS, Strided, surround_rule
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
 G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "nn_filter.npz"))
-PAD = 7                                   # row stride = d + PAD: the rows of one call differ in alignment
 POISON = -7
 NAN = float("nan")
 
@@ -30,33 +30,14 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
 
 
-class Rows:
-    """(n, d) float32 rows inside a longer buffer filled with `fill`: row stride d + PAD, first row `offset` elements in"""
-
-    def __init__(self, n, d, offset, device, fill=0.0, x_np=None):
-        self.n, self.d, self.offset, self.stride = n, d, offset, d + PAD
-        self.buf = torch.full((offset + n * self.stride + 5,), fill, dtype=torch.float32, device=device)
-        self.view = self.buf.as_strided((n, d), (self.stride, 1), offset)
-        if x_np is not None:
-            self.view.copy_(torch.from_numpy(x_np.copy()))
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + 4 * self.offset
-
-    def mask(self):
-        m = torch.zeros(self.buf.shape, dtype=torch.bool)
-        m.as_strided((self.n, self.d), (self.stride, 1), self.offset).fill_(True)
-        return m
-
-
+@surround_rule(*FLOAT_SURROUNDS)
 def aggregate_call(x_np, index_np, op, mutual, device, want_count=True):
     """mmk_nn_aggregate_f32 on strided, misaligned rows -> (out (n, d) float32 numpy, counts int32 numpy or None)"""
     lib = native.lib()
     n, d = x_np.shape
     t = index_np.shape[1]
-    x, out = Rows(n, d, 1, device, x_np=x_np), Rows(n, d, 3, device, fill=NAN)
-    index = torch.from_numpy(index_np.copy()).to(device)
+    x, out = Strided.of(x_np, 1, device), Strided((n, d), 3, device, NAN)
+    index = Strided.of(index_np, 4, device, row_stride=t, decoy=(0, n)).view                # (contiguous lists: decoy frames in front and behind)
     cbuf = torch.full((n + 3,), POISON, dtype=torch.int32, device=device)
     count = cbuf[1:1 + n]
     native.check(lib.mmk_nn_aggregate_f32(x.ptr, x.stride, n, d, index.data_ptr(), t, 1 if mutual else 0, native.NN_AGGREGATES.index(op), out.ptr,
@@ -101,6 +82,20 @@ def test_aggregate_on_drawn_lists(device, n, op):
     print(f"nn_aggregate n {n} {op}: {len(R.DS) * len(R.TS) * 2} cases, worst error / bound {worst:.3f}")
 
 
+@surround_rule(*FLOAT_SURROUNDS)
+def wrapper_on_placed_rows(x_np, index, op, device):
+    """native.nn_aggregate on columns 3 .. 3 + d of rows 80 floats wide"""
+    rows = Strided.of(x_np, 3, device, row_stride=80, tail=80 - 3 - x_np.shape[1])
+    return native.nn_aggregate(rows.view, index, op).cpu().numpy()
+
+
+@surround_rule(*FLOAT_SURROUNDS)
+def filter_on_placed_clips(clips_np, op, device):
+    """NearestNeighborFilter on (2, 96, 33) clips that are rows 2 .. 98 and columns 5 .. 38 of clips of 100 rows of 40 floats"""
+    padded = Strided.of(clips_np, 2 * 40 + 5, device, row_stride=40, batch_stride=100 * 40)
+    return mmk.NearestNeighborFilter(aggregate=op)(padded.view)
+
+
 def test_aggregate_contiguous_rows_and_a_single_row_list(device):
     """the wrapper (contiguous x, torch's own out) against the C ABI call on strided rows, and lists that leave every row empty"""
     x_np, index_np = R.kernel_case(129, 65, 16)
@@ -110,9 +105,7 @@ def test_aggregate_contiguous_rows_and_a_single_row_list(device):
         out, count = native.nn_aggregate(x, index, op, mutual=True, return_count=True)
         assert np.array_equal(bits(out.cpu().numpy()), bits(want)) and np.array_equal(count.cpu().numpy(), want_counts), op
         assert count.dtype == torch.int32 and out.dtype == torch.float32 and out.shape == x.shape
-        strided = torch.zeros((129, 80), device=device)[:, 3:68]
-        strided.copy_(x)
-        assert np.array_equal(bits(native.nn_aggregate(strided, index, op).cpu().numpy()), bits(want)), f"{op}: a row-strided x through the wrapper"
+        assert np.array_equal(bits(wrapper_on_placed_rows(x_np, index, op, device)), bits(want)), f"{op}: a row-strided x through the wrapper"
     nothing = torch.full((129, 3), -1, dtype=torch.int64, device=device)
     out, count = native.nn_aggregate(x, nothing, "median", return_count=True)
     assert np.array_equal(bits(out.cpu().numpy()), bits(x_np)) and int(count.abs().sum()) == 0
@@ -233,15 +226,13 @@ def test_filter_against_the_golden(device, name):
 def test_filter_on_a_batch_is_its_clips_one_by_one(device):
     names = ("cos96", "euc96")
     clips = torch.from_numpy(np.stack([R.fixture_frames(n) for n in names])).to(device)
-    padded = torch.zeros((2, 100, 40), device=device)[:, 2:98, 5:38]           # clips and rows at a stride
-    padded.copy_(clips)
     for op in ("median", "mean"):
         nf = mmk.NearestNeighborFilter(aggregate=op)
         got = nf(clips)
         assert got.shape == clips.shape and got.device.type == "cuda"
         for b in range(2):
             assert S.same_bits(got[b], nf(clips[b])), f"{op}: clip {b} of the batch differs from the clip alone"
-        assert S.same_bits(nf(padded), got), f"{op}: a strided batch differs"
+        assert S.same_bits(filter_on_placed_clips(clips.cpu().numpy(), op, device), got), f"{op}: a strided batch differs"      # clips and rows at a stride
         if op == "median":
             assert np.array_equal(bits(got[0].cpu().numpy()), bits(G["cos96_median"])), "neighbours crossed the clips"
     print("NearestNeighborFilter batch: worst error / bound 0.000 (bits)")

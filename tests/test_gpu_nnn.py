@@ -11,36 +11,32 @@ from mimikit_amd import native
 from mimikit_amd.models import NearestNextNeighbor
 from tests import helpers as H
 from tests import nnn_refs as R
+from tests.strided_inputs import FLOAT_SURROUNDS, Strided, surround_rule
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
 
-def strided(a, row_pad, lead, device):
-    """the (.., rows, k) array `a` inside a longer NaN-filled buffer: base `lead` floats in, rows k + row_pad apart (clips a further 5)
-    -> (buffer, pointer, batch stride, row stride)"""
-    a3 = a if a.ndim == 3 else a[None]
-    batch, rows, k = a3.shape
-    rs = k + row_pad
-    bs = rows * rs + 5
-    buf = torch.full((lead + batch * bs + 3,), float("nan"), dtype=torch.float32, device=device)
-    buf.as_strided((batch, rows, k), (bs, rs, 1), lead).copy_(torch.from_numpy(np.ascontiguousarray(a3)))
-    return buf, buf.data_ptr() + 4 * lead, bs, rs
+def placed(a, row_pad, device):
+    """the (.., rows, k) array `a` as an input of the call: base one float in, rows k + row_pad apart, clips a further 5"""
+    a3 = np.ascontiguousarray(a if a.ndim == 3 else a[None])
+    rs = a3.shape[2] + row_pad
+    return Strided.of(a3, 1, device, row_stride=rs, batch_stride=a3.shape[1] * rs + 5, tail=3)
 
 
+@surround_rule(*FLOAT_SURROUNDS)
 def cost_through_abi(x, y, device):
     """mmk_inv_row_norm_f32 twice and mmk_cosine_cost_f32 on strided, offset operands -> the whole (batch, m, n_pad) cost buffer"""
     batch, n, k = x.shape
     m = y.shape[0]
-    xb, xp, xbs, xrs = strided(x, 3, 1, device)
-    yb, yp, _, yrs = strided(y, 5, 1, device)
+    xs, ys = placed(x, 3, device), placed(y, 5, device)
     rx = torch.full((batch * n,), float("nan"), dtype=torch.float32, device=device)
     ry = torch.full((m,), float("nan"), dtype=torch.float32, device=device)
     st = native.stream_ptr(device)
-    native.check(native.lib().mmk_inv_row_norm_f32(xp, xbs, xrs, batch, n, k, rx.data_ptr(), st))
-    native.check(native.lib().mmk_inv_row_norm_f32(yp, 0, yrs, 1, m, k, ry.data_ptr(), st))
+    native.check(native.lib().mmk_inv_row_norm_f32(xs.ptr, xs.clip, xs.stride, batch, n, k, rx.data_ptr(), st))
+    native.check(native.lib().mmk_inv_row_norm_f32(ys.ptr, 0, ys.stride, 1, m, k, ry.data_ptr(), st))
     cost = torch.full((batch, m, R.n_pad(n)), float("nan"), dtype=torch.float32, device=device)
-    native.check(native.lib().mmk_cosine_cost_f32(xp, xbs, xrs, rx.data_ptr(), batch, n, yp, yrs, ry.data_ptr(), m, k, cost.data_ptr(), st))
+    native.check(native.lib().mmk_cosine_cost_f32(xs.ptr, xs.clip, xs.stride, rx.data_ptr(), batch, n, ys.ptr, ys.stride, ry.data_ptr(), m, k, cost.data_ptr(), st))
     return cost.cpu().numpy()
 
 

@@ -11,32 +11,13 @@ import mimikit_amd as mmk
 from mimikit_amd import native
 from tests import pca_refs as R
 from tests.f64_bounds import check_written
+from tests.strided_inputs import FLOAT_SURROUNDS, Strided, surround_rule
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
-PAD = 7                                   # row stride = d + PAD: the rows of one call differ in alignment
 NAMES = sorted(R.FIXTURES)
 NAN = float("nan")
-
-
-class Rows:
-    """(n, d) float32 rows inside a longer buffer: row stride d + PAD, first row `offset` elements in"""
-
-    def __init__(self, x_np, offset, device):
-        self.n, self.d = x_np.shape
-        self.offset, self.stride = offset, self.d + PAD
-        self.buf = torch.zeros((offset + self.n * self.stride + 5,), dtype=torch.float32, device=device)
-        self.view = self.buf.as_strided((self.n, self.d), (self.stride, 1), offset)
-        self.view.copy_(torch.from_numpy(x_np.copy()))
-        self.before = self.buf.clone()
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + 4 * self.offset
-
-    def untouched(self):
-        return torch.equal(self.buf, self.before)
 
 
 def same_bits(a, b):
@@ -57,9 +38,10 @@ def to_dev(a, device):
     return torch.from_numpy(np.array(a)).to(device)        # (a copy: the fixtures are read-only)
 
 
+@surround_rule(*FLOAT_SURROUNDS)
 def colstats_call(x_np, device):
     lib = native.lib()
-    x = Rows(x_np, 1, device)
+    x = Strided.of(x_np, 1, device)
     n, d = x_np.shape
     n_work = lib.mmk_pca_colstats_workspace_bytes(n, d)
     assert n_work == (min(-(-n // 256), 1024) + 1) * d * 8
@@ -72,9 +54,10 @@ def colstats_call(x_np, device):
     return mean[:d], scale[:d]
 
 
+@surround_rule(*FLOAT_SURROUNDS)
 def cov_call(x_np, mean, scale, device):
     lib = native.lib()
-    x = Rows(x_np, 3, device)
+    x = Strided.of(x_np, 3, device)
     n, d = x_np.shape
     n_work = lib.mmk_pca_cov_workspace_bytes(n, d)
     assert 0 < n_work and n_work % (64 * 64 * 8) == 0
@@ -102,9 +85,10 @@ def eig_call(c, k, device, max_iter=0):
     return comps[:k * d].reshape(k, d), var[:k], int(n_iter.value)
 
 
+@surround_rule(*FLOAT_SURROUNDS)
 def project_call(y_np, mean, scale, comps, device):
     lib = native.lib()
-    y = Rows(y_np, 2, device)
+    y = Strided.of(y_np, 2, device)
     m, d = y_np.shape
     k = comps.shape[0]
     stride = k + 3
@@ -149,6 +133,31 @@ def test_colstats_against_the_bound(device, name):
     print(f"pca_colstats {name}: worst error / bound {max((em / mean_bound).max(), (es / np.maximum(scale_bound, 1e-300)).max()):.3f}")
     assert (em <= mean_bound).all() and (es <= scale_bound).all()
     assert ((scale.cpu().numpy() == 1.0) == p["const"]).all(), "the constant-column rule"
+
+
+@pytest.mark.parametrize("n,d", ((1, 1), (1, 3), (2, 1), (2, 3), (257, 33)))
+def test_the_smallest_rows(device, n, d):
+    """one row, one column, a row shorter than any vector load, one row more than a block of 256: the three strided entry points under the
+    surround rule, the statistics inside the float64 bound, covariance and scores the bits of the wrappers on contiguous rows"""
+    x = np.random.default_rng(100 * n + d).standard_normal((n, d)).astype(np.float32)
+    p = R.pca64(x, 1) if n > 1 else None
+    mean, scale = colstats_call(x, device)
+    xd = to_dev(x, device)
+    wm, ws = native.pca_colstats(xd)
+    assert same_bits(mean, wm) and same_bits(scale, ws), "the wrapper on contiguous rows differs from the strided call"
+    if n == 1:                                              # a single row: its own mean exactly, every column constant
+        assert np.array_equal(mean.cpu().numpy(), x[0].astype(np.float64)) and bool((scale == 1.0).all())
+    else:
+        mean_bound, scale_bound = R.stats_bounds(p)
+        em, es = np.abs(mean.cpu().numpy() - p["mean"]), np.abs(scale.cpu().numpy() - p["scale"])
+        assert (em <= mean_bound).all() and (es <= scale_bound).all()
+        c = cov_call(x, mean, scale, device)
+        assert same_bits(c, native.pca_cov(xd, mean, scale)) and torch.equal(c, c.t())
+    comps = torch.eye(d, dtype=torch.float64, device=device)[:min(d, 2)].contiguous()
+    got = project_call(x, mean, scale, comps, device)
+    want = native.pca_project(xd, mean, scale, comps)
+    assert torch.equal(got.contiguous().view(torch.int32), want.view(torch.int32)), "the wrapper on contiguous rows differs from the strided call"
+    print(f"pca entry points on {n} x {d}: worst error / bound 0.000 (bits of the wrappers)")
 
 
 # ------------------------------------------------------------------------------------------------------------------ covariance

@@ -10,6 +10,7 @@ from mimikit_amd import native
 from oracle.weights import load_recipe
 from tests import helpers as H
 from tests import picker_refs as P
+from tests.strided_inputs import FLOAT_SURROUNDS, Strided, surround_rule
 
 pytestmark = pytest.mark.gpu
 
@@ -55,6 +56,18 @@ def check_sampled(row, n, tl, T, u, on_step, picks, tally, what):
 
 
 # ---- sample_kernel directly ------------------------------------------------------------------------------------------------------------------------
+@surround_rule(*FLOAT_SURROUNDS)
+def sample_rows(logits, n, col, temp, uni, device):
+    """native.categorical_sample on logits rows that are a strided, misaligned view (ld = width + PAD, 4 bytes in); the picks are those of
+    the contiguous rows"""
+    min_temp = P.MIN_TEMP if col else 0.
+    temp, uni = (None if t is None else t.to(device) for t in (temp, uni))
+    rows = Strided.of(logits.numpy(), 1, device)
+    got = native.categorical_sample(rows.view, n, col, min_temp, temp, uni).cpu()
+    assert torch.equal(got, native.categorical_sample(logits.to(device), n, col, min_temp, temp, uni).cpu()), "strided and contiguous rows give other picks"
+    return got
+
+
 @pytest.mark.parametrize("col", [True, False])
 @pytest.mark.parametrize("n", [48, 64, 200, 256, 321, 1000, 1024])
 def test_sample_kernel_on_crafted_rows(device, n, col):
@@ -78,12 +91,12 @@ def test_sample_kernel_on_crafted_rows(device, n, col):
     logits = torch.cat([full(row).expand(256, width) for row, *_ in blocks]).contiguous()
     temp = torch.cat([torch.full((256,), T) for _, _, T, _, _ in blocks])
     uni = torch.cat([u for *_, u, _ in blocks])
-    got = native.categorical_sample(logits.to(device), n, col, P.MIN_TEMP if col else 0., temp.to(device), uni.to(device)).cpu()
+    got = sample_rows(logits, n, col, temp, uni, device)
     for i, (row, tl, T, u, on) in enumerate(blocks):
         check_sampled(row, n, tl, torch.tensor([T]), u, on, got[256 * i:256 * (i + 1)], tally, what)
     greedy = [r for r in rows if r["kind"] == "greedy"]
     logits = torch.stack([full(row) for row in greedy])
-    got = native.categorical_sample(logits.to(device), n, col, P.MIN_TEMP if col else 0., None, None).cpu()
+    got = sample_rows(logits, n, col, None, None, device)
     for row, pick in zip(greedy, got.tolist()):
         want = P.picker_ref(row["logits"], n, row["temp_logit"] if col else None, P.MIN_TEMP)
         assert pick == want, (what, row["name"], pick, want)

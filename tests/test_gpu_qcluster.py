@@ -13,30 +13,15 @@ from mimikit_amd import native
 from tests import neighbors_refs as NR
 from tests import qcluster_refs as Q
 from tests.f64_bounds import check_written
+from tests.strided_inputs import FLOAT_SURROUNDS, INT_SURROUNDS, Strided, surround_rule
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
 G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "qcluster.npz"))
-PAD = 7                                   # row stride = k + PAD: the rows of one call differ in alignment
 SPAN = native.NN_SPAN
 POISON = -7
 LIMITS = {"cosine": (-1.0, 1.0), "euclidean": (float("-inf"), float("inf"))}      # key_min, key_max: a cosine is clamped, as nn_cosine clamps it
-
-
-class Rows:
-    """(batch, n) float32 rows inside a longer buffer: row stride n + PAD, first row `offset` elements in"""
-
-    def __init__(self, x_np, offset, device):
-        self.batch, self.n = x_np.shape
-        self.offset, self.stride = offset, self.n + PAD
-        self.buf = torch.zeros((offset + self.batch * self.stride + 5,), dtype=torch.float32, device=device)
-        self.view = self.buf.as_strided((self.batch, self.n), (self.stride, 1), offset)
-        self.view.copy_(torch.from_numpy(x_np.copy()))
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + 4 * self.offset
 
 
 def same_bits(a, b):
@@ -47,21 +32,22 @@ def scales(rows, metric, device):
     """(scale, shift) of the frames `rows` as a corpus: inverse norms and 0, or 1 and -|y|^2 / 2 through mmk_half_neg_sqnorm_f32 (into a
     NaN-filled buffer)"""
     if metric == "cosine":
-        return native.inv_row_norm(rows.view), torch.zeros((rows.batch,), dtype=torch.float32, device=device)
-    shift = torch.full((rows.batch + 3,), float("nan"), dtype=torch.float32, device=device)
-    native.check(native.lib().mmk_half_neg_sqnorm_f32(rows.ptr, rows.stride, rows.batch, rows.n, shift.data_ptr(), native.stream_ptr(device)))
+        return native.inv_row_norm(rows.view), torch.zeros((rows.rows,), dtype=torch.float32, device=device)
+    shift = torch.full((rows.rows + 3,), float("nan"), dtype=torch.float32, device=device)
+    native.check(native.lib().mmk_half_neg_sqnorm_f32(rows.ptr, rows.stride, rows.rows, rows.k, shift.data_ptr(), native.stream_ptr(device)))
     mask = torch.zeros(shift.shape, dtype=torch.bool)
-    mask[:rows.batch] = True
+    mask[:rows.rows] = True
     check_written(shift, mask, "half_neg_sqnorm")
-    return torch.ones((rows.batch,), dtype=torch.float32, device=device), shift[:rows.batch]
+    return torch.ones((rows.rows,), dtype=torch.float32, device=device), shift[:rows.rows]
 
 
+@surround_rule(*FLOAT_SURROUNDS)
 def topk_call(x_np, y_np, t, metric, device):
     """mmk_nn_topk_f32 on strided, misaligned rows (y_np None: self_exclude); outputs and workspace poisoned"""
     lib = native.lib()
-    x = Rows(x_np, 1, device)
-    y = x if y_np is None else Rows(y_np, 2, device)
-    rows, k, m = x.batch, x.n, y.batch
+    x = Strided.of(x_np, 1, device)
+    y = x if y_np is None else Strided.of(y_np, 2, device)
+    rows, k, m = x.rows, x.k, y.rows
     cscale, cshift = scales(y, metric, device)
     qscale = cscale if y_np is None else scales(x, metric, device)[0]
     n_work = lib.mmk_nn_topk_workspace_bytes(rows, m, t)
@@ -172,10 +158,12 @@ def test_topk_of_zero_rows_and_the_wrapper(device, metric):
 
 
 # ------------------------------------------------------------------------------------------------------------------ edge components
+@surround_rule(*INT_SURROUNDS, may_place_nothing=True)
 def components_call(src_np, dst_np, n, device):
     lib = native.lib()
     e = src_np.shape[0]
-    src, dst = torch.from_numpy(src_np.copy()).to(device), torch.from_numpy(dst_np.copy()).to(device)
+    # (contiguous lists: decoy frames of the case in front and behind; an empty list is a NULL pointer)
+    src, dst = (Strided.of(a.reshape(1, e), 4, device, row_stride=e, decoy=(0, n)).view[0] if e else torch.from_numpy(a.copy()).to(device) for a in (src_np, dst_np))
     n_work = lib.mmk_edge_components_workspace_bytes(n)
     assert 0 < n_work <= 13 * n + 8
     work = torch.full((n_work // 4 + 3,), POISON, dtype=torch.int32, device=device)

@@ -13,6 +13,7 @@ from mimikit_amd import native
 from tests import samplify_refs as R
 from tests import stream_cases as S
 from tests.f64_bounds import check_written
+from tests.strided_inputs import FLOAT_SURROUNDS, Strided, surround_rule
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -63,23 +64,33 @@ def test_spline_inside_the_bound_of_scipy(device, n):
     print(f"spline n={n}: worst error / bound {ratio:.3f}")
 
 
+@surround_rule(*FLOAT_SURROUNDS)
+def coef_call(x_np, device):
+    """mmk_spline2_coef_f64 on strided, misaligned float32 rows into a NaN-surrounded float64 view (rows n + 5 apart, 16 bytes in)"""
+    rows, n = x_np.shape
+    x, coef = Strided.of(x_np, 1, device), Strided((rows, n), 2, device, float("nan"), torch.float64, row_stride=n + 5, tail=2)
+    native.check(native.lib().mmk_spline2_coef_f64(x.ptr, x.stride, rows, n, coef.ptr, coef.stride, native.stream_ptr(device)), "mmk_spline2_coef_f64")
+    check_written(coef.buf, coef.mask(), "spline2_coef")
+    return coef.view.clone()
+
+
+@surround_rule(*FLOAT_SURROUNDS)
+def eval_call(coef_np, n_out, device):
+    """mmk_spline2_eval_f32 on strided float64 coefficients into a NaN-surrounded view (rows n_out + 3 apart, 4 bytes in)"""
+    rows, n = coef_np.shape
+    coef = Strided.of(coef_np, 2, device, row_stride=n + 5, tail=2)
+    out = Strided((rows, n_out), 1, device, float("nan"), row_stride=n_out + 3, tail=1)
+    native.check(native.lib().mmk_spline2_eval_f32(coef.ptr, coef.stride, rows, n, out.ptr, out.stride, n_out, native.stream_ptr(device)), "mmk_spline2_eval_f32")
+    check_written(out.buf, out.mask(), "spline2_eval")
+    return out.view.clone()
+
+
 def test_spline_entry_points_write_their_outputs_only(device):
-    lib = native.lib()
     n, n_out = TILE + 3, ETILE + 9
-    x = torch.rand(2, n, device=device) - 0.5
-    cbuf = torch.full((2 * (n + 5) + 4,), float("nan"), dtype=torch.float64, device=device)
-    native.check(lib.mmk_spline2_coef_f64(x.data_ptr(), n, 2, n, cbuf.data_ptr() + 16, n + 5, native.stream_ptr(device)), "mmk_spline2_coef_f64")
-    mask = torch.zeros(cbuf.shape, dtype=torch.bool)
-    mask.as_strided((2, n), (n + 5, 1), 2).fill_(True)
-    check_written(cbuf, mask, "spline2_coef")
-    coef = cbuf.as_strided((2, n), (n + 5, 1), 2)
-    assert torch.equal(coef, native.spline2_coef(x))
-    obuf = torch.full((2 * (n_out + 3) + 2,), float("nan"), dtype=torch.float32, device=device)
-    native.check(lib.mmk_spline2_eval_f32(coef.data_ptr(), n + 5, 2, n, obuf.data_ptr() + 4, n_out + 3, n_out, native.stream_ptr(device)), "mmk_spline2_eval_f32")
-    mask = torch.zeros(obuf.shape, dtype=torch.bool)
-    mask.as_strided((2, n_out), (n_out + 3, 1), 1).fill_(True)
-    check_written(obuf, mask, "spline2_eval")
-    assert torch.equal(obuf.as_strided((2, n_out), (n_out + 3, 1), 1), native.spline2_eval(coef.contiguous(), n_out))
+    x = torch.rand(2, n) - 0.5
+    coef = coef_call(x.numpy(), device)
+    assert torch.equal(coef, native.spline2_coef(x.to(device)))
+    assert torch.equal(eval_call(coef.cpu().numpy(), n_out, device), native.spline2_eval(coef.contiguous(), n_out))
     print("spline entry points: worst error / bound 0.000 (exact)")
 
 

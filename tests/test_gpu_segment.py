@@ -13,33 +13,15 @@ import mimikit_amd as mmk
 from mimikit_amd import native
 from tests import segment_refs as R
 from tests.f64_bounds import check_written
+from tests.strided_inputs import FLOAT_SURROUNDS, PAD, Strided, surround_rule
 from tests.golden import make_golden_segment as M
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
 G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "segment.npz"))
-PAD, GAP, OFFSET = 7, 11, 1              # row stride = D + PAD, clips GAP floats further apart than their rows need, the first row 4 bytes in
+OFFSET = 1                               # the first row 4 bytes in
 NAN = float("nan")
-
-
-class Clips:
-    """(batch, T, D) frames inside a longer buffer of other values"""
-
-    def __init__(self, x_np, device):
-        self.batch, self.T, self.D = x_np.shape
-        self.row, self.clip = self.D + PAD, self.T * (self.D + PAD) + GAP
-        self.buf = torch.full((OFFSET + self.batch * self.clip + 5,), 3.25, dtype=torch.float32, device=device)
-        self.view = self.buf.as_strided(x_np.shape, (self.clip, self.row, 1), OFFSET)
-        self.view.copy_(torch.from_numpy(np.array(x_np)))
-        self.before = self.buf.clone()
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + 4 * OFFSET
-
-    def unchanged(self):
-        return torch.equal(self.buf.view(torch.int32), self.before.view(torch.int32))
 
 
 def same_bits(a, b):
@@ -58,19 +40,20 @@ def halves_array(halves):
     return (C.c_int32 * len(halves))(*halves)
 
 
-def novelty_call(x_np, halves, device, own_norms):
+@surround_rule(*FLOAT_SURROUNDS)
+def novelty_call(x_np, halves, device, own_norms, gap=None):
     """mmk_novelty_f32 then mmk_novelty_finish_f32 -> raw (B, n, T), scores (B, n, T), dg (B, T) as torch tensors"""
     lib = native.lib()
-    clips = Clips(x_np, device)
     B, T, D = x_np.shape
+    clips = Strided.of(np.array(x_np), OFFSET, device, batch_stride=None if gap is None else (T - 1) * (D + PAD) + D + gap)
     n = len(halves)
     inv = None if own_norms else native.inv_row_norm(clips.view)
     raw, raw_mask = out_buffer(B * n * T, device)
-    native.check(lib.mmk_novelty_f32(clips.ptr, clips.clip, clips.row, native.ptr(inv), B, T, D, halves_array(halves), n, raw.data_ptr() + 4,
+    native.check(lib.mmk_novelty_f32(clips.ptr, clips.clip, clips.stride, native.ptr(inv), B, T, D, halves_array(halves), n, raw.data_ptr() + 4,
                                      native.stream_ptr(device)), "mmk_novelty_f32")
     what = f"B {B}, T {T}, D {D}, halves {halves}"
     check_written(raw, raw_mask, f"raw ({what})")
-    assert clips.unchanged(), f"{what}: the input was written"
+    assert clips.untouched(), f"{what}: the input was written"
     scores, s_mask = out_buffer(B * n * T, device)
     dg, g_mask = out_buffer(B * T, device)
     n_work = lib.mmk_novelty_finish_workspace_floats(B, n, T)
@@ -125,6 +108,9 @@ def test_two_clips_with_a_gap(device):
     for clip in range(2):
         one = novelty_call(x[clip:clip + 1], [6, 12], device, own_norms=False)
         assert all(same_bits(a[clip], b[0]) for a, b in zip(both, one)), "a clip's result depends on its neighbour"
+    for T, D, halves in ((5, 31, [6]), (R.TILE + 1, 33, [6, 12])):      # the clips end to end: behind a clip's last frame lies the next clip's first
+        x = R.frames_case(T, D, 2)
+        assert all(same_bits(a, b) for a, b in zip(novelty_call(x, halves, device, False), novelty_call(x, halves, device, False, gap=0)))
     print(f"novelty, two clips: worst error / bound {worst:.3f}")
 
 

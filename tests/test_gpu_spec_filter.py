@@ -17,12 +17,12 @@ from tests import far_cases as FC
 from tests import spec_filter_refs as R
 from tests import stream_cases as S
 from tests.f64_bounds import check_written
+from tests.strided_inputs import FLOAT_SURROUNDS, PAD, Strided, surround_rule
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
 G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "spec_filter.npz"))
-PAD = 7                                   # row stride = bins + PAD: the rows of one call differ in alignment
 NAN = float("nan")
 
 
@@ -33,43 +33,30 @@ def draw(seed, *shape, lo=0.05, hi=3.0):
     return s * rng.uniform(lo, hi, size=shape[:-1] + (1,)).astype(np.float32)
 
 
-class Clips:
-    """(B, T, F) float32 inside a longer buffer filled with `fill`: row stride F + PAD, clip stride T rows and 11 more, first element `offset` in"""
-
-    def __init__(self, shape, offset, device, fill=0.0, x_np=None):
-        self.shape, self.offset = tuple(shape), offset
-        b, t, f = shape
-        self.strides = (t * (f + PAD) + 11, f + PAD, 1)
-        self.buf = torch.full((offset + b * self.strides[0] + 5,), fill, dtype=torch.float32, device=device)
-        self.view = self.buf.as_strided(self.shape, self.strides, offset)
-        if x_np is not None:
-            self.view.copy_(torch.from_numpy(x_np.copy()))
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + 4 * self.offset
-
-    def mask(self):
-        m = torch.zeros(self.buf.shape, dtype=torch.bool)
-        m.as_strided(self.shape, self.strides, self.offset).fill_(True)
-        return m
+@surround_rule(*FLOAT_SURROUNDS)
+def abi_once(entry, s3, params, gap, device):
+    """the entry point on strided, misaligned clips, a clip `gap` elements behind the last frame of the one before it (None: GAP)"""
+    lib = native.lib()
+    s = Strided.of(s3, 1, device, batch_stride=None if gap is None else (s3.shape[1] - 1) * (s3.shape[2] + PAD) + s3.shape[2] + gap)
+    out = Strided(s3.shape, 3, device, NAN)
+    fn = lib.mmk_auto_convolve_f32 if entry == "ac" else lib.mmk_f0_filter_f32
+    rc = fn(s.ptr, s.strides[0], s.strides[1], *s3.shape, *params, out.ptr, out.strides[0], out.strides[1], native.stream_ptr(device))
+    native.check(rc, entry)
+    what = f"{entry} {s3.shape} {params}"
+    check_written(out.buf, out.mask(), what)
+    assert np.array_equal(R.bits(s.view.cpu().numpy()), R.bits(s3)), f"{what}: the input was written"
+    return out.view.cpu().numpy()
 
 
 def abi_call(entry, s_np, params, device):
-    """the entry point on strided, misaligned clips, twice -> (B, T, F) float32 numpy; nothing but the frames of out is written"""
-    lib = native.lib()
+    """abi_once twice -> (B, T, F) float32 numpy; nothing but the frames of out is written.  Clips of a batch are also laid end to end
+    (a gap of 0: the frame behind a clip's last is the next clip's first) for the same bits"""
     s3 = s_np if s_np.ndim == 3 else s_np[None]
-    got = []
-    for _ in range(2):
-        s, out = Clips(s3.shape, 1, device, x_np=s3), Clips(s3.shape, 3, device, fill=NAN)
-        fn = lib.mmk_auto_convolve_f32 if entry == "ac" else lib.mmk_f0_filter_f32
-        rc = fn(s.ptr, s.strides[0], s.strides[1], *s3.shape, *params, out.ptr, out.strides[0], out.strides[1], native.stream_ptr(device))
-        native.check(rc, entry)
-        what = f"{entry} {s3.shape} {params}"
-        check_written(out.buf, out.mask(), what)
-        assert np.array_equal(R.bits(s.view.cpu().numpy()), R.bits(s3)), f"{what}: the input was written"
-        got.append(out.view.cpu().numpy())
+    got = [abi_once(entry, s3, params, None, device) for _ in range(2)]
+    what = f"{entry} {s3.shape} {params}"
     assert np.array_equal(R.bits(got[0]), R.bits(got[1])), f"{what}: two calls differ"
+    if s3.shape[0] > 1:
+        assert np.array_equal(R.bits(abi_once(entry, s3, params, 0, device)), R.bits(got[0])), f"{what}: clips end to end give other bits"
     return got[0].reshape(s_np.shape)
 
 
@@ -112,7 +99,7 @@ SOFT = ((True, True), (True, False))       # (on drawn frames no gap is asserted
 def test_bins_from_two_to_the_maximum(device, bins):
     s = draw(bins, 3, bins)
     worst = f0_check(s, 4, 4, SOFT, device, f"f0 {bins} bins")
-    if bins in (2, R.MAX_BINS):
+    if bins in (2, 65, R.MAX_BINS):           # (2 and 65 bins: every harmonic but the first few lies beyond the spectrum)
         worst = max(worst, f0_check(s, R.MAX_OVERTONE, R.MAX_UNDERTONE, SOFT, device, f"f0 {bins} bins, both counts at their maximum"))
     n = R.ulp_rule(abi_call("ac", s, (3,), device), R.auto_convolve_numpy(s, 3).astype(np.float32), f"ac {bins} bins")
     print(f"{bins} bins: f0 worst error / bound {worst:.3f}, auto_convolve {n} elements off by one ulp")
@@ -124,6 +111,10 @@ def test_auto_convolve_frames_around_the_window_and_the_tile(device, k):
     for frames in (1, 2, R.TILE_FRAMES - 1, R.TILE_FRAMES + 1, 2 * R.TILE_FRAMES + 1):
         s = draw(100 * k + frames, frames, 65)
         n += R.ulp_rule(abi_call("ac", s, (k,), device), R.auto_convolve_numpy(s, k).astype(np.float32), f"ac k={k}, {frames} frames")
+    # clips shorter than the window, in a batch: a window that leaves a clip meets the next clip's frames (abi_call lays them end to end too)
+    short = draw(300 + k, 3, 2, 65)
+    want = np.stack([R.auto_convolve_numpy(c, k) for c in short]).astype(np.float32)
+    n += R.ulp_rule(abi_call("ac", short, (k,), device), want, f"ac k={k}, three clips of 2 frames")
     # longer than the longest window: frames that see a whole window and both edges.  The geometric mean of |N(0, 1)| is 0.53: scales
     # around 1.9 keep a product of 64 values within a few powers of e^9 of 1, so that log(1 + p) is neither p nor log(p) everywhere
     long = draw(7, 70, 65, lo=1.7, hi=2.1)
